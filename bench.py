@@ -1,8 +1,20 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X Sliding DFT engine (contract: see README/DESIGN).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 without a launcher: starts the N ranks itself, as a child)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                                                                  (N > 1 without a launcher: starts the N ranks itself, as a child)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: set-up (input, plan, output matrix), W warm-up steps, the K timed steps,
+the outputs of the last step when --dump-outputs is given, and the result line.  Everything else described below (the
+first-allocation region, the one-at-a-time steps, the analysis+synthesis region, the side measurements and the CPU
+baselines) runs only with --full.
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of `sdft_sdft_n` receives it: `dfts.npy`, rows
+of the DFT matrix as (rows, m, 2) real/imaginary pairs in the FD precision (every row when the matrix holds at most
+48 MiB, else a fixed seeded sample of rows that always includes the first and the last), and `dfts_rows.npy`, the
+(channel * n + t) index of each row, as float64.  The input is the deterministic sine sweep, so two builds run with the
+same arguments can be compared file for file.  (N > 1: rank 0's block of channels.)
 
 A "step" is one pass of the hot path over one batch of synthetic input that is already resident
 in HBM: `sdft_sdft_n` through the C-ABI of libsdft_hip.so on device pointers.
@@ -65,7 +77,37 @@ def parse_args():
     ap.add_argument("--no-extras", action="store_true", help="skip the side measurements outside the timed regions")
     ap.add_argument("--no-cpu-all-cores", action="store_true", help="skip the many-core CPU baseline of the batch share")
     ap.add_argument("--no-placement", action="store_true", help="take the output matrix as the first allocation comes (the line's first_allocation figure becomes the headline)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run every measurement beside the headline (first allocation, analysis+synthesis, "
+                                                        "side measurements, CPU baselines); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed under DIR as .npy files")
+    args = ap.parse_args()
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+    return args
+
+
+DUMP_BYTES = 48 << 20          # --dump-outputs: the rows written stay under this (the limit for the whole dump is 64 MB)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(directory, torch, np, matrix):
+    """The last timed step's DFT matrix as its caller receives it: every row if it fits in DUMP_BYTES, else a fixed seeded
+    sample of rows (the first and the last always among them), as real/imaginary pairs in the FD precision, and the rows'
+    indices.  Called after the timed region has been synchronised."""
+    m = matrix.shape[-1]
+    rows = matrix.reshape(-1, m)
+    total = rows.shape[0]
+    fd = np.float64 if matrix.dtype == torch.complex128 else np.float32
+    budget = max(DUMP_BYTES // (m * 2 * np.dtype(fd).itemsize), 2)
+    if total <= budget:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        pick = np.random.default_rng(DUMP_SEED).choice(np.arange(1, total - 1), size=budget - 2, replace=False)
+        idx = np.unique(np.concatenate([[0, total - 1], pick]).astype(np.int64))
+    sel = rows.index_select(0, torch.from_numpy(idx).to(rows.device))
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "dfts.npy"), torch.view_as_real(sel).cpu().numpy().astype(fd, copy=False))
+    np.save(os.path.join(directory, "dfts_rows.npy"), idx.astype(np.float64))
 
 
 def cpu_baseline(m, window, combo, n_cpu):
@@ -559,6 +601,8 @@ def launch_ranks(args) -> int:
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:]]
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", args.dump_outputs]         # (absolute: the ranks run in the repository's directory)
     print(f"[bench] --gpus {args.gpus} without a launcher: starting {args.gpus} ranks: {' '.join(cmd[1:9])} bench.py ...", file=sys.stderr)
     r = subprocess.run(cmd, env=env, cwd=ROOT)
     return r.returncode
@@ -705,70 +749,78 @@ def main():
     rate, secs = shard.job_throughput(units, elapsed, local_rank)
     local_elapsed = elapsed
     bytes_per_launch = count * n * (m * esz + np.dtype(td).itemsize)
-    # the same region into the process' first allocation (every rank; the same K and W)
-    # (every rank runs the region, placed or not: its barriers are collective)
-    first_elapsed, first_prof, _ = timed_region(out_first)
-    first_rate, first_secs = shard.job_throughput(units, first_elapsed, local_rank)
-    ff_ms, ff_calls = first_prof["forward"]
-    first_kernel_gbs = bytes_per_launch / (ff_ms / max(ff_calls, 1) * 1e-3) / 1e9 if ff_ms > 0 else 0.0
-    first_allocation = {
-        "value": round(first_rate / 1e6, 3), "unit": "Msamples/s", "ms_per_step": round(first_secs / args.steps * 1e3, 4),
-        "frac": round(first_kernel_gbs / HBM_PEAK_GBS, 4), "frac_is": "the kernel's algorithmic bytes / its HIP-event time / 8 TB/s, as roofline.frac",
-        "is": "the same K timed steps into the process' FIRST allocation of the matrix' size (a plain hipMalloc, what a host of the reference has: "
-              "sdft.h:605 'already allocated'); `value` is the matrix the library placed (buffer_placement)" if out is not out_first else
-              "this IS the headline: the matrix was not placed",
-    }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, np, out)      # (timed_region returned synchronised: the last step's matrix)
+
+    first_allocation, first_kernel_gbs = None, 0.0
+    if args.full:
+        # the same region into the process' first allocation (every rank; the same K and W)
+        # (every rank runs the region, placed or not: its barriers are collective)
+        first_elapsed, first_prof, _ = timed_region(out_first)
+        first_rate, first_secs = shard.job_throughput(units, first_elapsed, local_rank)
+        ff_ms, ff_calls = first_prof["forward"]
+        first_kernel_gbs = bytes_per_launch / (ff_ms / max(ff_calls, 1) * 1e-3) / 1e9 if ff_ms > 0 else 0.0
+        first_allocation = {
+            "value": round(first_rate / 1e6, 3), "unit": "Msamples/s", "ms_per_step": round(first_secs / args.steps * 1e3, 4),
+            "frac": round(first_kernel_gbs / HBM_PEAK_GBS, 4), "frac_is": "the kernel's algorithmic bytes / its HIP-event time / 8 TB/s, as roofline.frac",
+            "is": "the same K timed steps into the process' FIRST allocation of the matrix' size (a plain hipMalloc, what a host of the reference has: "
+                  "sdft.h:605 'already allocated'); `value` is the matrix the library placed (buffer_placement)" if out is not out_first else
+                  "this IS the headline: the matrix was not placed",
+        }
     if out is not out_first:
         del out_first                                         # (the side measurements need the room)
         torch.cuda.empty_cache()
 
-    # the same step one at a time (SURVEY.md 8d asks for a median): wall clock around one synchronised call each, and the
-    # kernel's own HIP events launch by launch; outside the contract's timed region above
     step_ms, kern_ms = [], []
-    for _ in range(min(args.steps, 20)):
-        sync()
-        ts = time.perf_counter()
-        plan.sdft(x, out)
-        sync()
-        step_ms.append((time.perf_counter() - ts) * 1e3)
-        pf = plan.profile()["forward"]
-        if pf[1]:
-            kern_ms.append(pf[0] / pf[1])
+    rate_rt = secs_rt = syn_rate = syn_read_only = None
+    i_avg = 0.0
+    if args.full:
+        # the same step one at a time (SURVEY.md 8d asks for a median): wall clock around one synchronised call each, and the
+        # kernel's own HIP events launch by launch; outside the contract's timed region above
+        for _ in range(min(args.steps, 20)):
+            sync()
+            ts = time.perf_counter()
+            plan.sdft(x, out)
+            sync()
+            step_ms.append((time.perf_counter() - ts) * 1e3)
+            pf = plan.profile()["forward"]
+            if pf[1]:
+                kern_ms.append(pf[0] / pf[1])
 
-    # second bracketed region, every rank: analysis + synthesis pairs (the metric string names both)
-    # (long synthesis calls find the fastest of their bit-identical forms and kinds of load on the first calls of a shape -- the ones that follow an
-    # analysis call separately from the ones that do not: logic::FormTuner; the pairs below are of the first kind, so pairs are what settles it)
-    y = plan.isdft(out)
-    for _ in range(TUNER_CALLS):
-        plan.sdft(x, out)
-        plan.isdft(out, y)
+        # second bracketed region, every rank: analysis + synthesis pairs (the metric string names both)
+        # (long synthesis calls find the fastest of their bit-identical forms and kinds of load on the first calls of a shape -- the ones that follow an
+        # analysis call separately from the ones that do not: logic::FormTuner; the pairs below are of the first kind, so pairs are what settles it)
+        y = plan.isdft(out)
+        for _ in range(TUNER_CALLS):
+            plan.sdft(x, out)
+            plan.isdft(out, y)
+            sync()
+        sync(); plan.profile()
+        shard.barrier(local_rank)
         sync()
-    sync(); plan.profile()
-    shard.barrier(local_rank)
-    sync()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        plan.sdft(x, out)
-        plan.isdft(out, y)
-    sync()
-    shard.barrier(local_rank)
-    sync()
-    elapsed_rt = time.perf_counter() - t1
-    prof_rt = plan.profile()
-    rate_rt, secs_rt = shard.job_throughput(units, elapsed_rt, local_rank)
-    i_ms, i_calls = prof_rt["inverse"]
-    i_avg = i_ms / max(i_calls, 1)
-    syn_rate = shard.sum_over_ranks(count * n / (i_avg * 1e-3) if i_avg > 0 else 0.0, local_rank)
-    # (outside both bracketed regions: the synthesis of a matrix that is only read -- call after call, no analysis in between; this rank's calls)
-    for _ in range(TUNER_CALLS):
-        plan.isdft(out, y)
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            plan.sdft(x, out)
+            plan.isdft(out, y)
         sync()
-    plan.profile()
-    for _ in range(5):
-        plan.isdft(out, y)
-    sync()
-    ro_ms, ro_calls = plan.profile()["inverse"]
-    syn_read_only = count * n / (ro_ms / max(ro_calls, 1) * 1e-3) if ro_ms > 0 else 0.0
+        shard.barrier(local_rank)
+        sync()
+        elapsed_rt = time.perf_counter() - t1
+        prof_rt = plan.profile()
+        rate_rt, secs_rt = shard.job_throughput(units, elapsed_rt, local_rank)
+        i_ms, i_calls = prof_rt["inverse"]
+        i_avg = i_ms / max(i_calls, 1)
+        syn_rate = shard.sum_over_ranks(count * n / (i_avg * 1e-3) if i_avg > 0 else 0.0, local_rank)
+        # (outside both bracketed regions: the synthesis of a matrix that is only read -- call after call, no analysis in between; this rank's calls)
+        for _ in range(TUNER_CALLS):
+            plan.isdft(out, y)
+            sync()
+        plan.profile()
+        for _ in range(5):
+            plan.isdft(out, y)
+        sync()
+        ro_ms, ro_calls = plan.profile()["inverse"]
+        syn_read_only = count * n / (ro_ms / max(ro_calls, 1) * 1e-3) if ro_ms > 0 else 0.0
 
     # roofline of the dominant kernel (this rank's launches; every rank runs the same shape)
     f_ms, f_calls = prof["forward"]
@@ -793,24 +845,17 @@ def main():
         "metric": "Msamples/s analysis+synthesis, m=1024 Hann fp64; achieved HBM GB/s vs peak",
         "value": round(rate / 1e6, 3),
         "unit": "Msamples/s",
-        "value_is": "analysis only (sdft_sdft_n), as configs[1] states; the analysis+synthesis pair rate is the next field",
-        "analysis_plus_synthesis_msamples_s": round(rate_rt / 1e6, 3),
-        "synthesis_msamples_s": round(syn_rate / 1e6, 3),
-        "synthesis_is": "the synthesis calls of the analysis + synthesis pairs (each reads the matrix the analysis has just written), by the plan's events; "
-                        "synthesis_matrix_only_read_msamples_s: call after call on a matrix nobody writes (this rank, outside the timed regions)",
-        "synthesis_matrix_only_read_msamples_s": round(syn_read_only / 1e6, 3),
+        "value_is": "analysis only (sdft_sdft_n), as configs[1] states; the analysis+synthesis pair rate is the next field (--full)",
         "n_gpus": n_gpus,
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(secs / args.steps * 1e3, 4),
-        "ms_per_step_median_one_at_a_time": round(float(np.median(step_ms)), 4) if step_ms else None,
-        "ms_per_step_analysis_plus_synthesis": round(secs_rt / args.steps * 1e3, 4),
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
         "dtype": "f64" if esz == 16 else "f32",
         "data": "synthetic",
-        "first_allocation": first_allocation,
+        "full": bool(args.full),
         "buffer_placement": placement,
         "config": {
             "workload": name,
@@ -832,8 +877,8 @@ def main():
             "per_gpu_msamples_s": round(rate / 1e6 / max(n_gpus, 1), 3),
             "ranks_with_a_placed_matrix": census["ranks_placed"],
             "placement_gbs_min_over_ranks": round(census["placement_gbs_min"], 1), "placement_gbs_max_over_ranks": round(census["placement_gbs_max"], 1),
-            "first_allocation_frac_min_over_ranks": round(census["first_allocation_frac_min"], 4),
-            "first_allocation_frac_max_over_ranks": round(census["first_allocation_frac_max"], 4),
+            "first_allocation_frac_min_over_ranks": round(census["first_allocation_frac_min"], 4) if args.full else None,
+            "first_allocation_frac_max_over_ranks": round(census["first_allocation_frac_max"], 4) if args.full else None,
             "placement_note": "buffer_placement is rank 0's; a rank whose arena did not fit took its first allocation (placement_gbs 0 in the minimum)",
         },
         "roofline": {
@@ -854,9 +899,20 @@ def main():
             "synthesis_read_gbs": round(bytes_per_launch / (i_avg * 1e-3) / 1e9, 1) if i_avg > 0 else None,
         },
     }
+    if args.full:
+        result.update({
+            "analysis_plus_synthesis_msamples_s": round(rate_rt / 1e6, 3),
+            "synthesis_msamples_s": round(syn_rate / 1e6, 3),
+            "synthesis_is": "the synthesis calls of the analysis + synthesis pairs (each reads the matrix the analysis has just written), by the plan's events; "
+                            "synthesis_matrix_only_read_msamples_s: call after call on a matrix nobody writes (this rank, outside the timed regions)",
+            "synthesis_matrix_only_read_msamples_s": round(syn_read_only / 1e6, 3),
+            "ms_per_step_median_one_at_a_time": round(float(np.median(step_ms)), 4) if step_ms else None,
+            "ms_per_step_analysis_plus_synthesis": round(secs_rt / args.steps * 1e3, 4),
+            "first_allocation": first_allocation,
+        })
 
     # side measurements outside the timed regions (rank 0, single GPU)
-    if rank == 0 and not distributed and not args.no_extras:
+    if args.full and rank == 0 and not distributed and not args.no_extras:
         extras = {}
         from sdft_amd import capi
         lib = capi.load()
@@ -1099,9 +1155,9 @@ def main():
             result["configs"] = baseline_configs(torch, np, SDFT, sine_sweep, local_rank, with_cpu=not args.no_cpu_baseline, placement=not args.no_placement)
         result["extras"] = extras
 
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(m, window, combo, args.cpu_samples)
-    elif rank == 0:
+    elif args.full and rank == 0:
         result["cpu_baseline"] = None
 
     # an N-GPU line must BE an N-GPU measurement: every rank in the collectives, and under RCCL every rank on a GPU of its own

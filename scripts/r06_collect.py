@@ -56,7 +56,7 @@ if tr and os.path.exists(und):
     regions = [("warm-up, placed matrix", W), ("TIMED REGION, placed matrix (the headline: roofline.avg_launch_ms)", K), ("warm-up, first allocation", W),
                ("timed region, first allocation (first_allocation)", K), ("one at a time, placed matrix", min(K, 20)), ("the rest (analysis + synthesis pairs, placed matrix)", len(d))]
     with open(os.path.join(P, "r06_bench_forward_launches.txt"), "w") as fh:
-        fh.write("# rocprofv3 --kernel-trace of `bench.py --steps %d --no-extras --no-cpu-baseline` (the command of r06_bench_n1e6_m1024_kernel_stats.csv): every launch of\n"
+        fh.write("# rocprofv3 --kernel-trace of `bench.py --full --steps %d --no-extras --no-cpu-baseline` (the command of r06_bench_n1e6_m1024_kernel_stats.csv): every launch of\n"
                  "# forward_rows_kernel<double, 1, 1, true, 1, 0, true, float, false>, milliseconds, in launch order, by the region of bench.py it belongs to.\n"
                  "# The line this run printed: roofline.avg_launch_ms %.4f (HIP events), first_allocation.frac %.4f.\n" % (K, line["roofline"]["avg_launch_ms"], line["first_allocation"]["frac"]))
         i = 0
@@ -87,7 +87,7 @@ for label, wf, ff, n, channels in (("single", "pmc_w/w_counter_collection.csv", 
     entries.append({"workload": label, "n": n, "m": 1024, "channels": channels, "bytes_per_launch": int(W * 1024 + 2 * F * 1024),
                     "WRITE_SIZE_KiB": W, "FETCH_SIZE_KiB_raw": F, "launches": len(w),
                     "algorithmic_bytes_per_launch": channels * n * (1024 * 16 + 4),
-                    "note": "rocprofv3 --pmc WRITE_SIZE and --pmc FETCH_SIZE in separate passes over bench.py --no-extras (round 6, forward_rows_kernel "
+                    "note": "rocprofv3 --pmc WRITE_SIZE and --pmc FETCH_SIZE in separate passes over bench.py --full --no-extras (round 6, forward_rows_kernel "
                             "dispatches only -- into the placed matrix and into the first allocation alike --, average per launch); counters are in KiB; "
                             "FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 reports half of wide reads)",
                     "source": "profiles/r06_bench_pmc.csv"})

@@ -79,8 +79,47 @@ def read_pcm24(path, count):
     return ((v + 0.5) / ((1 << 23) - 0.5)).astype(np.float32)      # reference test/wav.py:24-26
 
 
+# port-vs-reference cases of tests/test_oracle.py: (m, window, latency), input noise(5m + 7, seed=m), ragged hops
+TRACE_CASES = ((1, "hann", 1.0), (2, "blackman", 1.0), (4, "hamming", 0.5), (7, "blackman", 0.25),
+               (64, "hann", 1.0), (100, "boxcar", 0.5), (257, "blackman", 1.0))
+TRACE_HOPS = (1, 3, None, "2m-1", 10 ** 9)          # None = m
+
+
+def trace(plan, combo, m):
+    """Every array tests/test_oracle.py compares between the port and the reference, in order: the tables, the rows and
+    samples of each ragged hop across the roll-over, the state after them, and the rows of a first call after reset()."""
+    td = O.combo_types(combo)[0]
+    x = noise(5 * m + 7, seed=m, dtype=td)
+    out = list(plan.tables())
+    i = 0
+    for hop in TRACE_HOPS:
+        hop = m if hop is None else 2 * m - 1 if hop == "2m-1" else hop
+        xs = x[i:i + hop]; i += xs.size
+        if xs.size == 0:
+            break
+        d = plan.sdft(xs)
+        out += [d, plan.isdft(d)]
+    out += [np.asarray(a) for a in plan.state()]
+    plan.reset()
+    out.append(plan.sdft(x[:9]))
+    return out
+
+
+def trace_digests(arrays):
+    """sha256 of each array's dtype, shape and bytes: equal digests = bit-identical arrays."""
+    import hashlib
+    return [hashlib.sha256(f"{a.dtype.str}{a.shape}".encode() + np.ascontiguousarray(a).tobytes()).hexdigest() for a in arrays]
+
+
 def main():
     assert O.have_reference(), "build oracle/_ref first (make -C oracle)"
+    # 0. what the reference computes for the port-vs-reference cases, as digests (the arrays are compared bit for bit)
+    import json
+    digests = {combo: {f"{m}/{window}/{latency}": trace_digests(trace(O.Reference(m, window, latency, combo), combo, m))
+                       for m, window, latency in TRACE_CASES} for combo in O.COMBOS}
+    with open(os.path.join(HERE, "port_vs_reference.json"), "w") as fh:
+        json.dump(digests, fh, indent=1)
+        fh.write("\n")
     # 1. tiny exhaustive cases: every combo x window x latency, full matrices, packed in one file
     #    under keys "<combo>/<window>/<latency*100>/<m>/{x,d,y}"
     tiny = {}

@@ -76,7 +76,7 @@ def test_bench_starts_its_own_ranks():
 
 
 def test_single_rank_bench_line_contract():
-    res = run_bench(1, "--steps", "2", "--warmup", "1", "--samples", "65536", "--cpu-samples", "8192", "--no-cpu-all-cores")
+    res = run_bench(1, "--steps", "2", "--warmup", "1", "--samples", "65536", "--cpu-samples", "8192", "--no-cpu-all-cores", "--full")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in res, key
@@ -109,13 +109,42 @@ def test_single_rank_bench_line_contract():
     assert 0 < ns["sync"]["frac_of_peak_wall"] < 1 and 0 < ns["sync_first_allocation"]["frac_of_peak_wall"] < 1 and ns["buffer_placement"]["first"]["placed"] is True, ns
 
 
+def test_plain_bench_times_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) sets up, warms up, times the K steps and prints the line -- nothing beside the headline --
+    and --dump-outputs writes the matrix of the last timed step: rows of it (a seeded sample, first and last included,
+    under 64 MB) that the oracle, streamed through the same W + K calls of the same input, reproduces."""
+    import numpy as np
+    from oracle import oracle as O
+    from sdft_amd.signals import sine_sweep
+    n, m, warmup, steps = 8192, 1024, 1, 2
+    res = run_bench(1, "--steps", str(steps), "--warmup", str(warmup), "--samples", str(n), "--dump-outputs", str(tmp_path / "dump"))
+    assert res["steps"] == steps and res["warmup"] == warmup and res["full"] is False and res["ms_per_step"] > 0
+    assert res["metric"].startswith("Msamples/s") and res["unit"] == "Msamples/s" and res["higher_is_better"] is True and res["dtype"] == "f64"
+    assert abs(res["value"] - n / (res["ms_per_step"] * 1e-3) / 1e6) <= 0.02 * res["value"]
+    for key in ("first_allocation", "analysis_plus_synthesis_msamples_s", "cpu_baseline", "extras", "configs"):
+        assert key not in res, key
+    files = sorted(os.listdir(tmp_path / "dump"))
+    assert files == ["dfts.npy", "dfts_rows.npy"], files
+    assert sum(os.path.getsize(tmp_path / "dump" / f) for f in files) <= 64 << 20
+    d, rows = np.load(tmp_path / "dump" / "dfts.npy"), np.load(tmp_path / "dump" / "dfts_rows.npy")
+    assert d.dtype == np.float64 and rows.dtype == np.float64 and d.shape == (rows.size, m, 2) and rows.size < n
+    idx = rows.astype(np.int64)
+    assert idx[0] == 0 and idx[-1] == n - 1 and np.all(np.diff(idx) > 0)
+    ref = O.best(m, "hann", 1.0, "f32f64")
+    x = sine_sweep(n, channel=0, channels=1, dtype=np.float32)
+    for _ in range(warmup + steps):                          # the plan is a stream: every call continues it
+        want = ref.sdft(x)
+    got = d[..., 0] + 1j * d[..., 1]
+    assert np.abs(got - want[idx]).max() <= 1e-6 * np.abs(want[idx]).max()
+
+
 def test_eight_rank_bench_plumbing():
     """The N = 8 branch of bench.py (configs[4]: channels sharded over 8 ranks, weak scaling) has never seen 8 GPUs; so that
     the first such run cannot fail on plumbing it runs here with 8 ranks -- nccl where 8 GPUs exist, else all ranks on the
     one GPU over gloo: 2 channels per rank, short calls, ONE JSON line, value = all ranks' samples / slowest rank's time."""
     import torch
     backend = {} if torch.cuda.device_count() >= 8 else {"SDFT_BENCH_BACKEND": "gloo"}
-    res = run_bench(8, "--steps", "2", "--warmup", "1", "--samples", "4096", "--channels-per-gpu", "2", "--no-extras", env_extra=backend)
+    res = run_bench(8, "--steps", "2", "--warmup", "1", "--samples", "4096", "--channels-per-gpu", "2", "--no-extras", "--full", env_extra=backend)
     assert res["n_gpus"] == 8 and res["config"]["channels_total"] == 16 and res["config"]["samples_per_channel"] == 4096
     assert res["scaling"] == "weak" and res["cpu_baseline"] is None
     assert abs(res["value"] - 16 * 4096 / (res["ms_per_step"] * 1e-3) / 1e6) <= 0.02 * res["value"]
