@@ -1,5 +1,6 @@
 // spectrogram.cpp -- C++ host in the shape of the reference's cpp/examples/analysis.cpp (without the
-// plotting): sdft::SDFT<float, double> over a chirp, prints the strongest bin every 4000 samples.
+// plotting): sdft::SDFT<float, double> over a chirp, prints the strongest bin every 4000 samples.  Only those rows are
+// formed (sdft_every: 12 rows of 1000 bins instead of the 48000 x 1000 matrix).
 //
 //   make -C examples && ./examples/spectrogram
 
@@ -22,13 +23,16 @@ int main()
     x[i] = (float)std::sin(phi);
   }
   sdft::SDFT<float, double> sdft(m, sdft::Window::Hann, 1);
-  std::vector<std::complex<double>> dfts(n * m);
-  sdft.sdft(n, x.data(), dfts.data());
-  for (size_t t = 3999; t < n; t += 4000)
+  const size_t first = 3999, every = 4000;
+  std::vector<std::complex<double>> dfts((n - first + every - 1) / every * m);
+  const size_t rows = sdft.sdft_every(n, x.data(), every, first, dfts.data());
+  for (size_t r = 0; r < rows; ++r)
   {
+    const size_t t = first + r * every;
+    const std::complex<double>* row = dfts.data() + r * m;
     size_t best = 0;
     for (size_t k = 1; k < m; ++k)
-      if (std::abs(dfts[t * m + k]) > std::abs(dfts[t * m + best])) best = k;
+      if (std::abs(row[k]) > std::abs(row[best])) best = k;
     std::printf("t=%6zu  peak bin %4zu  ~%7.1f Hz  (instantaneous sweep frequency %7.1f Hz, window centre ~%zu samples earlier)\n",
                 t, best, (double)best * sr / (2.0 * m), (double)t / n * sr / 4, m);
   }

@@ -31,7 +31,8 @@ const char* sdft_hip_last_error(void);
   void sdft_hip_sdft_nd_##SUF(void* plan, std::size_t n, const TD* samples, void** dfts);           \
   TD sdft_hip_isdft_##SUF(void* plan, const void* dft);                                             \
   void sdft_hip_isdft_n_##SUF(void* plan, std::size_t n, const void* dfts, TD* samples);            \
-  void sdft_hip_isdft_nd_##SUF(void* plan, std::size_t n, const void** dfts, TD* samples);
+  void sdft_hip_isdft_nd_##SUF(void* plan, std::size_t n, const void** dfts, TD* samples);            \
+  long sdft_hip_sdft_every_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, void* dfts);
 SDFT_HPP_DECLARE(f32f64, float)
 SDFT_HPP_DECLARE(f32f32, float)
 SDFT_HPP_DECLARE(f64f64, double)
@@ -65,6 +66,7 @@ namespace sdft
       static TD isdft(void* p, const void* d) { return sdft_hip_isdft_##SUF(p, d); }                \
       static void isdft_n(void* p, std::size_t n, const void* d, TD* y) { sdft_hip_isdft_n_##SUF(p, n, d, y); } \
       static void isdft_nd(void* p, std::size_t n, const void** d, TD* y) { sdft_hip_isdft_nd_##SUF(p, n, d, y); } \
+      static long sdft_every_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, void* d) { return sdft_hip_sdft_every_n_##SUF(p, n, x, e, f, d); } \
     };
     SDFT_HPP_ABI(f32f64, float, double)
     SDFT_HPP_ABI(f32f32, float, float)
@@ -132,6 +134,23 @@ namespace sdft
     void sdft(const std::size_t nsamples, const T* samples, std::complex<F>** const dfts)
     {
       api::sdft_nd(plan_, nsamples, samples, reinterpret_cast<void**>(dfts));
+    }
+
+    /**
+     * Decimated analysis (sdft_hip_sdft_every_n): the rows sdft() would write for the samples first, first + every, ...
+     * < nsamples, dense in dfts; the plan's state advances over all samples.  Returns the number of rows written.
+     * Streaming: the next call's first is first + rows * every - nsamples (rows > 0), else first - nsamples.
+     **/
+    std::size_t sdft_every(const std::size_t nsamples, const T* samples, const std::size_t every, const std::size_t first,
+                           std::complex<F>* const dfts)
+    {
+      const long rows = api::sdft_every_n(plan_, nsamples, samples, every, first, dfts);
+      if (rows < 0)
+      {
+        const char* e = sdft_hip_last_error();
+        throw std::runtime_error(std::string("sdft_hip_sdft_every_n: ") + (e ? e : "failed"));
+      }
+      return static_cast<std::size_t>(rows);
     }
 
     /** Synthesizes a single sample from the given DFT vector (reference :205). */

@@ -147,6 +147,27 @@ typedef struct { const char* expr; const void* params; size_t nparams; } sdft_hi
 int sdft_hip_process_n(sdft_t* sdft, const sdft_size_t nsamples, const sdft_td_t* samples, sdft_td_t* const out,
                        const int op, const void* params, sdft_fdx_t* dfts) SDFT_HIP_SYMBOL(process_n);
 
+/* ---- decimated analysis --------------------------------------------------------------------------
+   sdft_hip_sdft_every_n writes only the rows sdft_sdft_n would write for the call's samples first, first + every,
+   first + 2*every, ... < nsamples -- a spectrogram at a hop of `every` samples -- without forming the others: the
+   recurrence still steps every sample, the demodulation, the window and the store happen at the grid's samples only.
+     rows = first < nsamples ? (nsamples - first + every - 1) / every : 0
+   dfts is [rows][dftsize]; batched plans: samples [channels][nsamples], dfts [channels][rows][dftsize].  Each row is the
+   row sdft_sdft_n gives (bit-identical wherever that call is: FD float, FD double with option "carry" = 1, calls shorter
+   than 512 samples; within 1e-11 relative otherwise), and the stream state afterwards -- accumulators, fiddles, delay line,
+   cursor -- is the one sdft_sdft_n of the same samples leaves: later sdft_sdft_n / sdft_isdft_n calls continue as if every
+   row had been computed.
+   The grid is local to the call (the plan keeps no grid state).  A host streaming in calls of any length passes, as the
+   next call's first,
+     first + rows * every - nsamples     (rows > 0)
+     first - nsamples                    (rows == 0)
+   and gets the rows one long call would give.  samples and dfts may each be host or device memory (option "async" applies
+   to device pointers); dfts may be NULL when the call keeps no row, and then only advances the stream.  every == 1 with
+   first == 0 is sdft_sdft_n itself.  Returns the number of rows written, or -1 with sdft_hip_last_error() set (a NULL plan,
+   every == 0, or dfts == NULL with rows > 0; the stream state is then untouched). */
+long sdft_hip_sdft_every_n(sdft_t* sdft, const sdft_size_t nsamples, const sdft_td_t* samples,
+                           const sdft_size_t every, const sdft_size_t first, sdft_fdx_t* dfts) SDFT_HIP_SYMBOL(sdft_every_n);
+
 /* ---- streams ---------------------------------------------------------------------------------
    Every plan owns a HIP stream.  Calls with host pointers always return with the output
    complete.  Calls with device pointers do too unless option "async" is 1; then they return after
@@ -261,7 +282,7 @@ double sdft_hip_time_hops(sdft_t* sdft, size_t hops, size_t hop, const sdft_td_t
    "relay_flow", "relay_groups", "chain_debug", "inverse_nt", "inverse_nt_skip_mb", "inverse_step", "inverse_ordered", "host_direct", "copy_streams" (sdft_capi.inc names what each selects);
    get_option "test_hooks" = 1 in that build.
    get_option additionally answers "tiles", "bins_per_lane", "row_slots", "last_chunks",
-   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop), "last_segments", "last_fused",
+   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis), "last_segments", "last_fused",
    "last_chain", "last_fused_exact", "last_fused_fold", "last_process_path" (1 fused kernel, 2 hop pair, 3 two-pass),
    "last_self", "last_inverse_nt" / "last_inverse_skip" (what the last synthesis launch used: non-temporal loads, rows read with ordinary loads),
    "cursor", "device", "ring_recoveries" (calls re-run with the serial carry pass after a poll loop of

@@ -82,6 +82,15 @@ int SDFT_FN(process_n)(void* p, size_t n, const SDFT_TD* x, SDFT_TD* y, int op, 
 {
   return p && P(p)->process_n(n, x, y, op, params, static_cast<fdx_t*>(dfts)) ? 0 : -1;
 }
+// decimated analysis: the rows of sdft_n at the call's samples first, first + every, ... < n; see sdft_hip.h
+long SDFT_FN(sdft_every_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, void* dfts)
+{
+  if (!p) { sdfthip::set_error("sdft_hip_sdft_every_n", "NULL plan"); return -1; }
+  size_t rows = 0;
+  if (!P(p)->sdft_every_n(n, x, every, first, static_cast<fdx_t*>(dfts), rows)) return -1;
+  if (rows > (size_t)LONG_MAX) { sdfthip::set_error("sdft_hip_sdft_every_n", "more rows than a long can count"); return -1; }
+  return (long)rows;
+}
 int SDFT_FN(set_stream)(void* p, void* hip_stream) { return p && P(p)->set_stream(static_cast<hipStream_t>(hip_stream)) ? 0 : -1; }
 // (a host that asks for the stream may queue work of its own behind a call: from here on every kernel of the plan is on it)
 void* SDFT_FN(get_stream)(void* p)

@@ -10,6 +10,7 @@
 #include "sdft_plan_logic.hpp"            // every decision that needs no HIP call (unit-tested on the CPU under sanitizers)
 #include "sdft_host_io.hpp"               // the caller's host memory: classification, registration, copies through pinned slots
 
+#include <limits.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -188,7 +189,7 @@ class Plan
   static constexpr size_t kSelfMax = (size_t)1 << 19;      // ... for calls of up to this many samples per channel (the fold of a chunk's past grows with n)
   long last_self = 0;
 
-  long last_kernel = 0;          // 1 = forward_kernel (independent tiles), 2 = forward_rows_kernel
+  long last_kernel = 0;          // 1 = forward_kernel (independent tiles), 2 = forward_rows_kernel, 3 = hop, 4 = forward_every_kernel
 
   // device-resident stream state
   DevBuf<fdx> d_tw, d_syn, d_wtab;
@@ -416,6 +417,13 @@ class Plan
     const logic::Chunking c = logic::choose_chunks(chunk_query(n, rows_kernel));
     chunks = c.chunks; len = c.len;
   }
+  void every_chunks(size_t n, long& chunks, long& len) const
+  {
+    logic::EveryQuery q;
+    q.n = n; q.channels = channels; q.tiles = tiles(); q.exact = carry_mode == CARRY_EXACT; q.forced_chunk = opt_chunk; q.compute_units = compute_units;
+    const logic::Chunking c = logic::choose_every_chunks(q);
+    chunks = c.chunks; len = c.len;
+  }
 
   // floor(2^32 / d) + 1, 0 for d <= 1: what flow_position divides a workgroup number by (ForwardArgs::inv_chunks, inv_channels)
   static unsigned inv32(unsigned d) { return d <= 1 ? 0u : (unsigned)((((unsigned long long)1) << 32) / d) + 1u; }
@@ -520,13 +528,14 @@ class Plan
     status_seen = now;
     return true;
   }
+  // every: decimated analysis (sdft_every_n) -- only the rows of that grid are stored, by forward_every_kernel
   bool forward_device(size_t n, const TD* x, size_t x_stride, fdx* out, size_t out_stride, fdx* const* rows,
-                      const FuseArgs<TD, FD>* fuse = nullptr)
+                      const FuseArgs<TD, FD>* fuse = nullptr, const EveryGrid* every = nullptr)
   {
     const size_t cursor0 = cursor;
     const int st0 = st_cur, hist0 = hist_cur;
     const bool canon0 = fid_canonical;
-    if (!forward_launch(n, x, x_stride, out, out_stride, rows, fuse))
+    if (!forward_launch(n, x, x_stride, out, out_stride, rows, fuse, every))
     {
       // a launch that failed half-way (a host expression that does not compile, a grid that does not fit, an allocation)
       // must not leave the stream half-advanced: what was queued wrote the OTHER buffer set and the workspace only
@@ -540,7 +549,7 @@ class Plan
     cursor = cursor0; st_cur = st0; hist_cur = hist0; fid_canonical = canon0;
     const long saved = opt_chain;
     opt_chain = 0;
-    const bool ok = forward_launch(n, x, x_stride, out, out_stride, rows, fuse) && (hipStreamSynchronize(stream) == hipSuccess);
+    const bool ok = forward_launch(n, x, x_stride, out, out_stride, rows, fuse, every) && (hipStreamSynchronize(stream) == hipSuccess);
     opt_chain = saved;
     ++ring_recoveries;
     // a recovered call is a valid call: it goes to the warning channel (and the counter), not to the error channel, so a
@@ -555,7 +564,7 @@ class Plan
   }
 
   bool forward_launch(size_t n, const TD* x, size_t x_stride, fdx* out, size_t out_stride, fdx* const* rows,
-                      const FuseArgs<TD, FD>* fuse = nullptr)
+                      const FuseArgs<TD, FD>* fuse = nullptr, const EveryGrid* every = nullptr)
   {
     if (n == 0 || nbins == 0) return true;
     const size_t nb = nbins, span = 2 * nbins;
@@ -563,7 +572,7 @@ class Plan
     flag_pending = false;                                    // only the hop kernel signals its completion
 
     calls.on_analysis(fuse != nullptr);                      // (which kind of host is calling: logic::CallPattern)
-    const bool use_rows = rows_kernel_ok(rows != nullptr);
+    const bool use_rows = !every && rows_kernel_ok(rows != nullptr);      // (the decimated analysis has the tile form only)
     long chunks, len;
     // (the folded fused kernel and the row-group forward kernel have the self-carried form)
     const bool folded_fuse = fuse && !wants_reference_order() && !fuse->store && opt_fold && coeff_ready;
@@ -588,12 +597,12 @@ class Plan
     }
     if (!self_form) pipe_this = false;
     if (out_hi) prev_out = logic::Range{out_lo, out_hi};
-    choose_chunks(n, chunks, len, use_rows);
+    if (every) every_chunks(n, chunks, len); else choose_chunks(n, chunks, len, use_rows);
     const long ntiles = tiles(), inter = interior_lanes();
-    last_kernel = use_rows ? 2 : 1;
+    last_kernel = every ? 4 : use_rows ? 2 : 1;
     last_chunks = chunks; last_chunk_len = len; last_tiles = ntiles; last_interior = inter;
     last_segments = 1; last_fused = 0; last_self = 0; last_chain = 0;
-    if (chunks == 1 && opt_hop_kernel && nbins >= 2 && !fuse) { if (!pipe_join()) return false; return forward_hop(n, x, x_stride, out, out_stride, rows); }
+    if (chunks == 1 && opt_hop_kernel && nbins >= 2 && !fuse && !every) { if (!pipe_join()) return false; return forward_hop(n, x, x_stride, out, out_stride, rows); }
 
     const bool exact = (carry_mode == CARRY_EXACT);
     // self-carried chunks: every workgroup derives its carry-in from the raw samples (fold + one FFT in LDS) and forms
@@ -680,7 +689,7 @@ class Plan
       // once the relays are through.  The forward launch is held back (relay_gate_kernel polls a word every relay workgroup
       // bumps at its start) until the relays are resident: a forward workgroup that waits for a relay which cannot start
       // would be a deadlock -- every wait in the kernels is bounded all the same, and a time-out re-runs the call (forward_device).
-      flow = use_chain && opt_relay_flow && opt_segments <= 0 && (fuse ? true : use_rows) && gate_ok();
+      flow = use_chain && opt_relay_flow && opt_segments <= 0 && (fuse ? true : use_rows) && !every && gate_ok();
       if (flow) segments = 1;
       if (flow && started_target > (1u << 30))
       {
@@ -870,6 +879,7 @@ class Plan
           return false;
       }
       else if (use_rows) launch_forward_rows(fa, (unsigned)(channels * (size_t)(j1 - j0)), (unsigned)(row_waves() * kWave), fused);
+      else if (every) { if (!grid_fits(blocks)) return false; launch_forward_every(fa, *every, (unsigned)blocks); }
       else launch_forward(fa, (unsigned)blocks);
       SDFT_TRY(hipGetLastError());
     }

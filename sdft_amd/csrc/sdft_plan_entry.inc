@@ -116,6 +116,68 @@
     return synchronize();
   }
 
+  // decimated analysis (sdft_hip_sdft_every_n): the rows sdft_n would write at the call's samples first, first + every, ...
+  // < n, dense [channels][rows][N]; the stream state afterwards is the one sdft_n leaves.  `rows` receives the row count.
+  // Never resident, pipelined or fused: whatever is in flight is retired / joined first, then one forward_launch on the
+  // plan's stream (forward_every_kernel).  Host memory goes through device scratch and the plan's pinned copy path, in
+  // time segments that keep both scratch buffers within stage_bytes.
+  bool sdft_every_n(size_t n, const TD* x, size_t every, size_t first, fdx* dfts, size_t& rows)
+  {
+    static const char* fn = "sdft_hip_sdft_every_n";
+    rows = 0;
+    if (every == 0) { set_error(fn, "every must be at least 1"); return false; }
+    rows = logic::every_rows(n, every, first);
+    if (rows > 0 && !dfts) { set_error(fn, "dfts is NULL but the call keeps rows"); return false; }
+    if (n == 0 || nbins == 0) return true;
+    if (every == 1 && first == 0) return sdft_n(n, x, dfts);      // every row: the analysis itself
+    if (!bind()) return false;
+    if (!pipe_join()) return false;
+    if (every > n) every = n;                                // (the same grid: at most one row; keeps first + k * every in range)
+    const size_t nb = nbins;
+    const bool xd = on_device(x);
+    const bool od = rows == 0 || on_device(dfts);
+    const size_t row_bytes = channels * nb * sizeof(fdx);
+    if (xd && od)
+    {
+      const EveryGrid g{(unsigned long long)every, (unsigned long long)first};
+      if (!forward_device(n, x, n, dfts, rows * nb, nullptr, nullptr, &g)) return false;
+      return finish(rows * row_bytes);
+    }
+    // host memory: segments of at most seg samples, each one forward launch on device scratch
+    size_t seg = n;
+    if (!od) seg = std::min(seg, std::max<size_t>(1, stage_bytes / std::max<size_t>(row_bytes, 1)) * every);
+    if (!xd) seg = std::min(seg, std::max<size_t>((size_t)logic::kHopSamples, stage_bytes / (channels * sizeof(TD))));
+    if (!xd && !d_stage_td.reserve(channels * seg)) return false;
+    if (!od && !d_stage_fdx.reserve(channels * ((seg + every - 1) / every) * nb)) return false;
+    for (size_t t = 0; t < n; t += seg)
+    {
+      const size_t m = std::min(seg, n - t);
+      const size_t f = logic::every_first_from(t, every, first);
+      const size_t r = logic::every_rows(m, every, f);
+      const size_t r0 = r ? (t + f - first) / every : 0;    // the segment's first row in the call's grid
+      const TD* xs; size_t xstride;
+      if (xd) { xs = x + t; xstride = n; }
+      else
+      {
+        if (!copy2d(d_stage_td.p, m * sizeof(TD), x + t, n * sizeof(TD), m * sizeof(TD), hipMemcpyHostToDevice)) return false;
+        xs = d_stage_td.p; xstride = m;
+      }
+      const EveryGrid g{(unsigned long long)every, (unsigned long long)f};
+      if (od)
+      {
+        if (!forward_device(m, xs, xstride, r ? dfts + r0 * nb : nullptr, rows * nb, nullptr, nullptr, &g)) return false;
+      }
+      else
+      {
+        if (!forward_device(m, xs, xstride, d_stage_fdx.p, r * nb, nullptr, nullptr, &g)) return false;
+        if (r && !copy2d(dfts + r0 * nb, rows * nb * sizeof(fdx), d_stage_fdx.p, r * nb * sizeof(fdx), r * nb * sizeof(fdx), hipMemcpyDeviceToHost))
+          return false;
+      }
+      SDFT_TRY(hipStreamSynchronize(stream));                // scratch buffers are reused; host memory is complete on return
+    }
+    return synchronize();
+  }
+
   // array-of-row-pointers variant (sdft.h:622-628).  Single-channel plans only: the reference's
   // table has one pointer per sample, a batched layout for it is not defined.
   bool single_channel(const char* fn)

@@ -298,6 +298,18 @@
   {
     if (fa.out_rows) launch_forward_t<true>(fa, blocks); else launch_forward_t<false>(fa, blocks);
   }
+  void launch_forward_every(const ForwardArgs<FD>& fa, const EveryGrid& g, unsigned blocks)
+  {
+    constexpr int BPL = sizeof(fdx) == 16 ? 1 : 2;
+    const dim3 gr(blocks), b(kBlock);
+    switch (window)
+    {
+      case WIN_HANN:     hipLaunchKernelGGL((forward_every_kernel<FD, BPL, WIN_HANN>), gr, b, 0, stream, fa, g); break;
+      case WIN_HAMMING:  hipLaunchKernelGGL((forward_every_kernel<FD, BPL, WIN_HAMMING>), gr, b, 0, stream, fa, g); break;
+      case WIN_BLACKMAN: hipLaunchKernelGGL((forward_every_kernel<FD, BPL, WIN_BLACKMAN>), gr, b, 0, stream, fa, g); break;
+      default:           hipLaunchKernelGGL((forward_every_kernel<FD, BPL, WIN_BOXCAR>), gr, b, 0, stream, fa, g); break;
+    }
+  }
 
 
   // rows in step (inverse_rows_body): float samples from double bins at latency 1 (the term of a bin is +-re: one register per

@@ -134,6 +134,64 @@ inline Chunking choose_chunks(const ChunkQuery& q)
   return r;
 }
 
+// ---- decimated analysis (sdft_hip_sdft_every_n) --------------------------------------------------------------------------------
+// Rows a call of n samples keeps: those at first, first + every, ... < n (the grid is call-local: every == 0 keeps none, the
+// entry point refuses it).  A streaming host passes every_next_first(...) as the next call's first.
+inline size_t every_rows(size_t n, size_t every, size_t first)
+{
+  return (every != 0 && first < n) ? (n - first - 1) / every + 1 : 0;          // (= ceil((n - first) / every), without overflow)
+}
+inline size_t every_next_first(size_t n, size_t every, size_t first)
+{
+  const size_t rows = every_rows(n, every, first);
+  return rows ? first + rows * every - n : (first >= n ? first - n : 0);
+}
+// first of the part of a call that starts at sample t0 (host-pointer segments): the grid's first sample at or after t0, from t0
+inline size_t every_first_from(size_t t0, size_t every, size_t first)
+{
+  if (first >= t0) return first - t0;
+  const size_t past = (t0 - first) % every;
+  return past ? every - past : 0;
+}
+// Time chunks of forward_every_kernel.  The kernel stores a row every `every` samples only: it is bound by the recurrence's
+// arithmetic (about ten unfused operations per bin and sample), not by HBM.  So the grid is sized by waves, not by bytes: enough
+// (chunk x tile x channel) waves for kEveryWavesPerSimd per SIMD of every CU, chunks not shorter than kEveryMinLen samples (each
+// chunk pays a carry-in and a share of the carry pre-pass), calls below kHopSamples in one chunk (bit-identical, as the hop
+// kernel's).  Exact carries: whole 128-sample blocks of the relay form.  The recurrence is a chain of dependent operations per
+// wave, so it takes many waves to cover the latency: configs[1] at every = 100, 863 chunks of 1160 samples (this choice) 0.541 ms,
+// chunks of 1024 / 2048 / 4632 (4 waves per SIMD) samples 0.524 / 0.542 / 0.582 ms (profiles/every_rates.txt).
+constexpr long kEveryWavesPerSimd = 16, kEverySimds = 4, kEveryMinLen = 256;
+struct EveryQuery
+{
+  size_t n = 0, channels = 1;
+  long tiles = 1;                // bin tiles of the independent-tile geometry
+  bool exact = false;
+  long forced_chunk = 0;         // option "chunk"
+  int compute_units = 256;
+};
+inline Chunking choose_every_chunks(const EveryQuery& q)
+{
+  Chunking r;
+  const size_t n = q.n;
+  if (n == 0) { r.chunks = 1; r.len = 0; return r; }
+  long len;
+  if (q.forced_chunk > 0) len = !q.exact ? ((q.forced_chunk + kSumBlockLen - 1) / kSumBlockLen) * kSumBlockLen : q.forced_chunk;
+  else
+  {
+    if (n < (size_t)kHopSamples) { r.chunks = 1; r.len = (long)n; return r; }
+    const long target = (long)std::max(q.compute_units, 1) * kEverySimds * kEveryWavesPerSimd;
+    const long per = std::max(1L, (long)std::max<size_t>(q.channels, 1) * std::max(1L, q.tiles));
+    long want = (target + per - 1) / per;
+    want = std::max(1L, std::min(want, (long)(n / (size_t)kEveryMinLen)));
+    len = (long)((n + (size_t)want - 1) / (size_t)want);
+    len = ((len + kTimeGroup - 1) / kTimeGroup) * kTimeGroup;
+    if (q.exact) len = ((len + 127) / 128) * 128;
+  }
+  len = std::max(1L, std::min(len, (long)n));
+  r.len = len; r.chunks = (long)((n + (size_t)len - 1) / (size_t)len);
+  return r;
+}
+
 // ---- exact carries, relay form: block length = seed distance -----------------------------------------------------------
 // divides 2N and the chunk length; L products live in L registers per lane (128 at FD float, 64 register pairs at FD double);
 // the seed table (fid at every L-th cursor) stays below 256 MiB.  0: no block length fits (serial pass).

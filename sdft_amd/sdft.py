@@ -212,6 +212,41 @@ class SDFT:
         self.api.check()
         return out
 
+    def sdft_every(self, x, every: int, first: int = 0, out=None):
+        """Decimated analysis (``sdft_hip_sdft_every_n``): the rows :meth:`sdft` would return for the samples ``first``,
+        ``first + every``, ... < n -> array of shape (rows, dftsize) [(channels, rows, dftsize) if batched], numpy for numpy
+        input, a device tensor for a device tensor.  The plan's state advances over all n samples, as with :meth:`sdft`.
+        The grid is local to the call: a streaming host passes :func:`every_next_first` as the next call's ``first``."""
+        self.api.clear()
+        every, first = int(every), int(first)
+        if every < 1 or first < 0:
+            raise ValueError(f"every must be >= 1 and first >= 0, got every={every}, first={first}")
+        if _is_tensor(x):
+            torch = _torch()
+            n = self._shape_x(x.shape)
+            self._check_tensor(x, "samples", self.td)
+            rows = every_rows(n, every, first)
+            shape = (rows, self.dftsize) if x.dim() == 1 else (self.channels, rows, self.dftsize)
+            if out is None:
+                out = torch.empty(shape, dtype=getattr(torch, np.dtype(self.fdx).name), device=x.device)
+            self._check_tensor(out, "out", self.fdx, shape)
+            got = self.api.sdft_every_n(self._p, n, C.c_void_p(x.data_ptr()), every, first, C.c_void_p(out.data_ptr() if rows else None))
+        else:
+            x = np.ascontiguousarray(x, dtype=self.td)
+            n = self._shape_x(x.shape)
+            rows = every_rows(n, every, first)
+            shape = (rows, self.dftsize) if x.ndim == 1 else (self.channels, rows, self.dftsize)
+            if out is None:
+                out = np.empty(shape, dtype=self.fdx)
+            assert out.flags.c_contiguous and out.shape == shape and out.dtype == self.fdx
+            got = self.api.sdft_every_n(self._p, n, C.c_void_p(x.ctypes.data), every, first, C.c_void_p(out.ctypes.data if rows else None))
+        if got < 0:
+            self.api.check()
+            raise SdftHipError("sdft_hip_sdft_every_n failed")
+        self.api.check()
+        assert got == rows, (got, rows)
+        return out
+
     def isdft(self, dfts, out=None):
         """Synthesise samples from a DFT matrix (n, dftsize) [(channels, n, dftsize)]."""
         self.api.clear()
@@ -319,6 +354,17 @@ class SDFT:
             raise SdftHipError("sdft_hip_process_n failed")
         self.api.check()
         return out
+
+
+def every_rows(n: int, every: int, first: int) -> int:
+    """Rows a decimated analysis call of n samples keeps (sdft_hip_sdft_every_n)."""
+    return (n - first + every - 1) // every if first < n else 0
+
+
+def every_next_first(n: int, every: int, first: int) -> int:
+    """The ``first`` of the next call when a stream is analysed in calls of any length on one row grid."""
+    rows = every_rows(n, every, first)
+    return first + rows * every - n if rows else first - n
 
 
 def plan_tables(dftsize: int, latency: float = 1.0, combo: str = "f32f64"):
