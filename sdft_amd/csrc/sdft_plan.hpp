@@ -93,6 +93,7 @@ struct Tables
 static_assert(logic::kLanes == kWave && logic::kRowWaves == kRowWavesMax && logic::kRowSlots == kRowSlotsMax && logic::kTimeGroup == kGroup &&
               logic::kSumBlockLen == kSumBlock && logic::kHopSamples == kHopMax && kGroup % kRowGroup == 0, "sdft_plan_logic.hpp and the kernels disagree");
 static_assert(logic::kWindowHann == WIN_HANN && logic::kWindowBlackman == WIN_BLACKMAN && logic::kWindowBoxcar == WIN_BOXCAR, "window numbering");
+static_assert(logic::kWavesPerBlock == kWavesPerBlock && logic::kProcGroup == kProcGroup && logic::kProcRow == kProcRow, "sdft_plan_logic.hpp and the kernels disagree");
 static_assert(sizeof(logic::Radices) == sizeof(RadixList), "radix lists");
 
 enum CarryMode : int { CARRY_FAST = 0, CARRY_EXACT = 1 };
@@ -117,12 +118,10 @@ class Plan
 
   // options
   int carry_mode = sizeof(FD) == 8 ? CARRY_FAST : CARRY_EXACT;
-  static constexpr size_t kFlagMax = (size_t)1 << 24;       // bin-samples up to which a row-group analysis call signals its own completion
 #ifdef SDFT_SELF_STAMPS
   long opt_self_stamps = 0;                                // development builds: device address of 8 stamp words
 #endif
   long opt_inverse_verify = 1, last_inverse_form = 0;      // launch_inverse
-  static constexpr size_t kInverseVerifyMax = 500000;      // rows up to which the tree sum with the rounding-interval proof serves sdft_isdft_n (beyond: the streaming kernel)
   bool rtc_failed = false;                                 // launch_inverse returns void: a failed run-time compilation is reported here
   std::string user_expr;                                   // sdft_hip_process_n with an expression: the statements of the call in flight
   template <typename T> static const char* type_name() { return sizeof(T) == 8 ? "double" : "float"; }
@@ -185,8 +184,7 @@ class Plan
                                  // -1 = in order exactly when the host asked for exact carries at FD double (carry = 1)
   long last_fused_exact = 0, last_fused_fold = 0, last_process_path = 0;   // last_process_path: 1 fused kernel, 2 hop pair, 3 two-pass segments
   long opt_spin = 1;             // synchronous short calls poll the stream instead of sleeping on it
-  long opt_self = 1;             // chunk-parallel FD double calls, 2N a power of two: self-carried chunks (no pre-pass launches)
-  static constexpr size_t kSelfMax = (size_t)1 << 19;      // ... for calls of up to this many samples per channel (the fold of a chunk's past grows with n)
+  long opt_self = 1;             // chunk-parallel FD double calls, 2N a power of two: self-carried chunks (no pre-pass launches; logic::kSelfMax)
   long last_self = 0;
 
   long last_kernel = 0;          // 1 = forward_kernel (independent tiles), 2 = forward_rows_kernel, 3 = hop, 4 = forward_every_kernel
@@ -412,18 +410,6 @@ class Plan
     q.forced_chunk = opt_chunk; q.row_waves = row_waves(); q.tiles = tiles(); q.compute_units = compute_units;
     return q;
   }
-  void choose_chunks(size_t n, long& chunks, long& len, bool rows_kernel = false) const
-  {
-    const logic::Chunking c = logic::choose_chunks(chunk_query(n, rows_kernel));
-    chunks = c.chunks; len = c.len;
-  }
-  void every_chunks(size_t n, long& chunks, long& len) const
-  {
-    logic::EveryQuery q;
-    q.n = n; q.channels = channels; q.tiles = tiles(); q.exact = carry_mode == CARRY_EXACT; q.forced_chunk = opt_chunk; q.compute_units = compute_units;
-    const logic::Chunking c = logic::choose_every_chunks(q);
-    chunks = c.chunks; len = c.len;
-  }
 
   // floor(2^32 / d) + 1, 0 for d <= 1: what flow_position divides a workgroup number by (ForwardArgs::inv_chunks, inv_channels)
   static unsigned inv32(unsigned d) { return d <= 1 ? 0u : (unsigned)((((unsigned long long)1) << 32) / d) + 1u; }
@@ -437,7 +423,7 @@ class Plan
 
   // ---- exact carries, relay form: block length / seed table -----------------------------------------
   unsigned relay_block(long len) const { return logic::relay_block(nbins, len, sizeof(FD), sizeof(fdx), opt_chain_L); }
-  // flow mode of the relay form (see forward_launch)
+  // flow mode of the relay form (logic::forward_route)
   long opt_relay_flow = 1, last_flow = 0;
   DevBuf<unsigned> d_ready;
   unsigned ready_seq = 0;
@@ -447,12 +433,13 @@ class Plan
   // start would be a deadlock until the bounded polls run out): a one-wave gate kernel on the forward stream polls the
   // word until the relays of the call are resident (round 3 used hipStreamWaitValue32 for this: the runtime's wait packet
   // took 135 us to notice -- profiles/r04_relay_gate_trace.txt)
+  // (asked by logic::forward_route before the call's workspace: the word is zeroed by the first flow call's carries stage, as
+  // when the counter would wrap)
   bool gate_ok()
   {
     if (d_started) return true;
     if (hipMalloc((void**)&d_started, 8) != hipSuccess) { (void)hipGetLastError(); d_started = nullptr; return false; }
-    if (hipMemset(d_started, 0, 8) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(d_started); d_started = nullptr; return false; }
-    started_target = 0;
+    started_target = ~0u;
     return true;
   }
   // relays (32 bins of a channel each), waves per relay.  (Two relays per workgroup -- the kernel has the form -- were measured
@@ -563,194 +550,138 @@ class Plan
     return ok;
   }
 
+  logic::ForwardQuery forward_query(size_t n, const fdx* out, size_t out_stride, fdx* const* rows, const FuseArgs<TD, FD>* fuse, const EveryGrid* every) const
+  {
+    logic::ForwardQuery q;
+    q.n = n; q.nbins = nbins; q.channels = channels; q.fd_bytes = sizeof(FD); q.fdx_bytes = sizeof(fdx);
+    q.window = window; q.compute_units = compute_units; q.cursor = cursor; q.exact = carry_mode == CARRY_EXACT; q.fid_canonical = fid_canonical;
+    q.fuse = fuse != nullptr; q.fuse_store = fuse && fuse->store; q.reference_order = fuse && wants_reference_order(); q.coeff_ready = coeff_ready;
+    q.every = every != nullptr; q.row_pointers = rows != nullptr; q.out = reinterpret_cast<uintptr_t>(out); q.out_stride = out_stride;
+    q.analysis_batch = calls.analysis_batch; q.pipe_wanted = pipe_wanted(nullptr); q.prev_out = prev_out;
+    q.rows_kernel = opt_rows_kernel; q.row_slots_max = opt_row_slots_max; q.interior = opt_interior; q.chunk = opt_chunk; q.self = opt_self;
+    q.fused = opt_fused; q.fold = opt_fold; q.fft_carry = opt_fft_carry; q.hop_kernel = opt_hop_kernel; q.chain = opt_chain; q.chain_L = opt_chain_L;
+    q.relay_flow = opt_relay_flow; q.segments = opt_segments; q.xcd_map = opt_xcd_map; q.rows_f32 = opt_rows_f32; q.pipeline = opt_pipeline;
+    return q;
+  }
+
+  // The route (logic::forward_route) decides; this runs it: the hop and self-carried routes in a launch of their own, every
+  // other route as delta -> carries -> forward
   bool forward_launch(size_t n, const TD* x, size_t x_stride, fdx* out, size_t out_stride, fdx* const* rows,
                       const FuseArgs<TD, FD>* fuse = nullptr, const EveryGrid* every = nullptr)
   {
     if (n == 0 || nbins == 0) return true;
-    const size_t nb = nbins, span = 2 * nbins;
     SDFT_TRY(hipSetDevice(device));
     flag_pending = false;                                    // only the hop kernel signals its completion
-
     calls.on_analysis(fuse != nullptr);                      // (which kind of host is calling: logic::CallPattern)
-    const bool use_rows = !every && rows_kernel_ok(rows != nullptr);      // (the decimated analysis has the tile form only)
-    long chunks, len;
-    // (the folded fused kernel and the row-group forward kernel have the self-carried form)
-    const bool folded_fuse = fuse && !wants_reference_order() && !fuse->store && opt_fold && coeff_ready;
-    // pipelined calls (forward_self): decided here because they take the self-carried form at any length and cut time differently
-    pipe_this = false;
-    uintptr_t out_lo = 0, out_hi = 0;
-    if (!fuse && !rows && out && use_rows)
-    {
-      out_lo = reinterpret_cast<uintptr_t>(out); out_hi = out_lo + ((channels - 1) * out_stride + n * nb) * sizeof(fdx);
-      // (calls of a few thousand rows gain a microsecond from it and cost the host seven runtime calls instead of one,
-      // 19 against 3 us: n = 4096, m = 1024: 25.6 against 26.4 us per call; from n = 8192 on 30.4 against 32.9)
-      pipe_this = calls.analysis_batch && pipe_wanted(nullptr) && self_eligible(n, false, true) && n < ((size_t)1 << 31) && channels * n * nb >= ((size_t)6 << 20) &&
-                  !logic::overlap(out_lo, out_hi, prev_out) && logic::pipeline_pays(chunk_query(n, true), opt_pipeline);
-    }
-    bool self_form = self_eligible(n, fuse != nullptr, pipe_this) && (fuse ? folded_fuse : use_rows);
-    if (self_form && fuse)
-    {
-      // the fused kernel folds into its transpose tiles: the 2N cells have to fit them, and it has one or two bins per lane
-      long pw, ps;
-      process_geometry(opt_fused != 0, pw, ps, n);
-      self_form = ps <= 2 && self_cells() * sizeof(fdx) <= process_tiles_bytes((unsigned)(pw * kWave));
-    }
-    if (!self_form) pipe_this = false;
-    if (out_hi) prev_out = logic::Range{out_lo, out_hi};
-    if (every) every_chunks(n, chunks, len); else choose_chunks(n, chunks, len, use_rows);
-    const long ntiles = tiles(), inter = interior_lanes();
-    last_kernel = every ? 4 : use_rows ? 2 : 1;
-    last_chunks = chunks; last_chunk_len = len; last_tiles = ntiles; last_interior = inter;
-    last_segments = 1; last_fused = 0; last_self = 0; last_chain = 0;
-    if (chunks == 1 && opt_hop_kernel && nbins >= 2 && !fuse && !every) { if (!pipe_join()) return false; return forward_hop(n, x, x_stride, out, out_stride, rows); }
-
-    const bool exact = (carry_mode == CARRY_EXACT);
-    // self-carried chunks: every workgroup derives its carry-in from the raw samples (fold + one FFT in LDS) and forms
-    // its own differences -- the call is ONE launch.  Kernels that have the form: the row-group forward kernel and the
-    // folded fused kernel, FD double, 2N a power of two of at most 4096 cells.
-    // (the fold of a chunk's past costs t0 / threads loads: hidden behind the other workgroups' row stores in the
-    // analysis, which is bound by HBM -- n = 1e6: 2.885 -> 2.853 ms -- but not in the fused call, which is bound by
-    // instruction issue: n = 48000: 45.9 -> 42.3 us, n = 131072: 99 -> 117 us; hence self_eligible's limit for it)
-    // (2N = 2/3/5-smooth: five Stockham stages with table look-ups -- n = 12000, N = 1000, chunks of 64 samples: 47 us with
-    // the pre-pass, 55 us self-carried; n = 48000, chunks of 192: 192 -> 173 us)
-    const bool self = self_form && chunks > 1 && ((span & (span - 1)) == 0 || len > 64);
-    last_self = self;
-    if (self) return forward_self(n, x, x_stride, out, out_stride, chunks, len, fuse);
+    const logic::ForwardRoute r = logic::forward_route(forward_query(n, out, out_stride, rows, fuse, every), [this] { return gate_ok(); });
+    pipe_this = r.pipelined;
+    if (r.out.hi) prev_out = r.out;
+    last_kernel = r.kernel; last_chunks = r.chunks; last_chunk_len = r.len; last_tiles = r.tiles; last_interior = r.interior;
+    last_segments = r.segments; last_fused = r.fused; last_self = r.self; last_chain = r.carry == logic::CARRY_RELAY ? 3 : 0;
+    if (r.kernel == logic::FK_HOP) { if (!pipe_join()) return false; return forward_hop(n, x, x_stride, out, out_stride, rows); }
+    if (r.self) return forward_self(n, x, x_stride, out, out_stride, r.chunks, r.len, fuse);
     if (!pipe_join()) return false;
-    // exact carries: relay form (seed table + identical waves that take the blocks of cL steps in turn, a block's products in
-    // registers) while the serial pass would leave most SIMDs idle; the plain serial pass when bins x channels already
-    // fill the chip.  The chunk grid is shifted so that every chunk but the first starts on a block boundary of the
-    // cursor (chunk j starts at sample j*len - shift; one more chunk may be needed for the tail)
-    const size_t serial_waves = ((nb + kWave / 2 - 1) / (kWave / 2)) * channels;
-    const bool chain_ok = exact && chunks > 1 && opt_chain && fid_canonical && (opt_chain >= 2 || serial_waves <= 1024);
-    const unsigned cL = (chain_ok && n < ((size_t)1 << 31)) ? relay_block(len) : 0u;
-    const bool use_chain = cL != 0;
-    const unsigned shift = use_chain ? (unsigned)(cursor % cL) : 0u;
-    if (shift) { chunks = (long)((n + shift + (size_t)len - 1) / (size_t)len); last_chunks = chunks; }
 
+    // workspace
+    const size_t nb = nbins, span = 2 * nbins;
     if (!d_delta.reserve(channels * n + 128)) return false;     // + slack: the exact pass prefetches bursts past a run
-    if (!d_carry.reserve(channels * (size_t)chunks * nb)) return false;
-    last_chain = use_chain ? 3 : 0;
-    if ((exact || chunks == 1) && !use_chain && !d_seed.reserve(channels * (size_t)chunks * nb)) return false;
-    if (use_chain && !ensure_fseed(cL)) return false;
-
-    // form of the chunk-parallel partial sums: FFT when 2N is a power of two or 2/3/5-smooth (and fits LDS) -- but
-    // direct sums for chunks of up to 64 samples, which need no barriers (n = 1024 / 4096, N = 1024: 28.0 / 32.1 ->
-    // 24.2 / 28.3 us per call even with one launch more) -- and direct sums for every other size
-    enum { SUMS_DIRECT = 0, SUMS_FFT2 = 1, SUMS_FFT_MIXED = 2 };
-    int sums_form = SUMS_DIRECT;
-    RadixList rl; rl.count = 0;
+    if (!d_carry.reserve(channels * (size_t)r.chunks * nb)) return false;
+    if (r.use_seed && !r.relay_L && !d_seed.reserve(channels * (size_t)r.chunks * nb)) return false;
+    if (r.relay_L && !ensure_fseed(r.relay_L)) return false;
+    if (r.segments > 1 || r.flow)
     {
-      const size_t span_bytes = span * sizeof(fdx);
-      const bool pow2 = (span & (span - 1)) == 0 && span >= 2;
-      if (!pow2) rl = smooth_radices(span);                           // other prime factors: direct sums
-      const bool short_chunks = len <= 64 && opt_fft_carry != 2;
-      if (opt_fft_carry && !short_chunks && pow2 && span_bytes <= (size_t)64 * 1024) sums_form = SUMS_FFT2;
-      else if (opt_fft_carry && !short_chunks && rl.count > 0 && 2 * span_bytes <= (size_t)64 * 1024) sums_form = SUMS_FFT_MIXED;
+      if (!aux) SDFT_TRY(hipStreamCreateWithFlags(&aux, hipStreamNonBlocking));
+      if (!ev_delta) SDFT_TRY(hipEventCreateWithFlags(&ev_delta, hipEventDisableTiming));
+      while ((long)seg_events.size() < r.segments)
+      {
+        hipEvent_t e; SDFT_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        seg_events.push_back(e);
+      }
+      for (int q = 0; q < 2; ++q)
+        if (!d_run_acc[q].reserve(channels * nb) || !d_run_fid[q].reserve(channels * nb)) return false;
     }
-    // K0: differences + delay line -- unless the chunk-parallel carry kernel forms them itself
-    const bool delta_in_carry = !exact && chunks > 1;
-    if (!delta_in_carry)
+
+    DeltaIn<TD, FD> din;
+    if (!forward_delta(r, n, x, x_stride, din) || !forward_carries(r, n, din) || !forward_rows_stage(r, n, out, out_stride, rows, fuse, every)) return false;
+
+    // fid stays on the canonical rotation sequence unless this call seeded chunks from the closed-form
+    // table; a call that crosses the roll-over with serial fid arithmetic puts it back
+    if (!r.use_seed) fid_canonical = false;
+    else if (cursor + n >= span) fid_canonical = true;
+    cursor = (cursor + n) % span;
+    st_cur ^= 1;
+    return true;
+  }
+  // K0: differences + delay line -- unless the chunk-parallel carry kernel forms them itself
+  bool forward_delta(const logic::ForwardRoute& r, size_t n, const TD* x, size_t x_stride, DeltaIn<TD, FD>& din)
+  {
+    const size_t span = 2 * nbins;
+    if (!r.delta_in_carry)
     {
-    if (!prof_begin(ST_DELTA)) return false;
-    {
-      const size_t work = std::max(n, span);
-      const size_t per_ch = (work + kBlock - 1) / kBlock;
+      if (!prof_begin(ST_DELTA)) return false;
+      const size_t per_ch = (std::max(n, span) + kBlock - 1) / kBlock;
       if (!grid_fits(per_ch * channels)) return false;
-      const bool single = (chunks == 1);
+      const bool single = r.chunks == 1;
       hipLaunchKernelGGL((delta_kernel<TD, FD>), dim3((unsigned)(per_ch * channels)), dim3(kBlock), 0, stream, x, x_stride,
                          d_hist[hist_cur].p, d_hist[hist_cur ^ 1].p, d_delta.p, n, span,
                          (const fdx*)acc_p(), (const fdx*)fid_p(), single ? d_carry.p : (fdx*)nullptr, single ? d_seed.p : (fdx*)nullptr,
                          (unsigned)per_ch);
       SDFT_TRY(hipGetLastError());
+      if (!prof_end(ST_DELTA)) return false;
     }
-    if (!prof_end(ST_DELTA)) return false;
-    }
-    DeltaIn<TD, FD> din;
-    din.x = delta_in_carry ? x : nullptr; din.x_stride = x_stride;
+    din.x = r.delta_in_carry ? x : nullptr; din.x_stride = x_stride;
     din.hist_in = d_hist[hist_cur].p; din.hist_out = d_hist[hist_cur ^ 1].p; din.delta_out = d_delta.p;
     hist_cur ^= 1;
-
-    // carries
-    long segments = 1;
-    bool flow = false;
-    if (exact && chunks > 1)
+    return true;
+  }
+  // carries: time segments of the exact pass on `aux` (each segment's forward launch on `stream` waits for its event), the relay
+  // form (flow mode: one launch, the forward workgroups wait for their chunk's carries), or the pre-pass partial sums + scan
+  bool forward_carries(const logic::ForwardRoute& r, size_t n, const DeltaIn<TD, FD>& din)
+  {
+    const size_t nb = nbins, span = 2 * nbins;
+    const long chunks = r.chunks, segments = r.segments;
+    if (r.flow && started_target > (1u << 30))
     {
-      // time segments: the serial pass of segment s+1 (few waves, latency-bound) runs on `aux`
-      // while the forward kernel of segment s streams the matrix on `stream`;
-      // up to 8 segments, each forward launch still filling the chip (>= 256 workgroups)
-      const long launch_blocks = use_rows ? (long)channels * chunks : (long)channels * chunks * ntiles / kWavesPerBlock;
-      segments = opt_segments > 0 ? opt_segments : std::max(1L, std::min(8L, launch_blocks / 256));
-      // Relay form, flow mode: ONE relay launch for the whole call on `aux` and ONE forward launch whose workgroups wait
-      // for their chunk's carries themselves (ForwardArgs::ready).  With segments and events the two passes barely overlap:
-      // a 16-wave forward workgroup fills a CU's registers, so the relays of segment s+1 wait until the forward launch of
-      // segment s has drained (config 3: chain 0.71 ms alone + forward 1.55 ms alone = 2.2 ms together).  Here the relays
-      // hold their CUs from the start, the forward workgroups take whatever is free, in time order, and the whole chip
-      // once the relays are through.  The forward launch is held back (relay_gate_kernel polls a word every relay workgroup
-      // bumps at its start) until the relays are resident: a forward workgroup that waits for a relay which cannot start
-      // would be a deadlock -- every wait in the kernels is bounded all the same, and a time-out re-runs the call (forward_device).
-      flow = use_chain && opt_relay_flow && opt_segments <= 0 && (fuse ? true : use_rows) && !every && gate_ok();
-      if (flow) segments = 1;
-      if (flow && started_target > (1u << 30))
-      {
-        // long before the start counter could wrap: drain both streams and begin it again (once per ~8 million calls)
-        if (aux) SDFT_TRY(hipStreamSynchronize(aux));
-        SDFT_TRY(hipStreamSynchronize(stream));
-        SDFT_TRY(hipMemset(d_started, 0, 8));
-        started_target = 0;
-      }
-      segments = std::max(1L, std::min(segments, chunks));
-      if (segments > 1 || flow)
-      {
-        if (!aux) SDFT_TRY(hipStreamCreateWithFlags(&aux, hipStreamNonBlocking));
-        if (!ev_delta) SDFT_TRY(hipEventCreateWithFlags(&ev_delta, hipEventDisableTiming));
-        while ((long)seg_events.size() < segments)
-        {
-          hipEvent_t e; SDFT_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-          seg_events.push_back(e);
-        }
-        for (int q = 0; q < 2; ++q)
-          if (!d_run_acc[q].reserve(channels * nb) || !d_run_fid[q].reserve(channels * nb)) return false;
-        SDFT_TRY(hipEventRecord(ev_delta, stream));                 // delta (and everything before) done
-        SDFT_TRY(hipStreamWaitEvent(aux, ev_delta, 0));
-      }
+      // a new start word, or long before the counter could wrap: drain both streams and begin it again (once per ~8 million calls)
+      if (aux) SDFT_TRY(hipStreamSynchronize(aux));
+      SDFT_TRY(hipStreamSynchronize(stream));
+      SDFT_TRY(hipMemset(d_started, 0, 8));
+      started_target = 0;
+    }
+    if (segments > 1 || r.flow)
+    {
+      SDFT_TRY(hipEventRecord(ev_delta, stream));                 // delta (and everything before) done
+      SDFT_TRY(hipStreamWaitEvent(aux, ev_delta, 0));
     }
     // the stage's events go where its kernels go (the overlapped exact pass runs on `aux`)
-    hipStream_t carry_stream = (segments > 1 || flow) ? aux : stream;
+    hipStream_t carry_stream = (segments > 1 || r.flow) ? aux : stream;
     if (!prof_begin(ST_CARRY, carry_stream)) return false;
     CarryArgs<FD> ca;
     ca.acc_next = nullptr; ca.fid_next = nullptr; ca.chunk0 = 0; ca.launch_chunks = (unsigned)chunks;
     ca.delta = d_delta.p; ca.tw = d_tw.p; ca.wtab = d_wtab.p; ca.carry = d_carry.p; ca.seed = d_seed.p;
     ca.acc_state = acc_p(); ca.fid_state = fid_p(); ca.n = n;
-    ca.nbins = (unsigned)nb; ca.chunks = (unsigned)chunks; ca.chunk_len = (unsigned)len; ca.cursor0 = (unsigned)cursor;
-    const unsigned bin_blocks = (unsigned)((nb + kBlock - 1) / kBlock);
+    ca.nbins = (unsigned)nb; ca.chunks = (unsigned)chunks; ca.chunk_len = (unsigned)r.len; ca.cursor0 = (unsigned)cursor;
+    const unsigned bin_blocks = (unsigned)((nb + kBlock - 1) / kBlock), eblocks = (unsigned)logic::relays(nb);
     if (!grid_fits((size_t)bin_blocks * (size_t)chunks * channels) || !grid_fits(((nb + kScanBins - 1) / kScanBins) * channels) ||
-        !grid_fits(((nb + kWave / 2 - 1) / (kWave / 2)) * channels)) return false;
-    bool use_seed = true;
-    if (chunks == 1)
+        !grid_fits((size_t)eblocks * channels)) return false;
+    if (r.carry == logic::CARRY_RELAY)
     {
-      // single chunk: the stream state is the carry; delta_kernel has already copied it
-    }
-    else if (exact)
-    {
-      const unsigned eblocks = (unsigned)((nb + kWave / 2 - 1) / (kWave / 2));
-      for (long sg = 0; sg < segments && use_chain; ++sg)
+      for (long sg = 0; sg < segments; ++sg)
       {
         const long j0 = chunks * sg / segments, j1 = chunks * (sg + 1) / segments;
         ChainArgs<FD> cc{};
         cc.delta = d_delta.p; cc.tw = d_tw.p; cc.fseed = d_fseed.p; cc.carry = d_carry.p;
         cc.acc_state = sg == 0 ? acc_p() : d_run_acc[(sg - 1) & 1].p;
         cc.acc_next = segments > 1 ? d_run_acc[sg & 1].p : nullptr;
-        cc.n = n; cc.nbins = (unsigned)nb; cc.chunks = (unsigned)chunks; cc.chunk_len = (unsigned)len; cc.cursor0 = (unsigned)cursor;
-        cc.chunk0 = (unsigned)j0; cc.launch_chunks = (unsigned)(j1 - j0); cc.L = cL; cc.P = 0; cc.chunk_shift = shift; cc.debug = (unsigned)opt_chain_debug & (47u | 128u); cc.stats = nullptr;
+        cc.n = n; cc.nbins = (unsigned)nb; cc.chunks = (unsigned)chunks; cc.chunk_len = (unsigned)r.len; cc.cursor0 = (unsigned)cursor;
+        cc.chunk0 = (unsigned)j0; cc.launch_chunks = (unsigned)(j1 - j0); cc.L = r.relay_L; cc.P = 0; cc.chunk_shift = r.shift; cc.debug = (unsigned)opt_chain_debug & (47u | 128u); cc.stats = nullptr;
         if (opt_chain_debug & (16 | 64 | 128)) { if (!d_chain_stats.reserve(64 + 3 * 1024)) return false; cc.stats = d_chain_stats.p; }
         cc.status = ensure_status() ? d_status : nullptr;
         if (cc.status) status_armed = true;
         cc.ready = nullptr; cc.ready_seq = 0; cc.started = nullptr; cc.chunks_channels = (unsigned)channels;
-        if (flow)
+        if (r.flow)
         {
-          const size_t relays_per_channel = (nb + kWave / 2 - 1) / (kWave / 2);
-          const size_t words = channels * (size_t)chunks * relays_per_channel;
+          const size_t words = channels * (size_t)chunks * eblocks;
           if (d_ready.cap < words)
           {
             if (!d_ready.reserve(words)) return false;
@@ -762,7 +693,7 @@ class Plan
         }
         const unsigned cblocks = eblocks * (unsigned)channels;
         bool ok = true;
-        switch (cL)
+        switch (r.relay_L)
         {
           case 128: ok = launch_relay<128>(cc, cblocks, carry_stream); break;
           case 64:  ok = launch_relay<64>(cc, cblocks, carry_stream); break;
@@ -771,17 +702,20 @@ class Plan
           default:  ok = launch_relay<8>(cc, cblocks, carry_stream); break;
         }
         if (!ok) return false;
-        if (segments > 1 || flow) SDFT_TRY(hipEventRecord(seg_events[sg], aux));
-        if (flow)
+        if (segments > 1 || r.flow) SDFT_TRY(hipEventRecord(seg_events[sg], aux));
+        if (r.flow)
         {
           // the forward launch may go once every relay workgroup of this launch is resident
-          const unsigned relays = cblocks, groups = relay_groups_of(cL);
+          const unsigned relays = cblocks, groups = relay_groups_of(r.relay_L);
           started_target += (relays + groups - 1) / groups;
           hipLaunchKernelGGL((relay_gate_kernel<FD>), dim3(1), dim3(kWave), 0, stream, (const unsigned*)d_started, started_target);
           SDFT_TRY(hipGetLastError());
         }
       }
-      for (long sg = 0; sg < segments && !use_chain; ++sg)
+    }
+    else if (r.carry == logic::CARRY_SERIAL)
+    {
+      for (long sg = 0; sg < segments; ++sg)
       {
         const long j0 = chunks * sg / segments, j1 = chunks * (sg + 1) / segments;
         CarryArgs<FD> cs = ca;
@@ -795,19 +729,19 @@ class Plan
         if (segments > 1) SDFT_TRY(hipEventRecord(seg_events[sg], aux));
       }
     }
-    else
+    else if (r.carry == logic::CARRY_SUMS)
     {
-      // partial sums per chunk (form chosen above)
+      // partial sums per chunk, then the scan over chunks
       const size_t span_bytes = span * sizeof(fdx);
-      const unsigned sum_chunks = (unsigned)(chunks - (delta_in_carry ? 0 : 1));
-      if (sums_form == SUMS_FFT2)
+      const unsigned sum_chunks = (unsigned)(chunks - (r.delta_in_carry ? 0 : 1));
+      if (r.sums == logic::SUMS_FFT2)
       {
         unsigned lg = 0; while (((size_t)1 << lg) < span) ++lg;
         hipLaunchKernelGGL((chunk_fft_kernel<TD, FD>), dim3((unsigned)(sum_chunks * channels)), dim3(kBlock), span_bytes, stream, ca, lg, din);
       }
-      else if (sums_form == SUMS_FFT_MIXED)
+      else if (r.sums == logic::SUMS_FFT_MIXED)
         hipLaunchKernelGGL((chunk_fft_mixed_kernel<TD, FD>), dim3((unsigned)(sum_chunks * channels)), dim3(kBlock), 2 * span_bytes,
-                           stream, ca, (unsigned)span, rl, din);
+                           stream, ca, (unsigned)span, smooth_radices(span), din);
       else
       {
         if (!grid_fits((size_t)bin_blocks * sum_chunks * channels)) return false;
@@ -817,84 +751,68 @@ class Plan
       hipLaunchKernelGGL((carry_scan_kernel<FD>), dim3((unsigned)(((nb + kScanBins - 1) / kScanBins) * channels)),
                          dim3(kScanBins * kScanSlices), 0, stream, ca);
       SDFT_TRY(hipGetLastError());
-      use_seed = false;
     }
-    if (!prof_end(ST_CARRY, carry_stream)) return false;
-
-    // K1
+    // (CARRY_STATE, a single chunk: the stream state is the carry; delta_kernel has already copied it)
+    return prof_end(ST_CARRY, carry_stream);
+  }
+  // K1: the rows, one launch per time segment (the new state goes to the other buffer set: the one a call started from survives
+  // it, see forward_device)
+  bool forward_rows_stage(const logic::ForwardRoute& r, size_t n, fdx* out, size_t out_stride, fdx* const* rows,
+                          const FuseArgs<TD, FD>* fuse, const EveryGrid* every)
+  {
+    const size_t nb = nbins;
+    const long chunks = r.chunks, segments = r.segments;
     if (!prof_begin(ST_FORWARD)) return false;
     ForwardArgs<FD> fa{};
     fa.delta = d_delta.p; fa.tw = d_tw.p; fa.wtab = d_wtab.p; fa.carry = d_carry.p;
-    fa.seed = (use_seed && !use_chain) ? d_seed.p : nullptr;
-    fa.fseed = use_chain ? d_fseed.p : nullptr; fa.fseed_L = use_chain ? cL : 0;
+    fa.seed = (r.use_seed && !r.relay_L) ? d_seed.p : nullptr;
+    fa.fseed = r.relay_L ? d_fseed.p : nullptr; fa.fseed_L = r.relay_L;
     fa.out = out; fa.out_stride = out_stride; fa.out_rows = rows;
-    // the new state goes to the other buffer set (the one a call started from survives it, see forward_device)
     fa.acc_state = d_accs[st_cur ^ 1].p; fa.fid_state = d_fids[st_cur ^ 1].p; fa.n = n;
-    fa.total_waves = (unsigned long long)channels * (unsigned long long)chunks * (unsigned long long)ntiles;
-    fa.nbins = (unsigned)nb; fa.chunks = (unsigned)chunks; fa.chunk_len = (unsigned)len; fa.tiles = (unsigned)ntiles;
-    fa.interior_lanes = (unsigned)inter; fa.cursor0 = (unsigned)cursor; fa.chunk_shift = shift;
-    fa.vec_store = (bins_per_lane() == 2 && (nb % 2 == 0) && ((uintptr_t)out % 16 == 0) && (out_stride % 2 == 0) && !rows) ? 1 : 0;
+    fa.nbins = (unsigned)nb; fa.chunks = (unsigned)chunks; fa.chunk_len = (unsigned)r.len; fa.tiles = (unsigned)r.tiles;
+    fa.interior_lanes = (unsigned)r.interior; fa.cursor0 = (unsigned)cursor; fa.chunk_shift = r.shift;
+    fa.vec_store = r.vec_store ? 1 : 0;
     fa.wscale = (window == WIN_HANN) ? (FD)(tab.aweight * (FD)(0.25)) : tab.aweight;   // :371
     fa.done.flag = nullptr; fa.done.count = nullptr; fa.done.seq = 0; fa.done.total = 0;
     fa.ready = nullptr; fa.ready_seq = 0; fa.ready_n = 0; fa.ready_channels = (unsigned)channels; fa.ready_status = nullptr; fa.ready_status_seen = 0;
     fa.inv_channels = inv32((unsigned)channels);
-    if (flow)
+    if (r.flow)
     {
-      fa.ready = d_ready.p; fa.ready_seq = ready_seq; fa.ready_n = (unsigned)((nb + kWave / 2 - 1) / (kWave / 2));
+      fa.ready = d_ready.p; fa.ready_seq = ready_seq; fa.ready_n = (unsigned)logic::relays(nb);
       fa.ready_status = ensure_status() ? d_status : nullptr;
       fa.ready_status_seen = fa.ready_status ? *(volatile unsigned*)h_status : 0u;
       if (fa.ready_status) status_armed = true;
     }
-    // short synchronous calls: the row-group kernels report their own completion (a word in pinned host memory
-    // reaches the host before the stream does).  Worth it while the kernel has little to write back: n = 4096,
-    // N = 1024: 49.7 -> 46.7 us per sdft_sdft_n, 40.4 -> 35.8 us per fused call; nothing at n = 48000.
-    if ((use_rows || fuse) && segments == 1 && channels * n * nb <= (fuse ? (size_t)1 << 26 : kFlagMax))
-      fa.done = arm_flag((unsigned)(channels * (size_t)chunks));
-    last_segments = segments;
+    if (r.arm_flag) fa.done = arm_flag((unsigned)(channels * (size_t)chunks));
+    const bool exact_order = fuse && wants_reference_order();
+    if (fuse) { last_fused_exact = exact_order; last_fused_fold = r.folded; }
+    if (!fuse && r.kernel == logic::FK_ROWS) last_rows_f32 = r.rows_f32;
     for (long sg = 0; sg < segments; ++sg)
     {
       const long j0 = chunks * sg / segments, j1 = chunks * (sg + 1) / segments;
+      const size_t groups = channels * (size_t)(j1 - j0);
       fa.chunk0 = (unsigned)j0; fa.launch_chunks = (unsigned)(j1 - j0); fa.inv_chunks = inv32(fa.launch_chunks);
-      fa.xcd_map = (opt_xcd_map && !flow && channels * (size_t)(j1 - j0) >= 16) ? (unsigned)(channels * (size_t)(j1 - j0)) : 0u;
-      fa.total_waves = (unsigned long long)channels * (unsigned long long)(j1 - j0) * (unsigned long long)ntiles;
+      fa.xcd_map = logic::xcd_groups(r.xcd_map, groups);
+      fa.total_waves = (unsigned long long)groups * (unsigned long long)r.tiles;
       if (segments > 1) SDFT_TRY(hipStreamWaitEvent(stream, seg_events[sg], 0));      // (flow mode: the kernel waits chunk by chunk)
       const unsigned long long blocks = (fa.total_waves + kWavesPerBlock - 1) / kWavesPerBlock;
-      // fused arithmetic only where the result is not claimed bit-identical: FD double with carries
-      // from the chunk-parallel pass (use_seed == false <=> fast mode, more than one chunk)
-      const bool fused = (use_rows || fuse) && opt_fused && sizeof(FD) == 8 && !use_seed;
-      last_fused = fused;
+      const unsigned threads = (unsigned)(row_waves() * kWave);
       if (fuse)
       {
         // rows never leave the workgroup: synthesis in the same launch (caller checked fuse_ok())
-        const bool exact_order = wants_reference_order();
-        last_fused_exact = exact_order;
-        const bool folded = !exact_order && !fuse->store && opt_fold && coeff_ready;
-        last_fused_fold = folded;
-        if (folded)
-        {
-          if (!launch_process(fa, *fuse, (unsigned)(channels * (size_t)(j1 - j0)), fused)) return false;
-        }
-        else if (!use_rows) { set_error("sdft_hip_process_n", "rows of this length are fused in the folded form only"); return false; }
-        else if (!launch_syn(fa, *fuse, (unsigned)(channels * (size_t)(j1 - j0)), (unsigned)(row_waves() * kWave), fused && !exact_order, exact_order))
-          return false;
+        if (r.folded) { if (!launch_process(fa, *fuse, (unsigned)groups, r.fused)) return false; }
+        else if (r.kernel != logic::FK_ROWS) { set_error("sdft_hip_process_n", "rows of this length are fused in the folded form only"); return false; }
+        else if (!launch_syn(fa, *fuse, (unsigned)groups, threads, r.fused && !exact_order, exact_order)) return false;
       }
-      else if (use_rows) launch_forward_rows(fa, (unsigned)(channels * (size_t)(j1 - j0)), (unsigned)(row_waves() * kWave), fused);
+      else if (r.kernel == logic::FK_ROWS) launch_forward_rows(fa, (unsigned)groups, threads, r.fused, r.rows_f32);
       else if (every) { if (!grid_fits(blocks)) return false; launch_forward_every(fa, *every, (unsigned)blocks); }
       else launch_forward(fa, (unsigned)blocks);
       SDFT_TRY(hipGetLastError());
     }
     SDFT_TRY(hipGetLastError());
-    if (flow) SDFT_TRY(hipStreamWaitEvent(stream, seg_events[0], 0));          // the call ends when both launches have
-    last_flow = flow;
-    if (!prof_end(ST_FORWARD)) return false;
-
-    // fid stays on the canonical rotation sequence unless this call seeded chunks from the closed-form
-    // table; a call that crosses the roll-over with serial fid arithmetic puts it back
-    if (!use_seed) fid_canonical = false;
-    else if (cursor + n >= span) fid_canonical = true;
-    cursor = (cursor + n) % span;
-    st_cur ^= 1;
-    return true;
+    if (r.flow) SDFT_TRY(hipStreamWaitEvent(stream, seg_events[0], 0));          // the call ends when both launches have
+    last_flow = r.flow;
+    return prof_end(ST_FORWARD);
   }
 
   static RadixList smooth_radices(size_t span)
@@ -905,14 +823,6 @@ class Plan
     return rl;
   }
   size_t self_cells() const { return logic::self_cells(nbins, opt_self >= 1, sizeof(fdx)); }
-  // what the self-carried form needs of the plan and the call (the kernel that has it is chosen by the caller)
-  // (any_length: pipelined calls take the form whatever the length -- one stream runs long calls faster with the pre-pass,
-  // n = 1e6: 77.3 against 75.5 % of peak, but two matrices in turn, pipelined: 82.4 %)
-  bool self_eligible(size_t n, bool fused_call, bool any_length = false) const
-  {
-    const size_t self_max = fused_call ? std::min<size_t>(kSelfMax, (size_t)1 << 16) : kSelfMax;
-    return sizeof(FD) == 8 && carry_mode != CARRY_EXACT && opt_self && self_cells() != 0 && (n <= self_max || any_length);
-  }
 
   // ---- pipelined calls ------------------------------------------------------------------------------------------
   // Asynchronous analysis calls on the plan's own stream: consecutive calls' row kernels do not wait for each other.  What
@@ -934,7 +844,7 @@ class Plan
   // them is ordered behind it, as one stream would have it (logic::RowRing decides, this class waits and records)
   logic::RowRing ring;
   logic::Range prev_out;                                     // the matrix of the previous analysis call (dense, row-group kernel)
-  bool pipe_this = false;                                    // forward_launch: this call is pipelined
+  bool pipe_this = false;                                    // forward_launch: this call is pipelined (logic::ForwardRoute::pipelined)
   // Only calls whose every pointer is the caller's DEVICE memory may leave the plan's stream: the host-pointer routes reuse
   // the plan's staging buffers (d_stage_*, d_io, d_pin) on the main stream right behind a launch and promise the outputs
   // complete on return.  Set by the device/device branches of sdft_n / isdft_n for the duration of the call.
@@ -1093,12 +1003,12 @@ class Plan
     fa.nbins = (unsigned)nb; fa.chunks = (unsigned)chunks; fa.chunk_len = (unsigned)len; fa.tiles = (unsigned)tiles();
     fa.interior_lanes = (unsigned)interior_lanes(); fa.cursor0 = (unsigned)cursor; fa.chunk_shift = 0;
     fa.chunk0 = 0; fa.launch_chunks = (unsigned)chunks; fa.inv_chunks = inv32(fa.launch_chunks);
-    fa.xcd_map = (opt_xcd_map && channels * (size_t)chunks >= 16) ? (unsigned)(channels * (size_t)chunks) : 0u;
+    fa.xcd_map = logic::xcd_groups(opt_xcd_map != 0, channels * (size_t)chunks);
     fa.vec_store = 0;
     fa.wscale = (window == WIN_HANN) ? (FD)(tab.aweight * (FD)(0.25)) : tab.aweight;   // :371
     fa.done.flag = nullptr; fa.done.count = nullptr; fa.done.seq = 0; fa.done.total = 0;
     if (!grid_fits(channels * (size_t)chunks)) return false;
-    if (channels * n * nb <= (fuse ? (size_t)1 << 26 : kFlagMax)) fa.done = arm_flag((unsigned)(channels * (size_t)chunks));
+    if (channels * n * nb <= (fuse ? logic::kFlagMaxFused : logic::kFlagMax)) fa.done = arm_flag((unsigned)(channels * (size_t)chunks));
     const unsigned blocks = (unsigned)(channels * (size_t)chunks);
     const bool fused = opt_fused != 0;
     last_fused = fused; last_segments = 1; last_chain = 0;
@@ -1363,7 +1273,7 @@ class Plan
     inv_after_write = calls.prev_was_analysis;
     calls.on_synthesis_begin();
     const bool inv_pipe = calls.inverse_batch && pipe_allowed && !rows && !ops_wanted && async && own_stream && !stream_exposed && opt_pipeline && profile == 0 &&
-                          channels * n * nbins >= ((size_t)6 << 20) && ensure_pipe();
+                          channels * n * nbins >= logic::kPipelineBinsMin && ensure_pipe();
     if (!(inv_pipe ? pipe_join_rows() : pipe_join())) return false;
     hipStream_t main_stream = stream;
     int si = 0;

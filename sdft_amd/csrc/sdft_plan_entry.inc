@@ -486,8 +486,7 @@
     }
 
     bool ok;
-    long chunks, len;
-    choose_chunks(n, chunks, len, rows_kernel_ok(false));
+    const long chunks = logic::choose_chunks(chunk_query(n, rows_kernel_ok(false))).chunks;
     // reference order asked for on two-slot rows at FD float: the ordered walk (N dependent additions shared
     // by the four samples of a group) costs more than the synthesis pass it saves (N = 4096, n = 262144:
     // 5.7 ms against 4.1 ms for the two passes, which give the same bits); fused_exact = 2 insists on the kernel

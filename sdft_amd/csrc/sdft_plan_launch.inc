@@ -1,7 +1,7 @@
 // sdft_plan_launch.inc -- member functions of Plan<TD, FD> (included inside the class body by sdft_plan.hpp): the kernel
 // launches.  A kernel is a template over the window, the slots per lane, the arithmetic flavour ...; the plan knows those at run
 // time, so every launch is a small table from run-time values to one instantiation.  No decision is taken here beyond that
-// table (which kernel FORM a call takes is decided in sdft_plan.hpp / sdft_plan_logic.hpp).
+// table (which route and kernel form a call takes is decided in sdft_plan_logic.hpp: forward_route, inverse_route).
 
   template <int WIN, bool FUSED, int S>
   bool launch_forward_rows_self_ws(const ForwardArgs<FD>& fa, const SelfArgs<TD, FD>& sa, unsigned blocks, unsigned threads)
@@ -95,7 +95,7 @@
       default: launch_forward_rows_ts<FUSED, 2>(fa, blocks, threads); break;
     }
   }
-  // FD float, rows of a multiple of 128 bins, dense aligned output: the bin-pair kernel (sdft_forward_rows_f32.hpp)
+  // FD float, rows of a multiple of 128 bins, dense aligned output: the bin-pair kernel (sdft_forward_rows_f32.hpp; logic::ForwardRoute::rows_f32)
   long opt_rows_f32 = 1;
   long last_rows_f32 = 0;
   // (samples per lockstep group: 4; 2 measured slower -- 25.5 against 27.9 GB/s per CU, profiles/r04_kernels_beside_held_cus.txt)
@@ -117,19 +117,18 @@
   }
   // (rows of two slots, 2048 < N <= 4096, as two one-slot workgroups per row were built in round 5 -- same bits, 8-14 % slower,
   // profiles/r05_half_row_workgroups_*.txt -- and removed in round 6)
-  void launch_forward_rows(const ForwardArgs<FD>& fa, unsigned blocks, unsigned threads, bool fused)
+  void launch_forward_rows(const ForwardArgs<FD>& fa, unsigned blocks, unsigned threads, bool fused, bool rows_f32)
   {
-    last_rows_f32 = 0;
     if constexpr (sizeof(FD) == 4)
     {
-      if (opt_rows_f32 && nbins % (2 * kWave) == 0 && fa.vec_store && !fa.out_rows)
+      if (rows_f32)
       {
-        last_rows_f32 = 1;
         if (row_slots() == 1) launch_forward_rows_f32_s<1>(fa, blocks, threads, 0);
         else launch_forward_rows_f32_s<2>(fa, blocks, threads, 0);
         return;
       }
     }
+    (void)rows_f32;
     if constexpr (sizeof(FD) == 8) { if (fused) { launch_forward_rows_t<true>(fa, blocks, threads); return; } }
     launch_forward_rows_t<false>(fa, blocks, threads);
   }
@@ -312,16 +311,10 @@
   }
 
 
-  // rows in step (inverse_rows_body): float samples from double bins at latency 1 (the term of a bin is +-re: one register per
-  // bin in flight; the general term needs both halves and the kernel's three groups in flight no longer fit 64 registers),
-  // dense rows of 64 ... 2048 bins; a form of the rounding-interval proof (option inverse_verify = 0 turns it off with the other one)
+  // rows in step (inverse_rows_body; where: logic::rows_in_step_ok)
   long last_inverse_nt = 0;                                  // the loads of the last synthesis launch were non-temporal ...
   long last_inverse_skip = 0;                                // ... but for its first last_inverse_skip rows
   long opt_inverse_step = 0;                                 // 1: always where it applies (tests, A/B); 0: a candidate of the tuner; -1: never
-  template <bool LAT1> bool rows_in_step_ok(const InverseArgs<TD, FD>& ia, size_t total_rows) const
-  {
-    return LAT1 && sizeof(TD) == 4 && sizeof(FD) == 8 && opt_inverse_verify && !ia.in_rows && nbins >= 64 && nbins <= 2048 && total_rows >= 64 && total_rows <= 0x7fffffffull * 4;
-  }
   template <bool LAT1> void launch_inverse_rows_in_step(const InverseArgs<TD, FD>& ia, size_t total_rows)
   {
     if constexpr (LAT1 && sizeof(TD) == 4 && sizeof(FD) == 8)
@@ -335,16 +328,8 @@
       else hipLaunchKernelGGL((inverse_rows2_kernel<TD, FD, LAT1>), dim3((unsigned)nchunks), dim3(waves * kWave), 0, stream, ia, (unsigned)chunk);
     }
   }
-  // whole rows, ordered sum (inverse_rows_ordered_kernel): every type pair, any latency; rows of up to 8 KiB of terms in one run (one channel, or
-  // channels without a gap between them), 16-byte loads
+  // whole rows, ordered sum (inverse_rows_ordered_kernel; where: logic::rows_ordered_ok): rows of up to 8 KiB of terms
   long opt_inverse_ordered = 0;                              // 1: always where it applies (tests, A/B); 0: a candidate of the tuner, the static choice from 0.7 GB on; -1: never
-  bool rows_ordered_ok(const InverseArgs<TD, FD>& ia, size_t total_rows) const
-  {
-    ordered_rows_geometry<FD> geo;
-    const bool one_run = ia.channels == 1 || (ia.in_stride == ia.n * (size_t)nbins && ia.y_stride == ia.n);
-    const bool loads_ok = (reinterpret_cast<uintptr_t>(ia.in) & 15) == 0 && (sizeof(cx<FD>) == 16 || nbins % 2 == 0);
-    return !ia.in_rows && one_run && loads_ok && total_rows >= 64 && total_rows <= 0x7fffffffull && geo.make(nbins, ordered_lds());
-  }
   // LDS of a workgroup: 140 KB hold 16 row slots of 8 KiB -- enough while a row has up to 1024 terms (the kernel is bound by HBM: 6.85 TB/s; with
   // more slots 6.75); rows of 1025 ... 2048 float terms are bound by the adding wave's chains, and 158 KB hold 18 slots in six groups:
   // 6.4 ... 6.6 TB/s against 5.6 ... 5.8 at 1e6 x 2048 (profiles/r06_synthesis_forms.txt)
@@ -374,195 +359,109 @@
     hipLaunchKernelGGL(kern, dim3((unsigned)nchunks), dim3(kWave * (ordered_rows_geometry<FD>::LOADERS + 1)), geo.lds_bytes, stream, ia, (unsigned)chunk, geo);
     return true;
   }
-  template <bool LAT1, bool OPS> void launch_inverse(const InverseArgs<TD, FD>& ia, size_t total_rows)
+  // every synthesis form: run-time form -> instantiation (rows_per_wave sizes the grid of the streaming forms).  false: the form
+  // did not launch (the ordered form's LDS was refused, a host expression did not compile)
+  template <bool LAT1, bool OPS> bool launch_inverse_form(int form, long rows_per_wave, const InverseArgs<TD, FD>& ia, size_t total_rows)
   {
-    size_t blocks = (total_rows + kWavesPerBlock - 1) / kWavesPerBlock;
-    blocks = std::min(blocks, (size_t)256 * 8 * 4);
-    flag_pending = false;                                    // only the row form below signals its completion
-    last_inverse_nt = ia.nt; last_inverse_skip = (long)ia.nt_skip;
-    // matrices from 6 GB on: the static choice too (n = 5e5 ... 1e6 x 1024, 64 x 48000 x 1024 / 2048, 250000 x 2048: +5 ... +10 % over
-    // the best streaming form; 4 GB: a tie; below: the streaming forms, by up to 12 % -- profiles/r05_synthesis_rows_in_step.txt)
-    const double matrix_bytes = (double)total_rows * (double)nbins * sizeof(cx<FD>);
-    const bool step_static = opt_inverse_step >= 0 && rows_in_step_ok<LAT1>(ia, total_rows) && matrix_bytes >= 6.0e9;
-    // (whole rows with the ordered sum: 6.85 TB/s at n = 1e6 x 1024 for every type pair -- rows in step 6.54, the tiles 5.8 ... 6.35;
-    // profiles/r06_synthesis_forms.txt)
-    const bool ordered_ok = !OPS && opt_exact_inverse && opt_inverse_rows <= 0 && opt_inverse_ordered >= 0 && rows_ordered_ok(ia, total_rows);
-    const bool ordered_static = ordered_ok && matrix_bytes >= 7.0e8;      // (48 000 x 1024 double bins: 6.1 TB/s against 5.7 for the best of the tiles; 200 000: 6.65 against 6.2)
-    if constexpr (!OPS)
+    const size_t rw = (size_t)std::max(1L, rows_per_wave);
+    const dim3 tiles((unsigned)std::min((total_rows + kWavesPerBlock - 1) / kWavesPerBlock, (size_t)256 * 8 * 4)), b(kBlock);
+    const dim3 g((unsigned)std::max<size_t>(1, std::min<size_t>(((total_rows + rw - 1) / rw + kWavesPerBlock - 1) / kWavesPerBlock, (size_t)256 * 32)));
+    switch (form)
     {
-      const bool step_forced = opt_exact_inverse && opt_inverse_rows <= 0 && opt_inverse_step == 1 && opt_inverse_ordered != 1 && rows_in_step_ok<LAT1>(ia, total_rows);
-      if (ordered_ok && !step_forced && (opt_inverse_ordered == 1 || (ordered_static && !opt_inverse_tune)))
+      case logic::F_TREE: hipLaunchKernelGGL((inverse_kernel<TD, FD, LAT1, OPS>), tiles, b, 0, stream, ia); return true;
+      case logic::F_VERIFY:
+        if constexpr (sizeof(TD) == 4 && sizeof(FD) == 8) hipLaunchKernelGGL((inverse_kernel<TD, FD, LAT1, OPS, true>), tiles, b, 0, stream, ia);
+        return true;
+      case logic::F_STEP: if constexpr (!OPS) launch_inverse_rows_in_step<LAT1>(ia, total_rows); return true;
+      case logic::F_ORDERED: if constexpr (!OPS) return launch_inverse_rows_ordered<LAT1>(ia, total_rows); return true;
+      case logic::F_ROW:
       {
-        if (launch_inverse_rows_ordered<LAT1>(ia, total_rows)) { last_inverse_form = 4; last_inverse_tuned = 7; return; }
-      }
-      if (opt_exact_inverse && opt_inverse_rows <= 0 && ((opt_inverse_step == 1 && rows_in_step_ok<LAT1>(ia, total_rows)) || (step_static && !opt_inverse_tune)))
-      {
-        launch_inverse_rows_in_step<LAT1>(ia, total_rows);
-        last_inverse_form = 3; last_inverse_tuned = 6;
-        return;
-      }
-    }
-    if (!opt_exact_inverse)
-    {
-      hipLaunchKernelGGL((inverse_kernel<TD, FD, LAT1, OPS>), dim3((unsigned)blocks), dim3(kBlock), 0, stream, ia);
-      last_inverse_form = 0;
-      return;
-    }
-    // the reference's summation order.  Measured (n=1e6, N=1024, f64): 32 rows per wave 2.75 ms, 16:
-    // 2.82, 64: 3.6 (130 VGPRs); float bins and medium calls do best with 16; below 64 Ki rows a wave
-    // with 16 rows and one tile of look-ahead is a chain of N/16 memory round trips (~70 us whatever
-    // n is): 4 rows with an 8-deep ring (n = 12000: 33 us against 79, n = 48000: 153 against 178,
-    // n = 131072: 397 against 355); short calls (a hop of 100 rows): one wave per row
-    // float samples from double bins, medium calls: the tree-sum kernel with the rounding-interval test gives the same bits
-    // without the chain of dependent additions (n = 4096: 22.5 -> 11.8 us, 48000: 145 -> 132 us, 200000: 585 -> 550 us;
-    // from about half a million rows on the streaming kernel below is the faster one: 2.64 against 2.78 ms at n = 1e6)
-    // Calls from 8 Ki rows on: the forms that stream at HBM speed differ by a few per cent either way from lease to lease -- 32 /
-    // 16 / 8 / 4 rows per wave, 256- or 512-byte row segments, and (float samples from double bins) the tree sum with the
-    // rounding-interval proof.  All give the same bits, so the plan measures them on the host's own calls (logic::FormTuner;
-    // scripts/synthesis_forms_ab.py: n = 1e6 tree sum +5.5 %, 262144 x 1024 f64f64 16 rows +19 %, m = 4096 FD float 512-byte
-    // segments +13 %; round 4's fixed switch points flipped winner five times between 16 k and 65 k rows).  Candidate 0 is the
-    // static choice.  Forced forms (options inverse_rows / inverse_rpi / inverse_verify = 0) and operations: static.
-    if constexpr (!OPS)
-    {
-      if (opt_inverse_tune && opt_inverse_rows <= 0 && total_rows >= 8192 && ensure_tune_events())
-      {
-        constexpr bool kProof = sizeof(TD) == 4 && sizeof(FD) == 8;
-        enum { F_VERIFY = 0, F_32 = 1, F_16 = 2, F_16W = 3, F_8 = 4, F_4 = 5, F_STEP = 6, F_ORDERED = 7, F_8W = 8 };
-        const bool verify0 = kProof && opt_inverse_verify && total_rows <= kInverseVerifyMax;
-        const long rw0 = logic::inverse_rows_per_wave(total_rows, sizeof(FD), 0, inverse_capacity[0], inverse_capacity[1], false);
-        const bool long_call = total_rows >= 65536;
-        // candidates: up to kMax pairs (form, rows read first with ordinary loads).  The matrix streams past the caches (non-temporal loads) but for the
-        // rows read first, which take ordinary loads: what an analysis left dirty in the Infinity Cache is slow to a non-temporal load.  1.5 GB of them
-        // are the static choice from 6 GiB on and none below (logic::inverse_ordinary_rows); between 2 and 16 GiB which is better depends on the form
-        // and on whether the host has just written the matrix (4.3 GB: TD = FD = double 1007 -> 835 us with them, f32f64 733 -> 779), so there every
-        // form is tried both ways (profiles/r05_after_write_16gb.txt)
-        int forms[logic::FormTuner::kMax]; size_t skips[logic::FormTuner::kMax]; int nf = 0;
-        const bool both_loads = ia.nt && opt_inverse_nt_skip_mb < 0 && matrix_bytes >= 2.0 * 1073741824.0 && matrix_bytes < 16.0 * 1073741824.0;
-        const size_t other_skip = ia.nt_skip ? 0 : logic::inverse_ordinary_rows((size_t)1 << 40, nbins * sizeof(cx<FD>), -1);
-        auto add = [&](int f)
+        InverseArgs<TD, FD> ir = ia;
+        ir.done = arm_flag((unsigned)total_rows);              // (the only form that signals its completion)
+        if (OPS && ia.op.kind == OP_USER)
         {
-          for (int i = 0; i < nf; ++i) if (forms[i] == f) return;
-          if (nf < logic::FormTuner::kMax) { forms[nf] = f; skips[nf] = ia.nt_skip; ++nf; }
-          if (both_loads && nf < logic::FormTuner::kMax) { forms[nf] = f; skips[nf] = other_skip; ++nf; }
-        };
-        add(ordered_static ? F_ORDERED : step_static ? F_STEP : verify0 ? F_VERIFY : (rw0 >= 32 ? F_32 : rw0 >= 16 ? F_16 : rw0 >= 8 ? F_8 : F_4));
-        // (float samples from double bins: the two forms with the rounding-interval proof first)
-        // (F_8W: 8 rows x 512 bytes, two tiles ahead -- the best of the tiles where rows are too long for the ordered form: 6.8 against 6.6 TB/s at
-        // 500 000 x 2048 double; profiles/r06_synthesis_forms.txt)
-        const int others_long[7] = {F_ORDERED, F_8W, F_STEP, F_VERIFY, F_16, F_32, F_16W}, others_medium[7] = {F_ORDERED, F_STEP, F_VERIFY, F_4, F_8, F_16, -1};
-        int kinds = 1;
-        for (int f : (long_call ? others_long : others_medium))
-        {
-          if (nf >= logic::FormTuner::kMax || kinds >= (both_loads ? 3 : 4)) break;
-          if (f == forms[0]) continue;
-          if (f < 0 || (f == F_ORDERED && !ordered_ok)) continue;
-          if (f == F_8W && ordered_ok) continue;
-          if (f == F_STEP && !(opt_inverse_step >= 0 && rows_in_step_ok<LAT1>(ia, total_rows))) continue;
-          if (f == F_VERIFY && !(kProof && opt_inverse_verify)) continue;
-          if (f == F_32 && sizeof(FD) != 8) continue;       // (64 registers of row segments: FD double only, as before)
-          add(f); ++kinds;
+          // the host's own statements inside the row synthesis of a hop: this instantiation, compiled at run time
+          char name[160];
+          snprintf(name, sizeof(name), "sdfthip::inverse_row_kernel<%s, %s, %s, true>", type_name<TD>(), type_name<FD>(), LAT1 ? "true" : "false");
+          hipFunction_t fn = nullptr;
+          if (!rtc_kernel(user_expr.c_str(), name, device, &fn)) { rtc_failed = true; return false; }
+          void* args[] = {&ir};
+          if (hipModuleLaunchKernel(fn, (unsigned)total_rows, 1, 1, kWave, 1, 1, 0, stream, args, nullptr) != hipSuccess) { rtc_failed = true; return false; }
+          return true;
         }
-        logic::TunerTable& table = inv_tunes[inv_after_write ? 1 : 0];
-        const int tslot = table.find(total_rows, nf);
-        logic::FormTuner& tuner = table.slot[tslot];
-        auto& tev = tune_evs[inv_after_write ? 1 : 0][tslot];
-        for (int i = 0; i < nf; ++i)
-          if (tuner.inflight[i] && hipEventQuery(tev[i][1]) == hipSuccess)
-          {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, tev[i][0], tev[i][1]) != hipSuccess) ms = 0.f;
-            tuner.report(i, ms);
-          }
-        (void)hipGetLastError();
-        bool timed = false;
-        const int pick = tuner.next(true, timed);
-        const int form = forms[pick];
-        InverseArgs<TD, FD> it = ia;
-        it.nt_skip = skips[pick];
-        last_inverse_skip = (long)it.nt_skip;
-        if (timed && hipEventRecord(tev[pick][0], stream) != hipSuccess) { (void)hipGetLastError(); timed = false; }
-        auto grid = [&](size_t rows_per_wave) { return dim3((unsigned)std::max<size_t>(1, std::min<size_t>(((total_rows + rows_per_wave - 1) / rows_per_wave + kWavesPerBlock - 1) / kWavesPerBlock, (size_t)256 * 32))); };
-        last_inverse_form = form == F_VERIFY ? 2 : form == F_STEP ? 3 : form == F_ORDERED ? 4 : 1;
-        last_inverse_tuned = 10 * (tuner.chosen >= 0 ? 1 : 0) + form;
-        if constexpr (kProof) { if (form == F_VERIFY) hipLaunchKernelGGL((inverse_kernel<TD, FD, LAT1, false, true>), dim3((unsigned)blocks), dim3(kBlock), 0, stream, it); }
-        if (form == F_STEP) launch_inverse_rows_in_step<LAT1>(it, total_rows);
-        if (form == F_ORDERED) (void)launch_inverse_rows_ordered<LAT1>(it, total_rows);     // (the attribute was granted when the form was found to apply ... or the launch fails and says so)
-        if constexpr (sizeof(FD) == 8) { if (form == F_32) hipLaunchKernelGGL((inverse_exact_kernel<TD, FD, LAT1, 32, 1, false>), grid(32), dim3(kBlock), 0, stream, it); }
-        if (form == F_16) hipLaunchKernelGGL((inverse_exact_kernel<TD, FD, LAT1, 16, 1, false>), grid(16), dim3(kBlock), 0, stream, it);
-        else if (form == F_16W) hipLaunchKernelGGL((inverse_exact_kernel<TD, FD, LAT1, 16, 1, false, 2>), grid(16), dim3(kBlock), 0, stream, it);
-        else if (form == F_8) hipLaunchKernelGGL((inverse_exact_kernel<TD, FD, LAT1, 8, 4, false>), grid(8), dim3(kBlock), 0, stream, it);
-        else if (form == F_8W) hipLaunchKernelGGL((inverse_exact_kernel<TD, FD, LAT1, 8, 2, false, 2>), grid(8), dim3(kBlock), 0, stream, it);
-        else if (form == F_4) hipLaunchKernelGGL((inverse_exact_kernel<TD, FD, LAT1, 4, 8, false>), grid(4), dim3(kBlock), 0, stream, it);
-        if (timed) { if (hipEventRecord(tev[pick][1], stream) == hipSuccess) tuner.launched(pick); else (void)hipGetLastError(); }
-        return;
+        hipLaunchKernelGGL((inverse_row_kernel<TD, FD, LAT1, OPS>), dim3((unsigned)total_rows), dim3(kWave), 0, stream, ir);
+        return true;
       }
-    }
-    if constexpr (sizeof(TD) == 4 && sizeof(FD) == 8)
-    {
-      if (opt_inverse_verify && opt_inverse_rows <= 0 && total_rows > 1024 && total_rows <= kInverseVerifyMax)
-      {
-        hipLaunchKernelGGL((inverse_kernel<TD, FD, LAT1, OPS, true>), dim3((unsigned)blocks), dim3(kBlock), 0, stream, ia);
-        last_inverse_form = 2;
-        return;
-      }
-    }
-    last_inverse_form = 1;
-    // (rows per wave: logic::inverse_rows_per_wave; the capacities of the 4-row and the 8-row form come from the occupancy API)
-    if constexpr (!OPS)
-    {
-      if (opt_inverse_rows <= 0 && inverse_capacity[0] == 0 && total_rows > 1024 && total_rows < 65536)
-      {
-        int dev_cus = 0, b4 = 0, b8 = 0;
-        if (hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&b4, inverse_exact_kernel<TD, FD, LAT1, 4, 8, false>, kBlock, 0) == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&b8, inverse_exact_kernel<TD, FD, LAT1, 8, 4, false>, kBlock, 0) == hipSuccess)
-        {
-          inverse_capacity[0] = (size_t)std::max(1, b4) * dev_cus * kWavesPerBlock;
-          inverse_capacity[1] = (size_t)std::max(1, b8) * dev_cus * kWavesPerBlock;
-        }
-        else { (void)hipGetLastError(); inverse_capacity[0] = inverse_capacity[1] = (size_t)-1; }
-      }
-    }
-    const long rw = logic::inverse_rows_per_wave(total_rows, sizeof(FD), opt_inverse_rows, inverse_capacity[0], inverse_capacity[1], OPS);
-    size_t eb = ((total_rows + rw - 1) / rw + kWavesPerBlock - 1) / kWavesPerBlock;
-    eb = std::max<size_t>(1, std::min(eb, (size_t)256 * 32));
-    const dim3 g((unsigned)eb), b(kBlock);
-    if (rw == 1 && total_rows <= 0x7fffffffull)
-    {
-      InverseArgs<TD, FD> ir = ia;
-      ir.done = arm_flag((unsigned)total_rows);
-      if (OPS && ia.op.kind == OP_USER)
-      {
-        // the host's own statements inside the row synthesis of a hop: this instantiation, compiled at run time
-        char name[160];
-        snprintf(name, sizeof(name), "sdfthip::inverse_row_kernel<%s, %s, %s, true>", type_name<TD>(), type_name<FD>(), LAT1 ? "true" : "false");
-        hipFunction_t fn = nullptr;
-        if (!rtc_kernel(user_expr.c_str(), name, device, &fn)) { rtc_failed = true; return; }
-        void* args[] = {&ir};
-        if (hipModuleLaunchKernel(fn, (unsigned)total_rows, 1, 1, kWave, 1, 1, 0, stream, args, nullptr) != hipSuccess) rtc_failed = true;
-        return;
-      }
-      hipLaunchKernelGGL((inverse_row_kernel<TD, FD, LAT1, OPS>), dim3((unsigned)total_rows), dim3(kWave), 0, stream, ir);
-    }
-    else if (rw >= 32)
-    {
-      if constexpr (!OPS)
-      {
-        hipLaunchKernelGGL((inverse_exact_kernel<TD, FD, LAT1, 32, 1, false>), g, b, 0, stream, ia);
-      }
-    }
-    // (16 rows x 4 tiles in flight was measured in round 4 and lost to 4 x 8 below 64 Ki rows and to 16 x 1 above: scripts/inverse_ab.py)
-    else if (rw >= 16)
-    {
-      hipLaunchKernelGGL((inverse_exact_kernel<TD, FD, LAT1, 16, 1, OPS>), g, b, 0, stream, ia);
-    }
-    else if (rw >= 8)
-    {
-      if constexpr (!OPS) hipLaunchKernelGGL((inverse_exact_kernel<TD, FD, LAT1, 8, 4, false>), g, b, 0, stream, ia);
-    }
-    else
-    {
-      if constexpr (!OPS) hipLaunchKernelGGL((inverse_exact_kernel<TD, FD, LAT1, 4, 8, false>), g, b, 0, stream, ia);
+      case logic::F_32: if constexpr (!OPS) hipLaunchKernelGGL((inverse_exact_kernel<TD, FD, LAT1, 32, 1, false>), g, b, 0, stream, ia); return true;
+      // (16 rows x 4 tiles in flight was measured in round 4 and lost to 4 x 8 below 64 Ki rows and to 16 x 1 above: scripts/inverse_ab.py)
+      case logic::F_16: hipLaunchKernelGGL((inverse_exact_kernel<TD, FD, LAT1, 16, 1, OPS>), g, b, 0, stream, ia); return true;
+      case logic::F_16W: if constexpr (!OPS) hipLaunchKernelGGL((inverse_exact_kernel<TD, FD, LAT1, 16, 1, false, 2>), g, b, 0, stream, ia); return true;
+      case logic::F_8: if constexpr (!OPS) hipLaunchKernelGGL((inverse_exact_kernel<TD, FD, LAT1, 8, 4, false>), g, b, 0, stream, ia); return true;
+      case logic::F_8W: if constexpr (!OPS) hipLaunchKernelGGL((inverse_exact_kernel<TD, FD, LAT1, 8, 2, false, 2>), g, b, 0, stream, ia); return true;
+      default: if constexpr (!OPS) hipLaunchKernelGGL((inverse_exact_kernel<TD, FD, LAT1, 4, 8, false>), g, b, 0, stream, ia); return true;   // F_4
     }
   }
-
+  // The route (logic::inverse_route) decides the form, or the candidates the tuner picks from; this runs it and keeps the
+  // tuner's books (a pair of events per timed candidate, reported once they have completed)
+  template <bool LAT1, bool OPS> void launch_inverse(const InverseArgs<TD, FD>& ia, size_t total_rows)
+  {
+    flag_pending = false;                                    // only the one-wave-per-row form signals its completion
+    last_inverse_nt = ia.nt; last_inverse_skip = (long)ia.nt_skip;
+    logic::InverseQuery q;
+    q.n = ia.n; q.channels = ia.channels; q.nbins = nbins; q.td_bytes = sizeof(TD); q.fd_bytes = sizeof(FD);
+    q.in_stride = ia.in_stride; q.y_stride = ia.y_stride; q.in = reinterpret_cast<uintptr_t>(ia.in); q.row_pointers = ia.in_rows != nullptr;
+    q.lat1 = LAT1; q.ops = OPS; q.nt = ia.nt != 0; q.nt_skip = ia.nt_skip; q.capacity4 = inverse_capacity[0]; q.capacity8 = inverse_capacity[1];
+    q.exact = opt_exact_inverse; q.rows = opt_inverse_rows; q.step = opt_inverse_step; q.ordered = opt_inverse_ordered; q.tune = opt_inverse_tune;
+    q.verify = opt_inverse_verify; q.nt_skip_mb = opt_inverse_nt_skip_mb;
+    auto ordered_geometry = [&] { ordered_rows_geometry<FD> geo; return geo.make(nbins, ordered_lds()); };
+    auto tune_events = [&] { return ensure_tune_events(); };
+    auto capacity = [&](size_t& c4, size_t& c8)
+    {
+      int dev_cus = 0, b4 = 0, b8 = 0;
+      if (hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess &&
+          hipOccupancyMaxActiveBlocksPerMultiprocessor(&b4, inverse_exact_kernel<TD, FD, LAT1, 4, 8, false>, kBlock, 0) == hipSuccess &&
+          hipOccupancyMaxActiveBlocksPerMultiprocessor(&b8, inverse_exact_kernel<TD, FD, LAT1, 8, 4, false>, kBlock, 0) == hipSuccess)
+      {
+        inverse_capacity[0] = (size_t)std::max(1, b4) * dev_cus * kWavesPerBlock;
+        inverse_capacity[1] = (size_t)std::max(1, b8) * dev_cus * kWavesPerBlock;
+      }
+      else { (void)hipGetLastError(); inverse_capacity[0] = inverse_capacity[1] = (size_t)-1; }
+      c4 = inverse_capacity[0]; c8 = inverse_capacity[1];
+    };
+    logic::InverseRoute r = logic::inverse_route(q, ordered_geometry, tune_events, capacity);
+    while (!r.tuned)
+    {
+      if (!launch_inverse_form<LAT1, OPS>(r.form, r.rows_per_wave, ia, total_rows) && r.form == logic::F_ORDERED)
+      {
+        q.ordered_failed = true;                             // (its LDS was refused: the route without the static ordered form)
+        r = logic::inverse_route(q, ordered_geometry, tune_events, capacity);
+        continue;
+      }
+      last_inverse_form = logic::inverse_form_code(r.form);
+      if (r.form == logic::F_STEP || r.form == logic::F_ORDERED) last_inverse_tuned = logic::inverse_tuned_code(r.form, false);
+      return;
+    }
+    logic::TunerTable& table = inv_tunes[inv_after_write ? 1 : 0];
+    const int tslot = table.find(total_rows, r.count);
+    logic::FormTuner& tuner = table.slot[tslot];
+    auto& tev = tune_evs[inv_after_write ? 1 : 0][tslot];
+    for (int i = 0; i < r.count; ++i)
+      if (tuner.inflight[i] && hipEventQuery(tev[i][1]) == hipSuccess)
+      {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, tev[i][0], tev[i][1]) != hipSuccess) ms = 0.f;
+        tuner.report(i, ms);
+      }
+    (void)hipGetLastError();
+    bool timed = false;
+    const int pick = tuner.next(true, timed);
+    const logic::InverseCandidate c = r.cand[pick];
+    InverseArgs<TD, FD> it = ia;
+    it.nt_skip = c.nt_skip;
+    last_inverse_skip = (long)it.nt_skip;
+    if (timed && hipEventRecord(tev[pick][0], stream) != hipSuccess) { (void)hipGetLastError(); timed = false; }
+    last_inverse_form = logic::inverse_form_code(c.form);
+    last_inverse_tuned = logic::inverse_tuned_code(c.form, tuner.chosen >= 0);
+    (void)launch_inverse_form<LAT1, OPS>(c.form, logic::inverse_form_rows(c.form), it, total_rows);   // (not checked yet: ADVICE.md)
+    if (timed) { if (hipEventRecord(tev[pick][1], stream) == hipSuccess) tuner.launched(pick); else (void)hipGetLastError(); }
+  }

@@ -1,7 +1,9 @@
 // sdft_plan_logic.hpp -- the host-side DECISIONS of the engine, free of any HIP dependency: launch geometry (lanes, tiles,
 // row slots), time chunking, the block length of the exact-carry relay, which calls leave the plan's stream (call pattern,
-// row-stream ring, address-range overlap), time parts of a hop, rows per wave of the synthesis, the wait of a synchronous
-// call, and the slot ring of the host-copy engine.  sdft_plan.hpp (Plan<TD, FD>) asks these functions and does the HIP calls;
+// row-stream ring, address-range overlap), time parts of a hop, rows per wave of the synthesis, the route of an analysis call
+// (forward_route) and the form of a synthesis call (inverse_route), the wait of a synchronous call, and the slot ring of the
+// host-copy engine.  sdft_plan.hpp (Plan<TD, FD>) builds the queries, asks these functions and does the HIP calls (a check that
+// needs one -- an allocation, the occupancy API -- is a callable the route asks only where it needs the answer);
 // tests/cpp/plan_logic_test.cpp compiles this header alone with g++ -fsanitize=address,undefined (and the ring under
 // -fsanitize=thread) in the `-m "not gpu"` suite (sanitizers on the host side).
 // Citations are into /root/reference/c/src/sdft/sdft.h.
@@ -496,6 +498,333 @@ inline ProcessGeometry process_geometry(size_t nbins, size_t channels, size_t n,
   if (want > 1) g.waves = std::max(1L, std::min(g.waves, (long)((nbins + (size_t)(kLanes * want) - 1) / (size_t)(kLanes * want))));
   g.slots = (long)((nbins + (size_t)g.waves * kLanes - 1) / ((size_t)g.waves * kLanes));
   return g;
+}
+
+// ---- analysis: the route of a call (Plan::forward_launch runs it) ------------------------------------------------------------
+constexpr int kWavesPerBlock = 4;                  // waves of a tile-kernel workgroup (kWavesPerBlock)
+constexpr int kProcGroup = 8, kProcRow = 72;       // the fused kernel's transpose tile: samples per group, row stride (kProcGroup, kProcRow)
+constexpr size_t kSelfMax = (size_t)1 << 19;       // self-carried chunks for calls of up to this many samples per channel (the fold of a chunk's past grows with n) ...
+constexpr size_t kSelfMaxFused = (size_t)1 << 16;  // ... of the fused call, which is bound by instruction issue (n = 131072: 99 -> 117 us self-carried)
+constexpr size_t kFlagMax = (size_t)1 << 24;       // bin-samples up to which a row-group analysis call signals its own completion ...
+constexpr size_t kFlagMaxFused = (size_t)1 << 26;  // ... and a fused call
+constexpr size_t kPipelineBinsMin = (size_t)6 << 20;   // bin-samples from which a call may leave the plan's stream (analysis and synthesis)
+constexpr size_t kSumsLds = (size_t)64 * 1024;     // LDS of a workgroup of the FFT forms of the chunk partial sums
+
+// relays of the exact carries (32 bins of a channel each) = waves of the serial pass per channel
+inline size_t relays(size_t nbins) { return (nbins + kLanes / 2 - 1) / (kLanes / 2); }
+
+struct ForwardQuery
+{
+  size_t n = 0, nbins = 0, channels = 1, fd_bytes = 8, fdx_bytes = 16;
+  int window = kWindowHann, compute_units = 256;
+  size_t cursor = 0;
+  bool exact = false;                     // exact carries (carry mode)
+  bool fid_canonical = true;              // fid is on the canonical rotation sequence (the relay form's seed table)
+  bool fuse = false, fuse_store = false;  // the fused call; it stores the processed spectrum too
+  bool reference_order = false;           // the fused call sums bins in the reference's order
+  bool coeff_ready = false;               // the fused call's folded coefficients are built
+  bool every = false;                     // decimated analysis (forward_every_kernel)
+  bool row_pointers = false;              // rows go to a table of row pointers
+  uintptr_t out = 0; size_t out_stride = 0;
+  bool analysis_batch = false;            // CallPattern: analyses come call after call
+  bool pipe_wanted = false;               // Plan::pipe_wanted: the plan and the call may leave the plan's stream
+  Range prev_out;                         // the matrix of the previous dense row-group analysis
+  // options
+  long rows_kernel = 1, row_slots_max = 2, interior = 0, chunk = 0, self = 1, fused = 1, fold = 1, fft_carry = 1, hop_kernel = 1, chain = 1,
+       chain_L = 0, relay_flow = 1, segments = 0, xcd_map = 1, rows_f32 = 1, pipeline = 1;
+};
+enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4 };     // = get_option "last_kernel"
+// carries: the single chunk's are the stream state (delta_kernel copies it); pre-pass partial sums + scan (carries from the
+// closed-form table); the serial exact pass (carry_exact_kernel); the relay form of the exact pass (carry_relay_kernel)
+enum CarryForm : int { CARRY_STATE = 0, CARRY_SUMS = 1, CARRY_SERIAL = 2, CARRY_RELAY = 3 };
+enum SumsForm : int { SUMS_NONE = -1, SUMS_DIRECT = 0, SUMS_FFT2 = 1, SUMS_FFT_MIXED = 2 };
+struct ForwardRoute
+{
+  int kernel = FK_TILES;                  // FK_HOP: forward_hop takes the call
+  bool self = false;                      // forward_self takes the call
+  bool pipelined = false;                 // ... on the two row streams (Plan::pipe_this)
+  Range out;                              // the matrix of a dense row-group analysis (the next call's prev_out), else empty
+  long chunks = 1, len = 0, tiles = 1, interior = 1;
+  unsigned relay_L = 0, shift = 0;        // CARRY_RELAY: block length; chunk j starts at sample j * len - shift
+  long segments = 1;                      // time segments of the exact carries (serial pass on the side stream)
+  bool flow = false;                      // relay form, flow mode: one relay launch, forward workgroups wait chunk by chunk
+  int carry = CARRY_STATE, sums = SUMS_NONE;
+  bool delta_in_carry = false;            // the partial-sums kernel forms the differences (no delta_kernel)
+  bool use_seed = true;                   // fid comes from the serial rotation (else the closed-form table)
+  bool fused = false;                     // fused multiply-add arithmetic (FD double, carries from the pre-pass)
+  bool folded = false;                    // the fused call's folded form (process_rows_kernel)
+  bool vec_store = false, rows_f32 = false, arm_flag = false, xcd_map = false;
+};
+
+// what the self-carried form needs of the plan and the call (the kernel that has it is chosen by the caller)
+// (any_length: pipelined calls take the form whatever the length -- one stream runs long calls faster with the pre-pass,
+// n = 1e6: 77.3 against 75.5 % of peak, but two matrices in turn, pipelined: 82.4 %)
+inline bool self_eligible(const ForwardQuery& q, bool fused_call, bool any_length)
+{
+  const size_t most = fused_call ? std::min(kSelfMax, kSelfMaxFused) : kSelfMax;
+  return q.fd_bytes == 8 && !q.exact && q.self && self_cells(q.nbins, q.self >= 1, q.fdx_bytes) != 0 && (q.n <= most || any_length);
+}
+inline ChunkQuery chunk_query(const ForwardQuery& q, bool rows_kernel, bool pipelined)
+{
+  ChunkQuery c;
+  c.n = q.n; c.channels = q.channels; c.nbins = q.nbins; c.rows_kernel = rows_kernel; c.exact = q.exact; c.pipelined = pipelined;
+  c.forced_chunk = q.chunk; c.row_waves = row_waves(q.nbins, q.fdx_bytes); c.tiles = tiles(q.nbins, q.window, q.fdx_bytes, q.interior);
+  c.compute_units = q.compute_units;
+  return c;
+}
+
+// gate_ok(): Plan::gate_ok (allocates the relays' start word on first use), asked only where flow mode is otherwise wanted
+template <class GateOk>
+inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
+{
+  ForwardRoute r;
+  const size_t nb = q.nbins, span = 2 * nb, n = q.n, ch = std::max<size_t>(q.channels, 1);
+  const bool pow2 = (span & (span - 1)) == 0;
+  // the decimated analysis has the tile form only
+  const bool rows = !q.every && rows_kernel_ok(nb, q.fdx_bytes, q.row_pointers, q.rows_kernel != 0, q.row_slots_max);
+  const bool folded = q.fuse && !q.reference_order && !q.fuse_store && q.fold && q.coeff_ready;
+  // pipelined calls (forward_self): decided first because they take the self-carried form at any length and cut time differently
+  // (calls of a few thousand rows gain a microsecond from it and cost the host seven runtime calls instead of one,
+  // 19 against 3 us: n = 4096, m = 1024: 25.6 against 26.4 us per call; from n = 8192 on 30.4 against 32.9)
+  if (!q.fuse && !q.row_pointers && q.out && rows)
+  {
+    r.out = Range{q.out, q.out + ((ch - 1) * q.out_stride + n * nb) * q.fdx_bytes};
+    r.pipelined = q.analysis_batch && q.pipe_wanted && self_eligible(q, false, true) && n < ((size_t)1 << 31) && ch * n * nb >= kPipelineBinsMin &&
+                  !overlap(r.out, q.prev_out) && pipeline_pays(chunk_query(q, true, false), q.pipeline);
+  }
+  // (the folded fused kernel and the row-group forward kernel have the self-carried form)
+  bool self_form = self_eligible(q, q.fuse, r.pipelined) && (q.fuse ? folded : rows);
+  if (self_form && q.fuse)
+  {
+    // the fused kernel folds into its transpose tiles: the 2N cells have to fit them, and it has one or two bins per lane
+    const ProcessGeometry g = process_geometry(nb, ch, n, q.fused != 0, q.fd_bytes, 0);
+    self_form = g.slots <= 2 && self_cells(nb, q.self >= 1, q.fdx_bytes) * q.fdx_bytes <= (size_t)g.waves * kProcGroup * kProcRow * sizeof(double);
+  }
+  if (!self_form) r.pipelined = false;
+  Chunking c;
+  if (q.every)
+  {
+    EveryQuery e;
+    e.n = n; e.channels = ch; e.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); e.exact = q.exact; e.forced_chunk = q.chunk; e.compute_units = q.compute_units;
+    c = choose_every_chunks(e);
+  }
+  else c = choose_chunks(chunk_query(q, rows, r.pipelined));
+  r.chunks = c.chunks; r.len = c.len;
+  r.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); r.interior = interior_lanes(q.window, q.fdx_bytes, q.interior);
+  r.kernel = q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
+  if (r.chunks == 1 && q.hop_kernel && nb >= 2 && !q.fuse && !q.every) { r.kernel = FK_HOP; return r; }
+
+  // self-carried chunks: every workgroup derives its carry-in from the raw samples (fold + one FFT in LDS) and forms
+  // its own differences -- the call is ONE launch.  Kernels that have the form: the row-group forward kernel and the
+  // folded fused kernel, FD double, 2N a power of two of at most 4096 cells.
+  // (the fold of a chunk's past costs t0 / threads loads: hidden behind the other workgroups' row stores in the
+  // analysis, which is bound by HBM -- n = 1e6: 2.885 -> 2.853 ms -- but not in the fused call, which is bound by
+  // instruction issue: n = 48000: 45.9 -> 42.3 us, n = 131072: 99 -> 117 us; hence kSelfMaxFused)
+  // (2N = 2/3/5-smooth: five Stockham stages with table look-ups -- n = 12000, N = 1000, chunks of 64 samples: 47 us with
+  // the pre-pass, 55 us self-carried; n = 48000, chunks of 192: 192 -> 173 us)
+  r.self = self_form && r.chunks > 1 && (pow2 || r.len > 64);
+  if (r.self) return r;
+
+  // exact carries: relay form (seed table + identical waves that take the blocks of L steps in turn, a block's products in
+  // registers) while the serial pass would leave most SIMDs idle; the plain serial pass when bins x channels already
+  // fill the chip.  The chunk grid is shifted so that every chunk but the first starts on a block boundary of the
+  // cursor (chunk j starts at sample j*len - shift; one more chunk may be needed for the tail)
+  const bool chain_ok = q.exact && r.chunks > 1 && q.chain && q.fid_canonical && (q.chain >= 2 || relays(nb) * ch <= 1024);
+  r.relay_L = (chain_ok && n < ((size_t)1 << 31)) ? relay_block(nb, r.len, q.fd_bytes, q.fdx_bytes, q.chain_L) : 0u;
+  if (r.relay_L)
+  {
+    r.shift = (unsigned)(q.cursor % r.relay_L);
+    if (r.shift) r.chunks = (long)((n + r.shift + (size_t)r.len - 1) / (size_t)r.len);
+  }
+  if (r.chunks == 1) r.carry = CARRY_STATE;
+  else if (q.exact) r.carry = r.relay_L ? CARRY_RELAY : CARRY_SERIAL;
+  else
+  {
+    // form of the chunk-parallel partial sums: FFT when 2N is a power of two or 2/3/5-smooth (and fits LDS) -- but
+    // direct sums for chunks of up to 64 samples, which need no barriers (n = 1024 / 4096, N = 1024: 28.0 / 32.1 ->
+    // 24.2 / 28.3 us per call even with one launch more) -- and direct sums for every other size
+    r.carry = CARRY_SUMS;
+    const size_t span_bytes = span * q.fdx_bytes;
+    const bool fft = q.fft_carry && !(r.len <= 64 && q.fft_carry != 2);
+    if (fft && pow2 && span_bytes <= kSumsLds) r.sums = SUMS_FFT2;
+    else if (fft && !pow2 && smooth_radices(span).count > 0 && 2 * span_bytes <= kSumsLds) r.sums = SUMS_FFT_MIXED;
+    else r.sums = SUMS_DIRECT;
+  }
+  r.delta_in_carry = r.carry == CARRY_SUMS;                // K0: differences + delay line -- unless the partial sums form them
+  r.use_seed = r.carry != CARRY_SUMS;
+  if (r.carry == CARRY_SERIAL || r.carry == CARRY_RELAY)
+  {
+    // time segments: the serial pass of segment s+1 (few waves, latency-bound) runs on the side stream while the forward kernel
+    // of segment s streams the matrix; up to 8 segments, each forward launch still filling the chip (>= 256 workgroups)
+    const long launch_blocks = rows ? (long)ch * r.chunks : (long)ch * r.chunks * r.tiles / kWavesPerBlock;
+    r.segments = q.segments > 0 ? q.segments : std::max(1L, std::min(8L, launch_blocks / 256));
+    // Relay form, flow mode: ONE relay launch for the whole call on the side stream and ONE forward launch whose workgroups wait
+    // for their chunk's carries themselves (ForwardArgs::ready).  With segments and events the two passes barely overlap:
+    // a 16-wave forward workgroup fills a CU's registers, so the relays of segment s+1 wait until the forward launch of
+    // segment s has drained (config 3: chain 0.71 ms alone + forward 1.55 ms alone = 2.2 ms together).  Here the relays
+    // hold their CUs from the start, the forward workgroups take whatever is free, in time order, and the whole chip
+    // once the relays are through.  The forward launch is held back (relay_gate_kernel polls a word every relay workgroup
+    // bumps at its start) until the relays are resident: a forward workgroup that waits for a relay which cannot start
+    // would be a deadlock -- every wait in the kernels is bounded all the same, and a time-out re-runs the call (forward_device).
+    r.flow = r.relay_L && q.relay_flow && q.segments <= 0 && (q.fuse || rows) && !q.every && gate_ok();
+    if (r.flow) r.segments = 1;
+    r.segments = std::max(1L, std::min(r.segments, r.chunks));
+  }
+  // fused arithmetic only where the result is not claimed bit-identical: FD double with carries from the pre-pass
+  r.fused = (rows || q.fuse) && q.fused && q.fd_bytes == 8 && !r.use_seed;
+  r.folded = folded;
+  r.vec_store = bins_per_lane(q.fdx_bytes) == 2 && nb % 2 == 0 && q.out % 16 == 0 && q.out_stride % 2 == 0 && !q.row_pointers;
+  // FD float, rows of a multiple of 128 bins, dense aligned output: the bin-pair kernel (sdft_forward_rows_f32.hpp)
+  r.rows_f32 = rows && !q.fuse && q.fd_bytes == 4 && q.rows_f32 && nb % (2 * kLanes) == 0 && r.vec_store;
+  // short synchronous calls: the row-group kernels report their own completion (a word in pinned host memory
+  // reaches the host before the stream does).  Worth it while the kernel has little to write back: n = 4096,
+  // N = 1024: 49.7 -> 46.7 us per sdft_sdft_n, 40.4 -> 35.8 us per fused call; nothing at n = 48000.
+  r.arm_flag = (rows || q.fuse) && r.segments == 1 && ch * n * nb <= (q.fuse ? kFlagMaxFused : kFlagMax);
+  r.xcd_map = q.xcd_map && !r.flow;
+  return r;
+}
+// ForwardArgs::xcd_map of a launch of `groups` (channel, chunk) workgroups
+inline unsigned xcd_groups(bool on, size_t groups) { return (on && groups >= 16) ? (unsigned)groups : 0u; }
+
+// ---- synthesis: the form of a call (Plan::launch_inverse runs it) --------------------------------------------------------------
+constexpr size_t kInverseVerifyMax = 500000;      // rows up to which the tree sum with the rounding-interval proof serves sdft_isdft_n (beyond: the streaming kernel)
+// the bit-identical forms (the numbering is get_option "last_inverse_tuned", + 10 once the tuner has settled) and two static ones:
+// the tree sum without the reference's order (option exact_inverse = 0) and one wave per row
+enum InverseForm : int { F_VERIFY = 0, F_32 = 1, F_16 = 2, F_16W = 3, F_8 = 4, F_4 = 5, F_STEP = 6, F_ORDERED = 7, F_8W = 8, F_TREE = 9, F_ROW = 10 };
+// get_option "last_inverse_form": 0 tree sum, 1 streaming rows, 2 tree sum with the proof, 3 rows in step, 4 ordered rows
+inline long inverse_form_code(int form) { return form == F_TREE ? 0 : form == F_VERIFY ? 2 : form == F_STEP ? 3 : form == F_ORDERED ? 4 : 1; }
+inline long inverse_tuned_code(int form, bool settled) { return 10 * (settled ? 1 : 0) + form; }
+// rows per wave of the streaming forms (what sizes their grid)
+inline long inverse_form_rows(int form)
+{
+  return form == F_32 ? 32 : (form == F_16 || form == F_16W) ? 16 : (form == F_8 || form == F_8W) ? 8 : form == F_4 ? 4 : 1;
+}
+
+struct InverseQuery
+{
+  size_t n = 0, channels = 1, nbins = 0, td_bytes = 4, fd_bytes = 8;
+  size_t in_stride = 0, y_stride = 0;
+  uintptr_t in = 0;
+  bool row_pointers = false, lat1 = true, ops = false;
+  bool nt = false; size_t nt_skip = 0;                 // the matrix's loads are non-temporal but for its first nt_skip rows
+  size_t capacity4 = 0, capacity8 = 0;                 // Plan::inverse_capacity as it stands (0: not asked yet)
+  bool ordered_failed = false;                         // the static ordered launch did not go: the route without it
+  // options
+  long exact = 1, rows = 0, step = 0, ordered = 0, tune = 1, verify = 1, nt_skip_mb = -1;
+};
+struct InverseCandidate { int form = F_VERIFY; size_t nt_skip = 0; };
+struct InverseRoute
+{
+  int form = F_TREE;                                   // the static form (tuned == false) ...
+  long rows_per_wave = 1;                              // ... and its rows per wave (F_32 ... F_4 take forced ones as well: option inverse_rows)
+  bool tuned = false;                                  // the tuner picks among the candidates; entry 0 is the static choice
+  int count = 0;
+  InverseCandidate cand[FormTuner::kMax];
+};
+
+// rows in step (inverse_rows_body): float samples from double bins at latency 1 (the term of a bin is +-re: one register per
+// bin in flight; the general term needs both halves and the kernel's three groups in flight no longer fit 64 registers),
+// dense rows of 64 ... 2048 bins; a form of the rounding-interval proof (option inverse_verify = 0 turns it off with the other one)
+inline bool rows_in_step_ok(const InverseQuery& q)
+{
+  const size_t rows = q.channels * q.n;
+  return q.lat1 && q.td_bytes == 4 && q.fd_bytes == 8 && q.verify && !q.row_pointers && q.nbins >= 64 && q.nbins <= 2048 && rows >= 64 && rows <= 0x7fffffffull * 4;
+}
+// whole rows, ordered sum (inverse_rows_ordered_kernel): every type pair, any latency; rows in one run (one channel, or channels
+// without a gap between them), 16-byte loads -- and rows that fit the kernel's LDS (ordered_geometry(): ordered_rows_geometry::make)
+template <class OrderedGeometry>
+inline bool rows_ordered_ok(const InverseQuery& q, OrderedGeometry&& ordered_geometry)
+{
+  const size_t rows = q.channels * q.n;
+  const bool one_run = q.channels == 1 || (q.in_stride == q.n * q.nbins && q.y_stride == q.n);
+  const bool loads_ok = (q.in & 15) == 0 && (q.fd_bytes == 8 || q.nbins % 2 == 0);
+  return !q.row_pointers && one_run && loads_ok && rows >= 64 && rows <= 0x7fffffffull && ordered_geometry();
+}
+
+// ordered_geometry(): as above; tune_events(): Plan::ensure_tune_events (creates the tuner's events on first use);
+// capacity(c4, c8): Plan's occupancy query for the 4-row and the 8-row form.  Each is asked only where the route needs it.
+template <class OrderedGeometry, class TuneEvents, class Capacity>
+inline InverseRoute inverse_route(const InverseQuery& q, OrderedGeometry&& ordered_geometry, TuneEvents&& tune_events, Capacity&& capacity)
+{
+  InverseRoute r;
+  const size_t rows = q.channels * q.n;
+  const double matrix_bytes = (double)rows * (double)q.nbins * (double)(2 * q.fd_bytes);
+  const bool exact_rows = q.exact && q.rows <= 0;      // the reference's order, rows per wave not forced
+  const bool step_ok = rows_in_step_ok(q);
+  // matrices from 6 GB on: the static choice too (n = 5e5 ... 1e6 x 1024, 64 x 48000 x 1024 / 2048, 250000 x 2048: +5 ... +10 % over
+  // the best streaming form; 4 GB: a tie; below: the streaming forms, by up to 12 % -- profiles/r05_synthesis_rows_in_step.txt)
+  const bool step_static = q.step >= 0 && step_ok && matrix_bytes >= 6.0e9;
+  // (whole rows with the ordered sum: 6.85 TB/s at n = 1e6 x 1024 for every type pair -- rows in step 6.54, the tiles 5.8 ... 6.35;
+  // profiles/r06_synthesis_forms.txt)
+  const bool ordered_ok = !q.ops && exact_rows && q.ordered >= 0 && rows_ordered_ok(q, ordered_geometry);
+  const bool ordered_static = ordered_ok && matrix_bytes >= 7.0e8;      // (48 000 x 1024 double bins: 6.1 TB/s against 5.7 for the best of the tiles; 200 000: 6.65 against 6.2)
+  if (!q.ops)
+  {
+    const bool step_forced = exact_rows && q.step == 1 && q.ordered != 1 && step_ok;
+    if (!q.ordered_failed && ordered_ok && !step_forced && (q.ordered == 1 || (ordered_static && !q.tune))) { r.form = F_ORDERED; return r; }
+    if (exact_rows && ((q.step == 1 && step_ok) || (step_static && !q.tune))) { r.form = F_STEP; return r; }
+  }
+  if (!q.exact) { r.form = F_TREE; return r; }
+  // the reference's summation order.  Measured (n=1e6, N=1024, f64): 32 rows per wave 2.75 ms, 16:
+  // 2.82, 64: 3.6 (130 VGPRs); float bins and medium calls do best with 16; below 64 Ki rows a wave
+  // with 16 rows and one tile of look-ahead is a chain of N/16 memory round trips (~70 us whatever
+  // n is): 4 rows with an 8-deep ring (n = 12000: 33 us against 79, n = 48000: 153 against 178,
+  // n = 131072: 397 against 355); short calls (a hop of 100 rows): one wave per row
+  // float samples from double bins, medium calls: the tree-sum kernel with the rounding-interval test gives the same bits
+  // without the chain of dependent additions (n = 4096: 22.5 -> 11.8 us, 48000: 145 -> 132 us, 200000: 585 -> 550 us;
+  // from about half a million rows on the streaming kernel below is the faster one: 2.64 against 2.78 ms at n = 1e6)
+  // Calls from 8 Ki rows on: the forms that stream at HBM speed differ by a few per cent either way from lease to lease -- 32 /
+  // 16 / 8 / 4 rows per wave, 256- or 512-byte row segments, and (float samples from double bins) the tree sum with the
+  // rounding-interval proof.  All give the same bits, so the plan measures them on the host's own calls (FormTuner;
+  // scripts/synthesis_forms_ab.py: n = 1e6 tree sum +5.5 %, 262144 x 1024 f64f64 16 rows +19 %, m = 4096 FD float 512-byte
+  // segments +13 %; round 4's fixed switch points flipped winner five times between 16 k and 65 k rows).  Candidate 0 is the
+  // static choice.  Forced forms (options inverse_rows / inverse_rpi / inverse_verify = 0) and operations: static.
+  const bool proof = q.td_bytes == 4 && q.fd_bytes == 8;
+  if (!q.ops && q.tune && q.rows <= 0 && rows >= 8192 && tune_events())
+  {
+    r.tuned = true;
+    const bool verify0 = proof && q.verify && rows <= kInverseVerifyMax;
+    const long rw0 = inverse_rows_per_wave(rows, q.fd_bytes, 0, q.capacity4, q.capacity8, false);
+    // candidates: up to kMax pairs (form, rows read first with ordinary loads).  The matrix streams past the caches (non-temporal loads) but for the
+    // rows read first, which take ordinary loads: what an analysis left dirty in the Infinity Cache is slow to a non-temporal load.  1.5 GB of them
+    // are the static choice from 6 GiB on and none below (inverse_ordinary_rows); between 2 and 16 GiB which is better depends on the form
+    // and on whether the host has just written the matrix (4.3 GB: TD = FD = double 1007 -> 835 us with them, f32f64 733 -> 779), so there every
+    // form is tried both ways (profiles/r05_after_write_16gb.txt)
+    const bool both_loads = q.nt && q.nt_skip_mb < 0 && matrix_bytes >= 2.0 * 1073741824.0 && matrix_bytes < 16.0 * 1073741824.0;
+    const size_t other_skip = q.nt_skip ? 0 : inverse_ordinary_rows((size_t)1 << 40, q.nbins * 2 * q.fd_bytes, -1);
+    auto add = [&](int f)
+    {
+      for (int i = 0; i < r.count; ++i) if (r.cand[i].form == f) return;
+      if (r.count < FormTuner::kMax) r.cand[r.count++] = InverseCandidate{f, q.nt_skip};
+      if (both_loads && r.count < FormTuner::kMax) r.cand[r.count++] = InverseCandidate{f, other_skip};
+    };
+    add(ordered_static ? F_ORDERED : step_static ? F_STEP : verify0 ? F_VERIFY : (rw0 >= 32 ? F_32 : rw0 >= 16 ? F_16 : rw0 >= 8 ? F_8 : F_4));
+    // (float samples from double bins: the two forms with the rounding-interval proof first)
+    // (F_8W: 8 rows x 512 bytes, two tiles ahead -- the best of the tiles where rows are too long for the ordered form: 6.8 against 6.6 TB/s at
+    // 500 000 x 2048 double; profiles/r06_synthesis_forms.txt)
+    static constexpr int others_long[7] = {F_ORDERED, F_8W, F_STEP, F_VERIFY, F_16, F_32, F_16W}, others_medium[7] = {F_ORDERED, F_STEP, F_VERIFY, F_4, F_8, F_16, -1};
+    int kinds = 1;
+    for (int f : (rows >= 65536 ? others_long : others_medium))
+    {
+      if (r.count >= FormTuner::kMax || kinds >= (both_loads ? 3 : 4)) break;
+      if (f == r.cand[0].form) continue;
+      if (f < 0 || (f == F_ORDERED && !ordered_ok)) continue;
+      if (f == F_8W && ordered_ok) continue;
+      if (f == F_STEP && !(q.step >= 0 && step_ok)) continue;
+      if (f == F_VERIFY && !(proof && q.verify)) continue;
+      if (f == F_32 && q.fd_bytes != 8) continue;      // (64 registers of row segments: FD double only)
+      add(f); ++kinds;
+    }
+    return r;
+  }
+  if (proof && q.verify && q.rows <= 0 && rows > 1024 && rows <= kInverseVerifyMax) { r.form = F_VERIFY; return r; }
+  // (rows per wave: inverse_rows_per_wave; the capacities of the 4-row and the 8-row form come from the occupancy API)
+  size_t c4 = q.capacity4, c8 = q.capacity8;
+  if (!q.ops && q.rows <= 0 && c4 == 0 && rows > 1024 && rows < 65536) capacity(c4, c8);
+  r.rows_per_wave = inverse_rows_per_wave(rows, q.fd_bytes, q.rows, c4, c8, q.ops);
+  const long rw = r.rows_per_wave;
+  r.form = (rw == 1 && rows <= 0x7fffffffull) ? F_ROW : rw >= 32 ? F_32 : rw >= 16 ? F_16 : rw >= 8 ? F_8 : F_4;
+  return r;
 }
 
 // ---- synchronous completion -----------------------------------------------------------------------------------------------------

@@ -306,6 +306,229 @@ static void test_piece_ring()
   }
 }
 
+// ---- the route of an analysis (forward_route) ---------------------------------------------------------------------------------
+static ForwardQuery random_forward_query()
+{
+  ForwardQuery q;
+  q.fd_bytes = (rnd() & 1) ? 8 : 4; q.fdx_bytes = 2 * q.fd_bytes;
+  static const size_t ms[] = {1, 2, 6, 64, 100, 240, 256, 1000, 1024, 1536, 2048, 4096, 5000};
+  q.nbins = (rnd() & 3) ? ms[rnd() % 13] : rnd_in(1, 5000);
+  q.n = (rnd() & 3) == 0 ? rnd_in(1, 600) : rnd_in(1, 2000000);
+  q.channels = (rnd() & 3) == 0 ? rnd_in(1, 64) : 1;
+  q.window = (int)rnd_in(0, 3);
+  q.cursor = rnd_in(0, 2 * q.nbins - 1);
+  q.exact = rnd() & 1; q.fid_canonical = (rnd() & 3) != 0;
+  q.fuse = (rnd() & 3) == 0;
+  if (q.fuse) { q.fuse_store = (rnd() & 3) == 0; q.reference_order = rnd() & 1; q.coeff_ready = (rnd() & 3) != 0; }
+  q.every = !q.fuse && (rnd() & 3) == 0;
+  q.row_pointers = !q.fuse && !q.every && (rnd() & 7) == 0;
+  q.out = q.row_pointers ? 0 : ((uintptr_t)rnd_in(1, 1000) << 20) + ((rnd() & 3) == 0 ? 8 : 0);
+  q.out_stride = q.n * q.nbins + ((rnd() & 3) == 0 ? 1 : 0);
+  q.analysis_batch = rnd() & 1; q.pipe_wanted = rnd() & 1;
+  if (rnd() & 1) q.prev_out = Range{q.out + 16, q.out + 32};
+  q.rows_kernel = (rnd() & 7) != 0; q.row_slots_max = (rnd() & 7) ? 2 : 1; q.interior = (rnd() & 7) ? 0 : (long)rnd_in(1, 64);
+  q.chunk = (rnd() & 7) ? 0 : (long)rnd_in(1, 5000); q.self = (rnd() & 7) != 0; q.fused = (rnd() & 7) != 0; q.fold = (rnd() & 7) != 0;
+  q.fft_carry = (long)rnd_in(0, 2); q.hop_kernel = (rnd() & 7) != 0; q.chain = (long)rnd_in(0, 2); q.chain_L = (rnd() & 7) ? 0 : (8L << rnd_in(0, 4));
+  q.relay_flow = (rnd() & 3) != 0; q.segments = (rnd() & 3) ? 0 : (long)rnd_in(1, 12); q.xcd_map = rnd() & 1; q.rows_f32 = (rnd() & 3) != 0;
+  q.pipeline = (long)rnd_in(0, 2);
+  return q;
+}
+
+static void test_forward_routes()
+{
+  for (int it = 0; it < 100000; ++it)
+  {
+    const ForwardQuery q = random_forward_query();
+    const bool gate = rnd() & 1;
+    int gates = 0;
+    const ForwardRoute r = forward_route(q, [&] { ++gates; return gate; });
+    const size_t span = 2 * q.nbins;
+    CHECK(r.chunks >= 1 && r.len >= 1 && (size_t)r.chunks * (size_t)r.len >= q.n + r.shift && (size_t)(r.chunks - 1) * (size_t)r.len < q.n + r.shift,
+          "chunks cover the (shifted) call once: n %zu %ld x %ld shift %u", q.n, r.chunks, r.len, r.shift);
+    if (r.chunks == 1 && q.hop_kernel && q.nbins >= 2 && !q.fuse && !q.every) CHECK(r.kernel == FK_HOP, "one chunk, hop kernel on: the hop route");
+    if (r.kernel == FK_HOP) CHECK(r.chunks == 1 && !r.self && !r.fused && !r.flow && gates == 0, "the hop route decides nothing else");
+    if (q.every) CHECK(r.kernel == FK_EVERY && !r.self && !r.pipelined && !r.flow, "decimated: tiles, never self-carried, pipelined or in flow mode");
+    if (q.fd_bytes == 4) CHECK(!r.self && !r.pipelined && !r.fused, "FD float is never self-carried");
+    if (q.exact) CHECK(r.sums == SUMS_NONE && r.carry != CARRY_SUMS && r.use_seed && !r.delta_in_carry && !r.self, "exact carries never take a sums form");
+    if (r.carry == CARRY_SUMS) CHECK(!q.exact && r.chunks > 1 && r.sums != SUMS_NONE && r.delta_in_carry && !r.use_seed, "pre-pass sums");
+    if (r.sums == SUMS_FFT2 || r.sums == SUMS_FFT_MIXED) CHECK(q.fft_carry && (r.len > 64 || q.fft_carry == 2), "short chunks take direct sums");
+    if (r.carry == CARRY_RELAY) CHECK(r.relay_L && span % r.relay_L == 0 && r.len % r.relay_L == 0 && r.shift < r.relay_L, "L %u divides 2N %zu and the chunk %ld", r.relay_L, span, r.len);
+    else CHECK(r.relay_L == 0 && r.shift == 0, "no relay, no block");
+    if (r.flow) CHECK(r.segments == 1 && r.carry == CARRY_RELAY && gate && !r.xcd_map, "flow mode is one segment of the relay form");
+    CHECK(gates <= 1, "the gate is asked at most once");
+    if (gates) CHECK(r.carry == CARRY_RELAY && q.relay_flow && q.segments <= 0 && !q.every, "the gate is asked only where flow mode is otherwise wanted");
+    CHECK(r.segments >= 1 && r.segments <= (q.segments > 0 ? r.chunks : std::min(8L, r.chunks)), "segments %ld of %ld chunks", r.segments, r.chunks);
+    if (r.segments > 1) CHECK(r.carry == CARRY_SERIAL || r.carry == CARRY_RELAY, "segments are the exact pass's");
+    if (r.vec_store) CHECK(q.out % 16 == 0 && q.out_stride % 2 == 0 && q.fdx_bytes == 8 && q.nbins % 2 == 0 && !q.row_pointers, "16-byte stores need alignment");
+    if (r.rows_f32) CHECK(r.kernel == FK_ROWS && !q.fuse && q.fd_bytes == 4 && r.vec_store && q.nbins % 128 == 0, "the bin-pair kernel");
+    if (r.fused) CHECK(q.fd_bytes == 8 && r.carry == CARRY_SUMS && (r.kernel == FK_ROWS || q.fuse), "fused arithmetic only where bits are not claimed");
+    if (r.self) CHECK(r.chunks > 1 && q.fd_bytes == 8 && !q.exact && !q.every && !q.row_pointers && (r.kernel == FK_ROWS || q.fuse), "self-carried");
+    if (r.pipelined) CHECK(!q.fuse && q.pipe_wanted && q.analysis_batch && q.pipeline && r.out.hi > r.out.lo, "pipelined");
+    if (r.arm_flag) CHECK(r.segments == 1 && (r.kernel == FK_ROWS || q.fuse), "the completion word");
+  }
+}
+
+static ForwardQuery fq(size_t n, size_t m, size_t ch, size_t fd, int window, bool exact)
+{
+  ForwardQuery q;
+  q.n = n; q.nbins = m; q.channels = ch; q.fd_bytes = fd; q.fdx_bytes = 2 * fd; q.window = window; q.exact = exact;
+  q.out = (uintptr_t)1 << 40; q.out_stride = n * m;
+  return q;
+}
+
+// routes of named shapes: BASELINE.json configs[0..4], the streaming hop, the decimated analysis and what the GPU tests force
+static void test_forward_shapes()
+{
+  struct Shape { const char* name; ForwardQuery q; int kernel, self, pipelined; long chunks, len; int carry, sums; unsigned L; int flow; long segments; int rows_f32, fused; };
+  ForwardQuery pipe = fq(48000, 1024, 1, 8, kWindowHann, false); pipe.analysis_batch = pipe.pipe_wanted = true;
+  ForwardQuery tiles_q = fq(48000, 1024, 1, 8, kWindowHann, false); tiles_q.rows_kernel = 0;
+  ForwardQuery every = fq(48000, 1024, 1, 8, kWindowHann, false); every.every = true;
+  ForwardQuery smoke = fq(6000, 1024, 1, 8, kWindowHann, false); smoke.chunk = 256;
+  ForwardQuery smoke32 = fq(6000, 256, 1, 4, kWindowBlackman, true); smoke32.chunk = 512;
+  ForwardQuery seg = fq(6000, 256, 1, 8, kWindowHann, true); seg.chunk = 200; seg.segments = 7;
+  ForwardQuery serial = seg; serial.chain = 0;
+  ForwardQuery mixed = fq(48000, 1000, 1, 8, kWindowHann, false); mixed.self = 0; mixed.fft_carry = 2;
+  const Shape shapes[] = {
+    {"configs[0], north star", fq(48000, 1024, 1, 8, kWindowHann, false), FK_ROWS, 1, 0, 250, 192, CARRY_STATE, SUMS_NONE, 0, 0, 1, 0, 0},
+    {"configs[0], two matrices in turn", pipe, FK_ROWS, 1, 1, 300, 160, CARRY_STATE, SUMS_NONE, 0, 0, 1, 0, 0},
+    {"configs[1], n = 1e6", fq(1000000, 1024, 1, 8, kWindowHann, false), FK_ROWS, 0, 0, 511, 1960, CARRY_SUMS, SUMS_FFT2, 0, 0, 1, 0, 1},
+    {"configs[2], m = 4096 FD float", fq(262144, 4096, 1, 4, kWindowBlackman, true), FK_ROWS, 0, 0, 2048, 128, CARRY_RELAY, SUMS_NONE, 128, 1, 1, 1, 0},
+    {"configs[3], 64 x 48000, m = 2048", fq(48000, 2048, 64, 8, kWindowHann, false), FK_ROWS, 1, 0, 8, 6000, CARRY_STATE, SUMS_NONE, 0, 0, 1, 0, 0},
+    {"configs[4], 64 x 48000 per GPU", fq(48000, 1024, 64, 8, kWindowHann, false), FK_ROWS, 1, 0, 8, 6000, CARRY_STATE, SUMS_NONE, 0, 0, 1, 0, 0},
+    {"hop of 100 at m = 1000", fq(100, 1000, 1, 8, kWindowHann, false), FK_HOP, 0, 0, 1, 100, CARRY_STATE, SUMS_NONE, 0, 0, 1, 0, 0},
+    {"every, n = 48000", every, FK_EVERY, 0, 0, 182, 264, CARRY_SUMS, SUMS_FFT2, 0, 0, 1, 0, 0},
+    {"rows_kernel 0", tiles_q, FK_TILES, 0, 0, 750, 64, CARRY_SUMS, SUMS_DIRECT, 0, 0, 1, 0, 0},
+    {"smoke, chunk 256", smoke, FK_ROWS, 1, 0, 24, 256, CARRY_STATE, SUMS_NONE, 0, 0, 1, 0, 0},
+    {"smoke, f32f32 exact, chunk 512", smoke32, FK_ROWS, 0, 0, 12, 512, CARRY_RELAY, SUMS_NONE, 128, 1, 1, 1, 0},
+    {"exact, chunk 200, segments 7", seg, FK_ROWS, 0, 0, 30, 200, CARRY_RELAY, SUMS_NONE, 8, 0, 7, 0, 0},
+    {"exact, chain 0, segments 7", serial, FK_ROWS, 0, 0, 30, 200, CARRY_SERIAL, SUMS_NONE, 0, 0, 7, 0, 0},
+    {"2N = 2000, mixed-radix sums", mixed, FK_ROWS, 0, 0, 250, 192, CARRY_SUMS, SUMS_FFT_MIXED, 0, 0, 1, 0, 1},
+  };
+  for (const Shape& s : shapes)
+  {
+    const ForwardRoute r = forward_route(s.q, [] { return true; });
+    CHECK(r.kernel == s.kernel && r.self == (s.self != 0) && r.pipelined == (s.pipelined != 0), "%s: kernel %d self %d pipelined %d", s.name, r.kernel, (int)r.self, (int)r.pipelined);
+    CHECK(r.chunks == s.chunks && r.len == s.len, "%s: %ld x %ld", s.name, r.chunks, r.len);
+    CHECK(r.carry == s.carry && r.sums == s.sums && r.relay_L == s.L && r.flow == (s.flow != 0) && r.segments == s.segments, "%s: carry %d sums %d L %u flow %d segments %ld",
+          s.name, r.carry, r.sums, r.relay_L, (int)r.flow, r.segments);
+    CHECK(r.rows_f32 == (s.rows_f32 != 0) && r.fused == (s.fused != 0), "%s: rows_f32 %d fused %d", s.name, (int)r.rows_f32, (int)r.fused);
+  }
+}
+
+// ---- the form of a synthesis (inverse_route) ----------------------------------------------------------------------------------
+static InverseQuery iq(size_t n, size_t m, size_t ch, size_t td, size_t fd)
+{
+  InverseQuery q;
+  q.n = n; q.channels = ch; q.nbins = m; q.td_bytes = td; q.fd_bytes = fd; q.in_stride = n * m; q.y_stride = n; q.in = (uintptr_t)1 << 40;
+  const size_t matrix = ch * n * m * 2 * fd;
+  q.nt = inverse_streaming_loads(matrix, -1); q.nt_skip = inverse_ordinary_rows(matrix, m * 2 * fd, -1);
+  return q;
+}
+
+static void test_inverse_routes()
+{
+  const double GiB = 1073741824.0;
+  static const size_t types[4][2] = {{4, 8}, {4, 4}, {8, 8}, {8, 4}};
+  static const size_t ms[] = {6, 64, 320, 1000, 1024, 1536, 2048, 4096};
+  for (int it = 0; it < 100000; ++it)
+  {
+    const int ty = (int)rnd_in(0, 3);
+    InverseQuery q = iq(rnd_in(0, 2) == 0 ? rnd_in(1, 2000) : rnd_in(1, 1200000), ms[rnd() % 8], (rnd() & 3) ? 1 : rnd_in(1, 64), types[ty][0], types[ty][1]);
+    if ((rnd() & 3) == 0) q.in_stride += 1;
+    if ((rnd() & 3) == 0) q.in += 8;
+    q.row_pointers = (rnd() & 7) == 0; q.lat1 = rnd() & 1; q.ops = (rnd() & 3) == 0;
+    if (rnd() & 1) { q.nt = rnd() & 1; q.nt_skip = (rnd() & 1) ? 0 : rnd_in(1, 100000); }
+    q.capacity4 = (rnd() & 1) ? 0 : rnd_in(1, 20000); q.capacity8 = q.capacity4 ? rnd_in(1, 20000) : 0;
+    q.ordered_failed = (rnd() & 7) == 0;
+    q.exact = (rnd() & 7) != 0; q.rows = (rnd() & 7) ? 0 : (1L << rnd_in(0, 5)); q.step = (long)rnd_in(0, 2) - 1; q.ordered = (long)rnd_in(0, 2) - 1;
+    q.tune = (rnd() & 3) != 0; q.verify = (rnd() & 7) != 0; q.nt_skip_mb = (rnd() & 3) ? -1 : (long)rnd_in(0, 2000);
+    const bool geo = rnd() & 1, events = (rnd() & 7) != 0;
+    int geos = 0, evs = 0, caps = 0;
+    auto geometry = [&] { ++geos; return geo; };
+    auto tune_events = [&] { ++evs; return events; };
+    auto capacity = [&](size_t& c4, size_t& c8) { ++caps; c4 = q.capacity4; c8 = q.capacity8; };
+    const InverseRoute r = inverse_route(q, geometry, tune_events, capacity);
+    const size_t rows = q.channels * q.n;
+    const double matrix = (double)rows * (double)q.nbins * (double)(2 * q.fd_bytes);
+    const bool ordered_ok = !q.ops && q.exact && q.rows <= 0 && q.ordered >= 0 && rows_ordered_ok(q, [&] { return geo; });
+    CHECK(geos <= 1 && evs <= 1 && caps <= 1, "every probe at most once: %d %d %d", geos, evs, caps);
+    if (caps) CHECK(!r.tuned && q.capacity4 == 0 && !q.ops && q.rows <= 0 && rows > 1024 && rows < 65536, "the occupancy is asked by the static streaming form only");
+    if (evs) CHECK(!q.ops && q.tune && q.exact && q.rows <= 0 && rows >= 8192, "the tuner's events only where it may run");
+    if (r.tuned) CHECK(evs == 1 && events, "tuned calls have their events");
+    if (q.ops) CHECK(!r.tuned && r.form != F_ORDERED && r.form != F_STEP, "operations never take the ordered, in-step or tuned forms");
+    if (!q.exact) CHECK(!r.tuned && r.form == F_TREE, "exact_inverse = 0: the tree sum");
+    if (!r.tuned && r.form == F_ORDERED) CHECK(ordered_ok && !q.ordered_failed, "the static ordered form where it applies");
+    if (!r.tuned && r.form == F_STEP) CHECK(rows_in_step_ok(q) && q.exact && q.rows <= 0, "rows in step where they apply");
+    if (!r.tuned) continue;
+    CHECK(r.count >= 1 && r.count <= FormTuner::kMax, "%d candidates", r.count);
+    const bool both_loads = q.nt && q.nt_skip_mb < 0 && matrix >= 2.0 * GiB && matrix < 16.0 * GiB;
+    for (int i = 0; i < r.count; ++i)
+    {
+      const int f = r.cand[i].form;
+      CHECK(f != F_TREE && f != F_ROW, "candidates are the bit-identical streaming forms");
+      CHECK(f != F_32 || q.fd_bytes == 8, "F_32 is never a candidate at FD float");
+      CHECK(f != F_8W || !ordered_ok, "F_8W is never a candidate where the ordered form applies");
+      CHECK(f != F_ORDERED || ordered_ok, "F_ORDERED only where it applies");
+      CHECK(f != F_STEP || rows_in_step_ok(q), "F_STEP only where it applies");
+      int same = 0;
+      for (int j = 0; j < r.count; ++j)
+      {
+        if (j != i) CHECK(!(r.cand[j].form == f && r.cand[j].nt_skip == r.cand[i].nt_skip), "no duplicate pairs");
+        if (r.cand[j].form == f) ++same;
+      }
+      CHECK(same == (both_loads ? 2 : 1), "with both kinds of load every form is tried both ways: form %d %d times", f, same);
+    }
+    CHECK(r.cand[0].nt_skip == q.nt_skip, "entry 0 takes the call's own loads");
+    if (q.ordered_failed) continue;
+    // entry 0 is the static choice: the route without the tuner (with the same capacities)
+    InverseQuery s = q; s.tune = 0;
+    const InverseRoute st = inverse_route(s, [&] { return geo; }, [] { return true; }, [&](size_t& c4, size_t& c8) { c4 = q.capacity4; c8 = q.capacity8; });
+    CHECK(!st.tuned && st.form == r.cand[0].form, "entry 0 (%d) is the static choice (%d)", r.cand[0].form, st.form);
+  }
+}
+
+static void test_inverse_shapes()
+{
+  struct Shape { const char* name; InverseQuery q; bool geo; bool tuned; int form; int count; long code; };
+  InverseQuery c1_static = iq(1000000, 1024, 1, 4, 8); c1_static.tune = 0;
+  InverseQuery c1_step = c1_static; c1_step.ordered = -1;
+  InverseQuery c1_refused = c1_static; c1_refused.ordered_failed = true;
+  InverseQuery tree = iq(48000, 1024, 1, 4, 8); tree.exact = 0;
+  InverseQuery verify = iq(4096, 1024, 1, 4, 8); verify.tune = 0;
+  InverseQuery rows4 = iq(48000, 1024, 1, 4, 8); rows4.rows = 4;
+  InverseQuery op = iq(48000, 1024, 1, 8, 8); op.ops = true;
+  InverseQuery forced = iq(70000, 1024, 1, 8, 8); forced.ordered = 1;
+  const Shape shapes[] = {
+    {"configs[0], north star", iq(48000, 1024, 1, 4, 8), true, true, F_ORDERED, 4, 4},
+    {"configs[1], n = 1e6", iq(1000000, 1024, 1, 4, 8), true, true, F_ORDERED, 6, 4},
+    {"configs[1], inverse_tune 0", c1_static, true, false, F_ORDERED, 0, 4},
+    {"configs[1], inverse_tune 0, inverse_ordered -1", c1_step, true, false, F_STEP, 0, 3},
+    {"configs[1], the ordered form's LDS refused", c1_refused, true, false, F_STEP, 0, 3},
+    {"configs[2], m = 4096 FD float", iq(262144, 4096, 1, 4, 4), false, true, F_16, 6, 1},
+    {"configs[3], 64 x 48000, m = 2048", iq(48000, 2048, 64, 4, 8), false, true, F_STEP, 4, 3},
+    {"hop of 100 at m = 1000", iq(100, 1000, 1, 4, 8), true, false, F_ROW, 0, 1},
+    {"exact_inverse 0", tree, true, false, F_TREE, 0, 0},
+    {"n = 4096, inverse_tune 0", verify, true, false, F_VERIFY, 0, 2},
+    {"inverse_rows 4", rows4, true, false, F_4, 0, 1},
+    {"an operation, f64f64", op, true, false, F_16, 0, 1},
+    {"inverse_ordered 1", forced, true, false, F_ORDERED, 0, 4},
+  };
+  for (const Shape& s : shapes)
+  {
+    const InverseRoute r = inverse_route(s.q, [&] { return s.geo; }, [] { return true; }, [](size_t& c4, size_t& c8) { c4 = c8 = (size_t)-1; });
+    const int form = r.tuned ? r.cand[0].form : r.form;
+    CHECK(r.tuned == s.tuned && form == s.form && (!r.tuned || r.count == s.count) && inverse_form_code(form) == s.code,
+          "%s: tuned %d form %d count %d", s.name, (int)r.tuned, form, r.count);
+  }
+  // configs[2]: the whole list -- three forms, each with and without the rows read first by ordinary loads
+  const InverseRoute r = inverse_route(iq(262144, 4096, 1, 4, 4), [] { return false; }, [] { return true; }, [](size_t&, size_t&) {});
+  const InverseCandidate want[6] = {{F_16, 49152}, {F_16, 0}, {F_8W, 49152}, {F_8W, 0}, {F_16W, 49152}, {F_16W, 0}};
+  for (int i = 0; i < 6; ++i) CHECK(r.cand[i].form == want[i].form && r.cand[i].nt_skip == want[i].nt_skip, "configs[2] candidate %d: %d %zu", i, r.cand[i].form, r.cand[i].nt_skip);
+  CHECK(inverse_tuned_code(F_ORDERED, false) == 7 && inverse_tuned_code(F_STEP, true) == 16 && inverse_form_rows(F_8W) == 8, "codes");
+  CHECK(relays(1024) == 32 && relays(1000) == 32 && relays(1) == 1, "relays of 32 bins");
+  CHECK(xcd_groups(true, 16) == 16 && xcd_groups(true, 15) == 0 && xcd_groups(false, 100) == 0, "xcd map");
+}
+
 int main()
 {
   test_geometry();
@@ -317,6 +540,10 @@ int main()
   test_small_decisions();
   test_piece_ring();
   test_form_tuner();
+  test_forward_routes();
+  test_forward_shapes();
+  test_inverse_routes();
+  test_inverse_shapes();
   if (failures) { fprintf(stderr, "%d failure(s)\n", failures); return 1; }
   printf("plan logic: all properties hold\n");
   return 0;
