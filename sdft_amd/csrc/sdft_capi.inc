@@ -44,9 +44,8 @@ size_t SDFT_FN(channels)(const void* p) { return p ? P(p)->channels : 0; }
 void SDFT_FN(sdft)(void* p, SDFT_TD sample, void* dft)
 {
   if (!p) return;
-  const bool saved = P(p)->async; P(p)->async = false;
+  sdfthip::Scoped<bool> sync(P(p)->async, false);
   (void)P(p)->sdft_n(1, &sample, static_cast<fdx_t*>(dft), 0 /* the by-value sample lives on the host stack */);
-  P(p)->async = saved;
 }
 // sdft.h:607 -- dense (nsamples, dftsize); batched plans: x [channels][n], dfts [channels][n][dftsize]
 void SDFT_FN(sdft_n)(void* p, size_t n, const SDFT_TD* x, void* dfts)

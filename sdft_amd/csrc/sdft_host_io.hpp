@@ -64,7 +64,6 @@ class HostIo
   // pages with their heap neighbours), at most 8 ranges that never share a page; anything the runtime refuses
   // falls back to the staged path.  Option "host_register" = 1 turns it on, a buffer of more than 256 MiB is never registered: the
   // bytes of one buffer (default 256 MiB: longer calls run at PCIe speed through the staged path anyway).
-  static constexpr size_t kSmallHostBytes = (size_t)64 << 10;
   static constexpr size_t kHostRegisterMin = (size_t)1 << 20;       // smaller buffers share pages with their heap neighbours: staged
   // OFF by default: a registration dies with the mapping it was made on.  A host that frees a buffer and gets the same
   // address back from its allocator (numpy does, every call) would make a remembered registration fault the GPU
@@ -160,7 +159,7 @@ class HostIo
   static constexpr size_t kBigPiece = (size_t)8 << 20;
   static constexpr size_t kBigCopy = (size_t)32 << 20;
   char* h_big = nullptr;
-  static constexpr size_t kDirectBytes = 2 * kPinPiece;      // a hop-sized matrix the kernels write / read in the pinned memory itself
+  static_assert(logic::kDirectBytes == 2 * kPinPiece, "a hop-sized matrix the kernels write / read in the pinned memory itself fills both pieces");
   long opt_host_copy = 0;
   long opt_host_direct = 1;                                  // hop-sized matrices: the kernels work on the pinned pieces themselves
   long opt_copy_threads = 2;                                 // worker threads of the host copies (0: the calling thread alone)

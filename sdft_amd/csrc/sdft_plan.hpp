@@ -100,6 +100,15 @@ enum CarryMode : int { CARRY_FAST = 0, CARRY_EXACT = 1 };
 
 enum ProfileStage : int { ST_DELTA = 0, ST_CARRY = 1, ST_FORWARD = 2, ST_INVERSE = 3, ST_COUNT = 4 };
 
+// a value a member holds for a scope: the old one is back on every way out
+template <typename T> struct Scoped
+{
+  T& ref; const T old;
+  Scoped(T& r, T v) : ref(r), old(r) { r = v; }
+  ~Scoped() { ref = old; }
+  Scoped(const Scoped&) = delete;                          // (not assignable either: a reference member)
+};
+
 template <typename TD, typename FD>
 class Plan
 {
@@ -131,8 +140,7 @@ class Plan
   long opt_float_parallel = 0;
   long opt_chunk = 0;            // forced chunk length (0 = heuristic)
   long opt_interior = 0;         // forced interior lanes per wave (0 = maximum)
-  static constexpr size_t kDefaultStageBytes = (size_t)1 << 30;
-  size_t stage_bytes = kDefaultStageBytes;   // host-pointer path: staging segment size
+  size_t stage_bytes = logic::kDefaultStageBytes;   // host-pointer path: staging segment size
   int profile = 0;               // 0 off, 1 = events around every stage, 2 = forward/inverse kernels only
   long opt_rows_kernel = 1;      // use the row-group forward kernel when the row fits one workgroup
   long opt_xcd_map = 1;          // every XCD takes a contiguous eighth of a launch's (channel, chunk) workgroups (ForwardArgs::xcd_map)
@@ -519,21 +527,20 @@ class Plan
   bool forward_device(size_t n, const TD* x, size_t x_stride, fdx* out, size_t out_stride, fdx* const* rows,
                       const FuseArgs<TD, FD>* fuse = nullptr, const EveryGrid* every = nullptr)
   {
-    const size_t cursor0 = cursor;
-    const int st0 = st_cur, hist0 = hist_cur;
-    const bool canon0 = fid_canonical;
+    const struct { size_t cursor; int st_cur, hist_cur; bool fid_canonical; } was{cursor, st_cur, hist_cur, fid_canonical};
+    auto restore = [&] { cursor = was.cursor; st_cur = was.st_cur; hist_cur = was.hist_cur; fid_canonical = was.fid_canonical; };
     if (!forward_launch(n, x, x_stride, out, out_stride, rows, fuse, every))
     {
       // a launch that failed half-way (a host expression that does not compile, a grid that does not fit, an allocation)
       // must not leave the stream half-advanced: what was queued wrote the OTHER buffer set and the workspace only
-      cursor = cursor0; st_cur = st0; hist_cur = hist0; fid_canonical = canon0;
+      restore();
       return false;
     }
     if (last_chain < 2 || async) return true;
     SDFT_TRY(hipStreamSynchronize(stream));
     if (aux) SDFT_TRY(hipStreamSynchronize(aux));
     if (!ring_gave_up()) return true;
-    cursor = cursor0; st_cur = st0; hist_cur = hist0; fid_canonical = canon0;
+    restore();
     const long saved = opt_chain;
     opt_chain = 0;
     const bool ok = forward_launch(n, x, x_stride, out, out_stride, rows, fuse, every) && (hipStreamSynchronize(stream) == hipSuccess);
@@ -544,7 +551,7 @@ class Plan
     if (ok) set_warning("carry_relay_kernel", "a poll loop timed out; the call was re-run with the serial carry pass (results are valid)");
     else
     {
-      cursor = cursor0; st_cur = st0; hist_cur = hist0; fid_canonical = canon0;
+      restore();
       set_error("carry_relay_kernel", "a poll loop timed out and the re-run with the serial carry pass failed");
     }
     return ok;
@@ -799,7 +806,7 @@ class Plan
       const unsigned threads = (unsigned)(row_waves() * kWave);
       if (fuse)
       {
-        // rows never leave the workgroup: synthesis in the same launch (caller checked fuse_ok())
+        // rows never leave the workgroup: synthesis in the same launch (caller checked rows_kernel_ok())
         if (r.folded) { if (!launch_process(fa, *fuse, (unsigned)groups, r.fused)) return false; }
         else if (r.kernel != logic::FK_ROWS) { set_error("sdft_hip_process_n", "rows of this length are fused in the folded form only"); return false; }
         else if (!launch_syn(fa, *fuse, (unsigned)groups, threads, r.fused && !exact_order, exact_order)) return false;
@@ -1050,11 +1057,10 @@ class Plan
         ForwardArgs<FD> fr = fa; SelfArgs<TD, FD> sr = sa;
         fr.acc_state = nullptr; fr.fid_state = nullptr; sr.hist_out = nullptr;
         fr.done.flag = nullptr; fr.done.count = nullptr; fr.done.seq = 0; fr.done.total = 0;
-        hipStream_t main_stream = stream;
-        stream = rs;
-        const bool ok = launch_forward_rows_self(fr, sr, blocks, (unsigned)(row_waves() * kWave), fused);
-        stream = main_stream;
-        if (!ok) return false;
+        {
+          Scoped<hipStream_t> on(stream, rs);
+          if (!launch_forward_rows_self(fr, sr, blocks, (unsigned)(row_waves() * kWave), fused)) return false;
+        }
         SDFT_TRY(hipEventRecord(ev_rows[ring.slot()], rs));
         ring.launched(olo, ohi, rsi);
         ++pipe_calls;
@@ -1275,7 +1281,6 @@ class Plan
     const bool inv_pipe = calls.inverse_batch && pipe_allowed && !rows && !ops_wanted && async && own_stream && !stream_exposed && opt_pipeline && profile == 0 &&
                           channels * n * nbins >= logic::kPipelineBinsMin && ensure_pipe();
     if (!(inv_pipe ? pipe_join_rows() : pipe_join())) return false;
-    hipStream_t main_stream = stream;
     int si = 0;
     uintptr_t ylo = 0, yhi = 0;
     if (inv_pipe)
@@ -1290,9 +1295,8 @@ class Plan
       // what the OTHER row stream still has outstanding: samples this call overwrites (a host that rotates three sample
       // buffers) or a matrix that was reinterpreted from them -- ordered behind it
       if (pk.wait_other) SDFT_TRY(hipStreamWaitEvent(row_streams[si], ev_inv[si ^ 1], 0));
-      stream = row_streams[si];
     }
-    struct Restore { hipStream_t& s; hipStream_t v; ~Restore() { s = v; } } restore{stream, main_stream};
+    Scoped<hipStream_t> on(stream, inv_pipe ? row_streams[si] : stream);
     if (!prof_begin(ST_INVERSE)) return false;
     InverseArgs<TD, FD> ia;
     ia.in = in; ia.in_stride = in_stride; ia.in_rows = rows; ia.syn = d_syn.p; ia.y = y; ia.y_stride = y_stride;
@@ -1429,10 +1433,8 @@ class Plan
   // wrote over PCIe (a stream query that reports "done" first keeps the wait short; the synchronisation then returns at once)
   bool finish_mapped(size_t hbm_bytes)
   {
-    const bool saved = async; async = false;
-    const bool ok = finish(hbm_bytes);
-    async = saved;
-    if (!ok) return false;
+    Scoped<bool> sync(async, false);
+    if (!finish(hbm_bytes)) return false;
     SDFT_TRY(hipStreamSynchronize(stream));
     return true;
   }
@@ -1452,7 +1454,6 @@ class Plan
 
   // ---- the caller's host memory (sdft_host_io.hpp): registered in place, or copied through pinned slots of the plan ----------
   HostIo io;
-  static constexpr size_t kSmallHostBytes = HostIo::kSmallHostBytes;
   void* map_host(const void* p, size_t bytes, bool will_write = false) { return io.map_host(p, bytes, will_write); }
   // Both are complete on return as far as the caller's memory goes: to_device has read it, to_host has written it.
   bool copy_failed() { set_error("host copy", "a copy between host memory and the device through the plan's pinned slots failed"); return false; }
@@ -1485,15 +1486,14 @@ class Plan
 
   // Small host-side sample buffers (a hop of the host's signal, the by-value sample of sdft_sdft, the sample sdft_isdft
   // returns) do not go through the runtime's pageable copy path (5-10 us per copy): they travel through a pinned scratch
-  // of the plan that the kernels read and write directly over PCIe, and the call completes on the kernel's completion
-  // word.  Single-sample calls on a device row: 21.9 -> see profiles/r04_single_sample.txt.
-  static constexpr size_t kIoBytes = (size_t)64 << 10;      // = kSmallHostBytes: samples in the first half... one direction per call
+  // of the plan (logic::kSmallHostBytes, one direction per call) that the kernels read and write directly over PCIe, and the
+  // call completes on the kernel's completion word.  Single-sample calls on a device row: 21.9 -> see profiles/r04_single_sample.txt.
   TD* h_io = nullptr;
   TD* d_io = nullptr;
   bool ensure_io()
   {
     if (h_io) return true;
-    if (hipHostMalloc((void**)&h_io, kIoBytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { (void)hipGetLastError(); h_io = nullptr; return false; }
+    if (hipHostMalloc((void**)&h_io, logic::kSmallHostBytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { (void)hipGetLastError(); h_io = nullptr; return false; }
     if (hipHostGetDevicePointer((void**)&d_io, h_io, 0) != hipSuccess) { (void)hipGetLastError(); (void)hipHostFree(h_io); h_io = nullptr; d_io = nullptr; return false; }
     return true;
   }

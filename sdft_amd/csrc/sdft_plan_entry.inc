@@ -1,7 +1,61 @@
 // sdft_plan_entry.inc -- member functions of Plan<TD, FD> (included inside the class body by sdft_plan.hpp): the entry points
 // behind the C-ABI -- dense matrices or row-pointer tables, host or device pointers, single samples, the fused call, state
-// access -- and the routes host memory takes through them (pinned scratch, registered in place, pinned slots, staged segments).
+// access.  They run the routes sdft_plan_logic.hpp decides: host memory (logic::host_route), the fused call (logic::process_route).
 // Citations are into /root/reference/c/src/sdft/sdft.h.
+
+  // ---- host memory: the route of a call, and the one loop of the staged route ---------------------------------------
+  // td: the samples side of the call, mat: its matrix side; td_map / mat_map receive the device-side address of a side the route
+  // registered in place (whichever side the kernels write is registered writable)
+  logic::HostRoute host_route(bool analysis, size_t n, const TD* td, bool td_device, bool by_value, const fdx* mat, bool mat_device, TD*& td_map, fdx*& mat_map)
+  {
+    logic::HostQuery q;
+    q.analysis = analysis; q.samples_device = td_device; q.matrix_device = mat_device; q.by_value = by_value;
+    q.samples_bytes = channels * n * sizeof(TD); q.matrix_bytes = matrix_bytes(n);
+    q.pinned_io = opt_pinned_io; q.host_copy = io.opt_host_copy; q.host_direct = io.opt_host_direct;
+    q.stage_bytes = stage_bytes; q.n = n; q.row_bytes = channels * nbins * sizeof(fdx);
+    return logic::host_route(q, [&] { return ensure_io(); },
+                             [&] { return (mat_map = static_cast<fdx*>(map_host(mat, q.matrix_bytes, analysis))) != nullptr; },
+                             [&] { return (td_map = static_cast<TD*>(map_host(td, q.samples_bytes, !analysis))) != nullptr; },
+                             [&] { return io.ensure_pin(); }, [&] { return io.pin_idle(); });
+  }
+
+  // A call in time segments of at most `seg` samples: a side that is host memory goes through device scratch (copied in before
+  // the segment runs, out after it), a side that is device memory is used where it is.  run(Segment&) does the segment's device
+  // call on s.td / s.mat; an analysis that keeps fewer rows than samples (sdft_every_n) sets s.row0 / s.rows, the rows copied out.
+  struct StagedCall
+  {
+    bool analysis; TD* td; bool td_host; fdx* mat; bool mat_host;
+    size_t mat_rows, seg_rows;                               // matrix rows of the whole call; of one segment, at most
+  };
+  struct Segment { size_t t, m; TD* td; size_t td_stride; fdx* mat; size_t mat_stride, row0, rows; };
+  template <class Run>
+  bool staged_segments(size_t n, size_t seg, const StagedCall& c, Run&& run)
+  {
+    const size_t nb = nbins;
+    if (c.td_host && !d_stage_td.reserve(channels * seg)) return false;
+    if (c.mat_host && !d_stage_fdx.reserve(channels * c.seg_rows * nb)) return false;
+    for (size_t t = 0; t < n; t += seg)
+    {
+      const size_t m = std::min(seg, n - t);
+      Segment s{t, m, c.td_host ? d_stage_td.p : c.td + t, c.td_host ? m : n,
+                c.mat_host ? d_stage_fdx.p : (c.mat ? c.mat + t * nb : nullptr), (c.mat_host ? m : c.mat_rows) * nb, t, m};
+      if (c.analysis && c.td_host && !copy2d(s.td, m * sizeof(TD), c.td + t, n * sizeof(TD), m * sizeof(TD), hipMemcpyHostToDevice)) return false;
+      if (!c.analysis && c.mat_host && !copy2d(s.mat, m * nb * sizeof(fdx), c.mat + t * nb, n * nb * sizeof(fdx), m * nb * sizeof(fdx), hipMemcpyHostToDevice)) return false;
+      if (!run(s)) return false;
+      if (c.analysis && c.mat_host && s.rows &&
+          !copy2d(c.mat + s.row0 * nb, c.mat_rows * nb * sizeof(fdx), s.mat, s.rows * nb * sizeof(fdx), s.rows * nb * sizeof(fdx), hipMemcpyDeviceToHost)) return false;
+      if (!c.analysis && c.td_host && !copy2d(c.td + t, n * sizeof(TD), s.td, m * sizeof(TD), m * sizeof(TD), hipMemcpyDeviceToHost)) return false;
+      SDFT_TRY(hipStreamSynchronize(stream));                // scratch buffers are reused; host memory is complete on return
+    }
+    return synchronize();
+  }
+
+  // host samples through device scratch (one small copy); nullptr: failed
+  const TD* staged_samples(const TD* x, size_t count)
+  {
+    if (!d_stage_td.reserve(count) || !to_device(d_stage_td.p, x, count * sizeof(TD))) return nullptr;
+    return d_stage_td.p;
+  }
 
   // ---- public entry points: dense matrices, host or device pointers ---------------------------
   // x: [channels][n], dfts: [channels][n][N]
@@ -14,106 +68,33 @@
     if (!bind()) return false;
     const bool xd = x_class < 0 ? on_device(x) : x_class != 0;
     const bool od = on_device(dfts);
-    if (xd && od)
+    TD* x_map = nullptr; fdx* o_map = nullptr;
+    const logic::HostRoute r = host_route(true, n, x, xd, x_class == 0, dfts, od, x_map, o_map);
+    if (r.refused) return copy_failed();
+    if (r.route == logic::HR_STAGED)
+      return staged_segments(n, r.seg, StagedCall{true, const_cast<TD*>(x), !xd, dfts, !od, n, r.seg},
+                             [&](Segment& s) { return forward_device(s.m, s.td, s.td_stride, s.mat, s.mat_stride, nullptr); });
+    // one launch on the whole call: the samples and the matrix as the kernels see them
+    const size_t xbytes = channels * n * sizeof(TD), obytes = matrix_bytes(n);
+    const bool direct = r.route == logic::HR_DIRECT;
+    const TD* xs = r.samples == logic::HS_MAPPED ? x_map : x;
+    if (r.samples == logic::HS_IO) { memcpy(h_io, x, xbytes); xs = d_io; }
+    if (r.samples == logic::HS_STAGE_TD && !(xs = staged_samples(x, channels * n))) return false;
+    fdx* out = direct ? reinterpret_cast<fdx*>(io.d_pin) : (od ? dfts : o_map);
+    // (the flags hold until the function returns; only the launches read them -- arm_flag, hop_parts, the pipe tests -- not finish)
+    Scoped<bool> sync(async, async && !r.synchronous), flag(flag_wanted, r.flag_wanted), pipe(pipe_allowed, r.pipe_allowed);
+    if (direct) ++io.pin_copies;
+    const double t0 = direct ? HostIo::now_us() : 0.0;
+    if (!forward_device(n, xs, n, out, n * nbins, nullptr)) return false;
+    if (!(r.end == logic::HE_FINISH ? finish(obytes) : finish_mapped(obytes))) return false;
+    if (direct)
     {
-      flag_wanted = true;                                    // a call of one time chunk may signal its own completion
-      pipe_allowed = true;
-      const bool ok = forward_device(n, x, n, dfts, n * nbins, nullptr);
-      flag_wanted = false; pipe_allowed = false;
-      return ok && finish(matrix_bytes(n));
+      // the kernels wrote the plan's pinned pieces: the host copies the matrix out
+      const double t1 = HostIo::now_us();
+      io.copy_bytes(dfts, io.h_pin, obytes);
+      io.pin_us_device += t1 - t0; io.pin_us_memcpy += HostIo::now_us() - t1;
     }
-
-    // small host samples, device matrix (hop-wise streaming from a host signal, sdft_sdft on a device row): through the
-    // pinned scratch, completion by the kernel's word -- the call is complete on return like every host-pointer call
-    if (!xd && od && channels * n * sizeof(TD) <= kIoBytes && opt_pinned_io && ensure_io())
-    {
-      memcpy(h_io, x, channels * n * sizeof(TD));
-      const bool saved = async; async = false;
-      flag_wanted = true;
-      const bool ok = forward_device(n, d_io, n, dfts, n * nbins, nullptr);
-      flag_wanted = false;
-      const bool done = ok && finish(matrix_bytes(n));
-      async = saved;
-      return done;
-    }
-    // host buffers mapped in place (see map_host): the kernels work on the caller's memory
-    {
-      // (a hop's samples are a different slice of the host's signal every call: a few hundred bytes go through the
-      // staging buffer, only buffers beyond 64 KiB are worth a registration)
-      const bool small_x = channels * n * sizeof(TD) <= kSmallHostBytes;
-      fdx* om = od ? dfts : static_cast<fdx*>(map_host(dfts, channels * n * nbins * sizeof(fdx), true));
-      const TD* xm = xd ? x : ((x_class == 0 || small_x) ? nullptr : static_cast<const TD*>(map_host(x, channels * n * sizeof(TD))));
-      if (om && !xm && !xd && small_x)
-      {
-        if (!d_stage_td.reserve(channels * n)) return false;
-        if (!to_device(d_stage_td.p, x, channels * n * sizeof(TD))) return false;
-        xm = d_stage_td.p;
-      }
-      if (xm && om)
-      {
-        const bool ok = forward_device(n, xm, n, om, n * nbins, nullptr);
-        return ok && finish_mapped(matrix_bytes(n));   // host memory: complete on return, through the stream
-      }
-    }
-    // a hop-sized matrix for host memory (the reference driver's 100 x 1000 bins = 1.6 MB, test/test.c:62-83): the kernels
-    // write it into the plan's pinned pieces over PCIe -- no staging matrix, no DMA launch -- and the host copies it out
-    // (scripts/host_hop_paths.py, profiles/r04_host_copy_paths.txt)
-    {
-      const size_t obytes = channels * n * nbins * sizeof(fdx), xbytes = channels * n * sizeof(TD);
-      if (!od && io.opt_host_copy == 0 && io.opt_host_direct && obytes <= HostIo::kDirectBytes && (xd || xbytes <= kSmallHostBytes) && io.ensure_pin())
-      {
-        if (!io.pin_idle()) return copy_failed();
-        const TD* xm = x;
-        if (!xd)
-        {
-          if (xbytes <= kIoBytes && opt_pinned_io && ensure_io()) { memcpy(h_io, x, xbytes); xm = d_io; }
-          else
-          {
-            if (!d_stage_td.reserve(channels * n)) return false;
-            if (!to_device(d_stage_td.p, x, xbytes)) return false;
-            xm = d_stage_td.p;
-          }
-        }
-        ++io.pin_copies;
-        const double t0 = HostIo::now_us();
-        if (!forward_device(n, xm, n, reinterpret_cast<fdx*>(io.d_pin), n * nbins, nullptr)) return false;
-        if (!finish_mapped(matrix_bytes(n))) return false;
-        const double t1 = HostIo::now_us();
-        io.copy_bytes(dfts, io.h_pin, obytes);
-        io.pin_us_device += t1 - t0; io.pin_us_memcpy += HostIo::now_us() - t1;
-        return true;
-      }
-    }
-    // staged path (host pointers): time segments so that the staging matrix stays bounded;
-    // the stream state carries over from segment to segment exactly like hop-wise calls do
-    const size_t row_bytes = channels * nbins * sizeof(fdx);
-    size_t seg = std::max<size_t>(1, stage_bytes / std::max<size_t>(row_bytes, 1));
-    seg = std::min(seg, n);
-    if (!xd && !d_stage_td.reserve(channels * seg)) return false;
-    if (!od && !d_stage_fdx.reserve(channels * seg * nbins)) return false;
-    for (size_t t = 0; t < n; t += seg)
-    {
-      const size_t m = std::min(seg, n - t);
-      const TD* xs; size_t xstride;
-      if (xd) { xs = x + t; xstride = n; }
-      else
-      {
-        if (!copy2d(d_stage_td.p, m * sizeof(TD), x + t, n * sizeof(TD), m * sizeof(TD), hipMemcpyHostToDevice)) return false;
-        xs = d_stage_td.p; xstride = m;
-      }
-      if (od)
-      {
-        if (!forward_device(m, xs, xstride, dfts + t * nbins, n * nbins, nullptr)) return false;
-      }
-      else
-      {
-        if (!forward_device(m, xs, xstride, d_stage_fdx.p, m * nbins, nullptr)) return false;
-        if (!copy2d(dfts + t * nbins, n * nbins * sizeof(fdx), d_stage_fdx.p, m * nbins * sizeof(fdx),
-                    m * nbins * sizeof(fdx), hipMemcpyDeviceToHost)) return false;
-      }
-      if (!xd || !od) SDFT_TRY(hipStreamSynchronize(stream));     // staging buffers are reused
-    }
-    return synchronize();
+    return true;
   }
 
   // decimated analysis (sdft_hip_sdft_every_n): the rows sdft_n would write at the call's samples first, first + every, ...
@@ -140,42 +121,21 @@
     if (xd && od)
     {
       const EveryGrid g{(unsigned long long)every, (unsigned long long)first};
-      if (!forward_device(n, x, n, dfts, rows * nb, nullptr, nullptr, &g)) return false;
-      return finish(rows * row_bytes);
+      return forward_device(n, x, n, dfts, rows * nb, nullptr, nullptr, &g) && finish(rows * row_bytes);
     }
-    // host memory: segments of at most seg samples, each one forward launch on device scratch
+    // host memory: segments of at most seg samples (rows kept and samples within stage_bytes), each one forward launch on device scratch
     size_t seg = n;
-    if (!od) seg = std::min(seg, std::max<size_t>(1, stage_bytes / std::max<size_t>(row_bytes, 1)) * every);
-    if (!xd) seg = std::min(seg, std::max<size_t>((size_t)logic::kHopSamples, stage_bytes / (channels * sizeof(TD))));
-    if (!xd && !d_stage_td.reserve(channels * seg)) return false;
-    if (!od && !d_stage_fdx.reserve(channels * ((seg + every - 1) / every) * nb)) return false;
-    for (size_t t = 0; t < n; t += seg)
-    {
-      const size_t m = std::min(seg, n - t);
-      const size_t f = logic::every_first_from(t, every, first);
-      const size_t r = logic::every_rows(m, every, f);
-      const size_t r0 = r ? (t + f - first) / every : 0;    // the segment's first row in the call's grid
-      const TD* xs; size_t xstride;
-      if (xd) { xs = x + t; xstride = n; }
-      else
-      {
-        if (!copy2d(d_stage_td.p, m * sizeof(TD), x + t, n * sizeof(TD), m * sizeof(TD), hipMemcpyHostToDevice)) return false;
-        xs = d_stage_td.p; xstride = m;
-      }
+    if (!od) seg = std::min(seg, logic::stage_rows(n, row_bytes, stage_bytes) * every);
+    if (!xd) seg = std::min(seg, std::max<size_t>((size_t)logic::kHopSamples, logic::stage_rows(n, channels * sizeof(TD), stage_bytes)));
+    return staged_segments(n, seg, StagedCall{true, const_cast<TD*>(x), !xd, dfts, !od, rows, (seg + every - 1) / every}, [&](Segment& s) {
+      const size_t f = logic::every_first_from(s.t, every, first);
+      s.rows = logic::every_rows(s.m, every, f);
+      s.row0 = s.rows ? (s.t + f - first) / every : 0;       // the segment's first row in the call's grid
+      if (od) s.mat = s.rows ? dfts + s.row0 * nb : nullptr;
+      else s.mat_stride = s.rows * nb;
       const EveryGrid g{(unsigned long long)every, (unsigned long long)f};
-      if (od)
-      {
-        if (!forward_device(m, xs, xstride, r ? dfts + r0 * nb : nullptr, rows * nb, nullptr, nullptr, &g)) return false;
-      }
-      else
-      {
-        if (!forward_device(m, xs, xstride, d_stage_fdx.p, r * nb, nullptr, nullptr, &g)) return false;
-        if (r && !copy2d(dfts + r0 * nb, rows * nb * sizeof(fdx), d_stage_fdx.p, r * nb * sizeof(fdx), r * nb * sizeof(fdx), hipMemcpyDeviceToHost))
-          return false;
-      }
-      SDFT_TRY(hipStreamSynchronize(stream));                // scratch buffers are reused; host memory is complete on return
-    }
-    return synchronize();
+      return forward_device(s.m, s.td, s.td_stride, s.mat, s.mat_stride, nullptr, nullptr, &g);
+    });
   }
 
   // array-of-row-pointers variant (sdft.h:622-628).  Single-channel plans only: the reference's
@@ -186,49 +146,46 @@
     set_error(fn, "row-pointer variants take single-channel plans only (use sdft_sdft_n / sdft_isdft_n with a batched plan)");
     return false;
   }
+  // a host table of device rows goes to the device; nullptr: failed
+  fdx* const* device_table(fdx* const* dfts, size_t n, bool table_on_device)
+  {
+    if (table_on_device) return dfts;
+    if (!d_rowptr.reserve(n) || !to_device(d_rowptr.p, dfts, n * sizeof(fdx*))) return nullptr;
+    return d_rowptr.p;
+  }
   bool sdft_nd(size_t n, const TD* x, fdx** dfts)
   {
     if (n == 0 || nbins == 0) return true;
     if (!single_channel("sdft_sdft_nd")) return false;
     if (!bind()) return false;
     const bool table_on_device = is_device_pointer(dfts);
-    bool rows_on_device = false;
-    std::vector<fdx*> host_rows;
-    if (!table_on_device) { rows_on_device = is_device_pointer(dfts[0]); }
-    if (table_on_device || rows_on_device)
+    if (table_on_device || is_device_pointer(dfts[0]))
     {
       // rows live on the device: hand the pointer table to the kernel
-      fdx* const* table = dfts;
-      if (!table_on_device)
-      {
-        if (!d_rowptr.reserve(n)) return false;
-        if (!to_device(d_rowptr.p, dfts, n * sizeof(fdx*))) return false;
-        table = d_rowptr.p;
-      }
-      const TD* xs = x;
-      if (!is_device_pointer(x))
-      {
-        if (!d_stage_td.reserve(n)) return false;
-        if (!to_device(d_stage_td.p, x, n * sizeof(TD))) return false;
-        xs = d_stage_td.p;
-      }
-      return forward_device(n, xs, n, nullptr, 0, table) && synchronize();
+      fdx* const* table = device_table(dfts, n, table_on_device);
+      if (!table) return false;
+      const TD* xs = is_device_pointer(x) ? x : staged_samples(x, n);
+      return xs && forward_device(n, xs, n, nullptr, 0, table) && synchronize();
     }
     // host rows: compute dense segments, scatter row by row
-    const size_t seg = std::min(n, std::max<size_t>(1, stage_bytes / std::max<size_t>(nbins * sizeof(fdx), 1)));
+    const size_t seg = logic::stage_rows(n, nbins * sizeof(fdx), stage_bytes);
     std::vector<fdx> host(seg * nbins);
+    Scoped<bool> sync(async, false);
     for (size_t t = 0; t < n; t += seg)
     {
       const size_t m = std::min(seg, n - t);
-      const bool saved = async; async = false;
-      const bool ok = sdft_n(m, x + t, host.data());
-      async = saved;
-      if (!ok) return false;
+      if (!sdft_n(m, x + t, host.data())) return false;
       for (size_t r = 0; r < m; ++r) memcpy(dfts[t + r], host.data() + r * nbins, nbins * sizeof(fdx));
     }
     return true;
   }
 
+  // empty spectrum: the reference returns (td)(0 * 2)
+  bool zero_samples(size_t n, TD* y, bool yd)
+  {
+    if (yd) SDFT_TRY(hipMemsetAsync(y, 0, channels * n * sizeof(TD), stream)); else memset(y, 0, channels * n * sizeof(TD));
+    return finish();
+  }
   // y_class: -1 = classify y, 0 = y is host memory whatever option "pointers" says (the by-value result of sdft_isdft)
   bool isdft_n(size_t n, const fdx* dfts, TD* y, int y_class = -1)
   {
@@ -237,97 +194,36 @@
     if (!bind()) return false;
     const bool id = on_device(dfts);
     const bool yd = y_class < 0 ? on_device(y) : y_class != 0;
-    if (nbins == 0)
+    if (nbins == 0) return zero_samples(n, y, yd);
+    TD* y_map = nullptr; fdx* i_map = nullptr;
+    const logic::HostRoute r = host_route(false, n, y, yd, y_class == 0, dfts, id, y_map, i_map);
+    if (r.refused) return copy_failed();
+    if (r.route == logic::HR_STAGED)
+      return staged_segments(n, r.seg, StagedCall{false, y, !yd, const_cast<fdx*>(dfts), !id, n, r.seg},
+                             [&](Segment& s) { return inverse_device(s.m, s.mat, s.mat_stride, nullptr, s.td, s.td_stride); });
+    const size_t ibytes = matrix_bytes(n), ybytes = channels * n * sizeof(TD);
+    const bool direct = r.route == logic::HR_DIRECT;
+    double t1 = 0.0;
+    if (direct)
     {
-      // empty spectrum: the reference returns (td)(0 * 2)
-      if (yd) SDFT_TRY(hipMemsetAsync(y, 0, channels * n * sizeof(TD), stream)); else memset(y, 0, channels * n * sizeof(TD));
-      return finish();
+      // the host copies the matrix into the plan's pinned pieces, which the kernel reads over PCIe
+      const double t0 = HostIo::now_us();
+      io.copy_bytes(io.h_pin, dfts, ibytes);
+      t1 = HostIo::now_us();
+      io.pin_us_memcpy += t1 - t0;
+      ++io.pin_copies;
     }
-    if (id && yd)
-    {
-      flag_wanted = true;
-      pipe_allowed = true;
-      const bool ok = inverse_device(n, dfts, n * nbins, nullptr, y, n);
-      flag_wanted = false; pipe_allowed = false;
-      return ok && finish(matrix_bytes(n));
-    }
-    // device matrix, small host output: the kernel writes the samples into the pinned scratch
-    if (id && !yd && channels * n * sizeof(TD) <= kIoBytes && opt_pinned_io && ensure_io())
-    {
-      const bool saved = async; async = false;
-      flag_wanted = true;
-      const bool ok = inverse_device(n, dfts, n * nbins, nullptr, d_io, n);
-      flag_wanted = false;
-      const bool done = ok && finish(matrix_bytes(n));
-      async = saved;
-      if (done) memcpy(y, h_io, channels * n * sizeof(TD));
-      return done;
-    }
-    {
-      const bool small_y = channels * n * sizeof(TD) <= kSmallHostBytes;
-      const fdx* im = id ? dfts : static_cast<const fdx*>(map_host(dfts, channels * n * nbins * sizeof(fdx)));
-      TD* ym = yd ? y : (small_y ? nullptr : static_cast<TD*>(map_host(y, channels * n * sizeof(TD), true)));
-      if (im && !ym && !yd && small_y) { if (!d_stage_td.reserve(channels * n)) return false; ym = d_stage_td.p; }
-      if (im && ym)
-      {
-        bool ok = inverse_device(n, im, n * nbins, nullptr, ym, n);
-        if (ok && ym == d_stage_td.p && !yd)
-        {
-          ok = to_host(y, ym, channels * n * sizeof(TD));
-        }
-        return ok && finish_mapped(matrix_bytes(n));
-      }
-    }
-    // a hop-sized matrix in host memory: copied into the plan's pinned pieces, which the kernel reads over PCIe
-    {
-      const size_t ibytes = channels * n * nbins * sizeof(fdx), ybytes = channels * n * sizeof(TD);
-      if (!id && io.opt_host_copy == 0 && io.opt_host_direct && ibytes <= HostIo::kDirectBytes && (yd || ybytes <= kSmallHostBytes) && io.ensure_pin())
-      {
-        if (!io.pin_idle()) return copy_failed();
-        const double t0 = HostIo::now_us();
-        io.copy_bytes(io.h_pin, dfts, ibytes);
-        const double t1 = HostIo::now_us();
-        io.pin_us_memcpy += t1 - t0;
-        ++io.pin_copies;
-        TD* ym = y;
-        const bool through_io = !yd && ybytes <= kIoBytes && opt_pinned_io && ensure_io();
-        if (!yd) { if (through_io) ym = d_io; else { if (!d_stage_td.reserve(channels * n)) return false; ym = d_stage_td.p; } }
-        if (!inverse_device(n, reinterpret_cast<const fdx*>(io.d_pin), n * nbins, nullptr, ym, n)) return false;
-        if (!yd && !through_io && !to_host(y, ym, ybytes)) return false;
-        if (!finish_mapped(matrix_bytes(n))) return false;
-        io.pin_us_device += HostIo::now_us() - t1;
-        if (through_io) memcpy(y, h_io, ybytes);
-        return true;
-      }
-    }
-    const size_t row_bytes = channels * nbins * sizeof(fdx);
-    size_t seg = std::max<size_t>(1, stage_bytes / std::max<size_t>(row_bytes, 1));
-    seg = std::min(seg, n);
-    if (!id && !d_stage_fdx.reserve(channels * seg * nbins)) return false;
-    if (!yd && !d_stage_td.reserve(channels * seg)) return false;
-    for (size_t t = 0; t < n; t += seg)
-    {
-      const size_t m = std::min(seg, n - t);
-      const fdx* in; size_t istride;
-      if (id) { in = dfts + t * nbins; istride = n * nbins; }
-      else
-      {
-        if (!copy2d(d_stage_fdx.p, m * nbins * sizeof(fdx), dfts + t * nbins, n * nbins * sizeof(fdx),
-                    m * nbins * sizeof(fdx), hipMemcpyHostToDevice)) return false;
-        in = d_stage_fdx.p; istride = m * nbins;
-      }
-      if (yd)
-      {
-        if (!inverse_device(m, in, istride, nullptr, y + t, n)) return false;
-      }
-      else
-      {
-        if (!inverse_device(m, in, istride, nullptr, d_stage_td.p, m)) return false;
-        if (!copy2d(y + t, n * sizeof(TD), d_stage_td.p, m * sizeof(TD), m * sizeof(TD), hipMemcpyDeviceToHost)) return false;
-      }
-      SDFT_TRY(hipStreamSynchronize(stream));
-    }
-    return synchronize();
+    // (the route has asked ensure_io already, before the copy above: it allocates on a plan's first such call only)
+    TD* ys = r.samples == logic::HS_MAPPED ? y_map : r.samples == logic::HS_IO ? d_io : y;
+    if (r.samples == logic::HS_STAGE_TD) { if (!d_stage_td.reserve(channels * n)) return false; ys = d_stage_td.p; }
+    const fdx* in = direct ? reinterpret_cast<const fdx*>(io.d_pin) : (id ? dfts : i_map);
+    Scoped<bool> sync(async, async && !r.synchronous), flag(flag_wanted, r.flag_wanted), pipe(pipe_allowed, r.pipe_allowed);   // (as in sdft_n)
+    if (!inverse_device(n, in, n * nbins, nullptr, ys, n)) return false;
+    if (r.samples == logic::HS_STAGE_TD && !to_host(y, ys, ybytes)) return false;
+    if (!(r.end == logic::HE_FINISH ? finish(ibytes) : finish_mapped(ibytes))) return false;
+    if (direct) io.pin_us_device += HostIo::now_us() - t1;
+    if (r.samples == logic::HS_IO) memcpy(y, h_io, ybytes);   // the kernel wrote the samples into the pinned scratch
+    return true;
   }
 
   bool isdft_nd(size_t n, const fdx** dfts, TD* y)
@@ -337,16 +233,10 @@
     if (!bind()) return false;
     if (nbins == 0) return isdft_n(n, nullptr, y);
     const bool table_on_device = is_device_pointer(dfts);
-    const bool rows_on_device = table_on_device || is_device_pointer(dfts[0]);
-    if (rows_on_device)
+    if (table_on_device || is_device_pointer(dfts[0]))
     {
-      const fdx* const* table = dfts;
-      if (!table_on_device)
-      {
-        if (!d_rowptr.reserve(n)) return false;
-        if (!to_device(d_rowptr.p, dfts, n * sizeof(fdx*))) return false;
-        table = d_rowptr.p;
-      }
+      const fdx* const* table = device_table(const_cast<fdx* const*>(dfts), n, table_on_device);
+      if (!table) return false;
       TD* yy = y;
       const bool yd = is_device_pointer(y);
       if (!yd) { if (!d_stage_td.reserve(n)) return false; yy = d_stage_td.p; }
@@ -354,16 +244,14 @@
       if (!yd && !to_host(y, yy, n * sizeof(TD))) return false;
       return synchronize();
     }
-    const size_t seg = std::min(n, std::max<size_t>(1, stage_bytes / std::max<size_t>(nbins * sizeof(fdx), 1)));
+    const size_t seg = logic::stage_rows(n, nbins * sizeof(fdx), stage_bytes);
     std::vector<fdx> host(seg * nbins);
+    Scoped<bool> sync(async, false);
     for (size_t t = 0; t < n; t += seg)
     {
       const size_t m = std::min(seg, n - t);
       for (size_t r = 0; r < m; ++r) memcpy(host.data() + r * nbins, dfts[t + r], nbins * sizeof(fdx));
-      const bool saved = async; async = false;
-      const bool ok = isdft_n(m, host.data(), y + t);
-      async = saved;
-      if (!ok) return false;
+      if (!isdft_n(m, host.data(), y + t)) return false;
     }
     return true;
   }
@@ -375,10 +263,8 @@
     if (nbins == 0) { *y = (TD)0; return true; }           // the reference returns (td)(0 * 2)
     if (opt_resident && resident_synthesis_sample(dft, y)) return true;
     if (!bind()) return false;
-    const bool saved = async; async = false;
-    const bool ok = isdft_n(1, dft, y, 0);                   // (a device row: through the pinned scratch, see isdft_n; y lives on the host stack)
-    async = saved;
-    return ok;
+    Scoped<bool> sync(async, false);
+    return isdft_n(1, dft, y, 0);                            // (a device row: through the pinned scratch, see isdft_n; y lives on the host stack)
   }
 
   // ---- fused analysis -> spectral operation -> synthesis (SURVEY.md 8 f2) ------------------------
@@ -387,32 +273,21 @@
   // params: OP_GAIN -> FD gains[N], OP_CGAIN -> cx<FD> gains[N] (host or device memory), OP_SHIFT -> const long* (host).
   DevBuf<FD> d_gain;
   DevBuf<TD> d_stage_y;
-  bool fuse_ok() const { return rows_kernel_ok(false); }
-  // fused call: bins summed in the reference's order?  (-1: exactly when the host asked for exact carries at FD double)
-  bool wants_reference_order() const
-  {
-    return opt_fused_exact < 0 ? (carry_mode == CARRY_EXACT && sizeof(FD) == 8) : opt_fused_exact != 0;
-  }
+  bool wants_reference_order() const { return logic::reference_order(opt_fused_exact, carry_mode == CARRY_EXACT, sizeof(FD)); }
 
-  bool process_n(size_t n, const TD* x, TD* y, int op_kind, const void* params, fdx* dfts)
+  // the call's operation: public operation numbers (enum sdft_hip_op: 0 identity, 1 gain, 2 shift, 3 cgain, 4 gain_rows, 5 cgain_rows,
+  // 6 gate, 7 power, 8 expression) to the kernels' SpectralOp, parameters checked, gains on the device.  build == false (an
+  // empty spectrum has no operation): only the checks that do not depend on the spectrum.
+  bool process_op(int op_public, const void* params, const fdx* dfts, bool build, SpectralOp<FD>& op)
   {
-    if (n == 0) return true;
-    if (!bind()) return false;
-    // public operation numbers (enum sdft_hip_op): 0 identity, 1 gain, 2 shift, 3 cgain, 4 gain_rows, 5 cgain_rows, 6 gate, 7 power,
-    // 8 expression
-    const int op_public = op_kind;
-    if (op_public < 0 || op_public > 8) { set_error("sdft_hip_process_n", "unknown operation"); return false; }
-    if ((op_public != 0) && !params) { set_error("sdft_hip_process_n", "the operation needs parameters"); return false; }
-    op_kind = op_public == 4 ? OP_GAIN : op_public == 5 ? OP_CGAIN : op_public == 6 ? OP_GATE : op_public == 7 ? OP_POWER : op_public == 8 ? OP_USER : op_public;
-    if (op_kind == OP_SHIFT && dfts) { set_error("sdft_hip_process_n", "a copy of the spectrum is not available with the shift operation"); return false; }
-    const bool yd = on_device(y);
-    if (nbins == 0)
-    {
-      if (yd) SDFT_TRY(hipMemsetAsync(y, 0, channels * n * sizeof(TD), stream)); else memset(y, 0, channels * n * sizeof(TD));
-      return finish();
-    }
-    if (dfts && !on_device(dfts)) { set_error("sdft_hip_process_n", "dfts must be device memory (or NULL)"); return false; }
-    SpectralOp<FD> op{}; op.kind = op_kind; op.gain = nullptr; op.shift = 0; op.rows = 1; op.hop = 0; op.t0 = 0;
+    static const char* fn = "sdft_hip_process_n";
+    if (op_public < 0 || op_public > 8) { set_error(fn, "unknown operation"); return false; }
+    if ((op_public != 0) && !params) { set_error(fn, "the operation needs parameters"); return false; }
+    const int op_kind = op_public == 4 ? OP_GAIN : op_public == 5 ? OP_CGAIN : op_public == 6 ? OP_GATE : op_public == 7 ? OP_POWER : op_public == 8 ? OP_USER : op_public;
+    if (op_kind == OP_SHIFT && dfts) { set_error(fn, "a copy of the spectrum is not available with the shift operation"); return false; }
+    if (!build) return true;
+    if (dfts && !on_device(dfts)) { set_error(fn, "dfts must be device memory (or NULL)"); return false; }
+    op.kind = op_kind; op.gain = nullptr; op.shift = 0; op.rows = 1; op.hop = 0; op.t0 = 0;
     if (op_kind == OP_GAIN || op_kind == OP_CGAIN)
     {
       const FD* g = static_cast<const FD*>(params);
@@ -422,8 +297,8 @@
         // time-varying gains: { gains, rows, hop } (sdft_hip_gain_rows_t)
         struct table_t { const void* gains; size_t rows, hop; };
         const table_t* tb = static_cast<const table_t*>(params);
-        if (!tb->gains || tb->rows == 0 || (tb->rows > 1 && tb->hop == 0)) { set_error("sdft_hip_process_n", "gain table: gains, rows >= 1 and hop >= 1 are required"); return false; }
-        if (tb->rows > 0xffffffffull) { set_error("sdft_hip_process_n", "gain table: too many rows"); return false; }
+        if (!tb->gains || tb->rows == 0 || (tb->rows > 1 && tb->hop == 0)) { set_error(fn, "gain table: gains, rows >= 1 and hop >= 1 are required"); return false; }
+        if (tb->rows > 0xffffffffull) { set_error(fn, "gain table: too many rows"); return false; }
         g = static_cast<const FD*>(tb->gains); rows = tb->rows; op.rows = (unsigned)rows; op.hop = tb->hop;
       }
       const size_t per_bin = op_kind == OP_CGAIN ? 2 : 1;          // real factors, or (re, im) pairs
@@ -442,13 +317,12 @@
       // { expr, p, np }: the parameters travel to the device with the call (host memory; np may be 0)
       struct expr_t { const char* expr; const void* p; size_t np; };
       const expr_t* ex = static_cast<const expr_t*>(params);
-      if (!ex->expr || !*ex->expr) { set_error("sdft_hip_process_n", "expression: no statements"); return false; }
+      if (!ex->expr || !*ex->expr) { set_error(fn, "expression: no statements"); return false; }
       user_expr = ex->expr;
       if (ex->np <= 8)
       {
         // up to eight parameters ride in the kernel arguments (SpectralOp::pv)
         for (size_t i = 0; i < ex->np; ++i) op.pv[i] = static_cast<const FD*>(ex->p)[i];
-        op.gain = nullptr;
       }
       else
       {
@@ -457,18 +331,21 @@
         op.gain = d_gain.p;
       }
     }
-    const bool linear = op_is_linear<FD>(op_kind);
-    const bool one_vector = op.rows <= 1;
+    return true;
+  }
 
-    // samples: device pointers as they are, host pointers staged (4 bytes per sample each way)
+  bool process_n(size_t n, const TD* x, TD* y, int op_kind, const void* params, fdx* dfts)
+  {
+    if (n == 0) return true;
+    if (!bind()) return false;
+    SpectralOp<FD> op{};
+    if (nbins == 0) return process_op(op_kind, params, dfts, false, op) && zero_samples(n, y, on_device(y));
+    if (!process_op(op_kind, params, dfts, true, op)) return false;
+    const bool yd = on_device(y);
+    // the samples: device pointers as they are, host pointers staged (4 bytes per sample each way)
     const bool xd = on_device(x);
     const TD* xs = x;
-    if (!xd)
-    {
-      if (!d_stage_td.reserve(channels * n)) return false;
-      if (!to_device(d_stage_td.p, x, channels * n * sizeof(TD))) return false;
-      xs = d_stage_td.p;
-    }
+    if (!xd && !(xs = staged_samples(x, channels * n))) return false;
     TD* ys = y;
     if (!yd) { if (!d_stage_y.reserve(channels * n)) return false; ys = d_stage_y.p; }
     // In place (out == samples) or overlapping device buffers: the two reference calls read every sample before the first
@@ -484,107 +361,74 @@
         xs = d_stage_td.p;
       }
     }
-
-    bool ok;
-    const long chunks = logic::choose_chunks(chunk_query(n, rows_kernel_ok(false))).chunks;
-    // reference order asked for on two-slot rows at FD float: the ordered walk (N dependent additions shared
-    // by the four samples of a group) costs more than the synthesis pass it saves (N = 4096, n = 262144:
-    // 5.7 ms against 4.1 ms for the two passes, which give the same bits); fused_exact = 2 insists on the kernel
-    const bool walk_loses = row_slots() == 2 && sizeof(FD) == 4 && carry_mode == CARRY_EXACT && opt_fused_exact == 1;
-    // calls of one time chunk: the folded form in one launch (process_hop2_kernel) unless the reference's order
-    // is wanted -- then the hop kernel + row synthesis pair below, which is bit-identical
-    const bool one_chunk_folded = chunks == 1 && n <= (size_t)kHopMax && !wants_reference_order() && !dfts && opt_fold && nbins >= 8 && opt_hop_kernel &&
-                                  linear && one_vector;
-    if (one_chunk_folded)
+    // the route: every input is a quantity of the plan or an option, but for the device's free memory
+    logic::ProcessQuery q;
+    q.chunk = chunk_query(n, rows_kernel_ok(false)); q.fd_bytes = sizeof(FD); q.fdx_bytes = sizeof(fdx);
+    q.linear = op_is_linear<FD>(op.kind); q.user = op.kind == OP_USER; q.gain_rows = op.rows;
+    q.spectrum = dfts != nullptr; q.x_device = xd; q.y_device = yd;
+    q.fused_exact = opt_fused_exact; q.fold = opt_fold; q.hop_kernel = opt_hop_kernel;
+    q.exact_inverse = opt_exact_inverse; q.inverse_rows = opt_inverse_rows;
+    q.stage_bytes = stage_bytes; q.workspace = d_stage_fdx.cap;
+    const logic::ProcessRoute r = logic::process_route(q, [] {
+      size_t free_b = 0, total_b = 0;
+      const bool known = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+      (void)hipGetLastError();
+      return known ? free_b : (size_t)0;
+    });
     {
-      if (!fold_coefficients(op)) return false;
-      last_process_path = 1;
-      flag_wanted = xd && yd;
-      ok = coeff_ready && process_hop(n, xs, n, ys, n);
-      flag_wanted = false;
-    }
-    // the folded form carries up to four bins per lane whatever the bin type is (N <= 4096); the forms that keep the
-    // windowed rows in LDS stop at two slots of the row-group kernel (N <= 2048 double / 4096 float)
-    else if ((fuse_ok() || (linear && op.rows <= 65535u && !wants_reference_order() && !dfts && opt_fold && nbins >= 8 && nbins <= (size_t)4 * kWave * kRowWavesMax))
-             && (chunks > 1 || n > (size_t)kHopMax) && !walk_loses)       // (many channels: one chunk per channel, however long)
-    {
-      FuseArgs<TD, FD> fz{};
-      fz.y = ys; fz.y_stride = n; fz.syn = d_syn.p; fz.sweight = tab.sweight; fz.op = op; fz.store = dfts ? 1 : 0;
-      fz.walked = walked_counter();
-      if (!dfts) { if (!fold_coefficients(op)) return false; } else coeff_ready = false;
-      last_process_path = 1;
-      flag_wanted = xd && yd;
-      ok = forward_device(n, xs, n, dfts, n * nbins, nullptr, &fz);
-      flag_wanted = false;
-    }
-    else
-    {
-      // short calls (one time chunk: the hop kernel and the row-per-wave synthesis, two launches) and
-      // shapes the row-group kernel does not cover: analysis into the caller's matrix or a bounded
-      // workspace, synthesis with the operation applied on the way in
-      const size_t row_elems = channels * nbins;
-      size_t seg = dfts ? n : std::min(n, std::max<size_t>(1, stage_bytes / std::max<size_t>(row_elems * sizeof(fdx), 1)));
-      if (!dfts && seg < n && stage_bytes == kDefaultStageBytes)
+      Scoped<bool> flag(flag_wanted, r.flag_wanted);         // (read by the launches only: arm_flag, hop_parts -- not by fold_coefficients)
+      if (r.path == logic::PP_HOP_FOLDED)
       {
-        // long calls run best in one piece (time segments restart the carry pipeline): unless the host
-        // has bounded it (option stage_bytes), the workspace may take up to half of what the device has free
-        if (d_stage_fdx.cap >= row_elems * n) seg = n;
-        else
-        {
-          size_t free_b = 0, total_b = 0;
-          if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-            seg = std::max(seg, std::min(n, (free_b / 2) / std::max<size_t>(row_elems * sizeof(fdx), 1)));
-          (void)hipGetLastError();
-        }
+        if (!fold_coefficients(op)) return false;
+        last_process_path = 1;
+        if (!coeff_ready || !process_hop(n, xs, n, ys, n)) return false;
       }
-      // (batched plans take segments too: the workspace's channel stride is the segment, mstride below)
-      if (!dfts && !d_stage_fdx.reserve(row_elems * seg)) return false;
-      last_process_path = (chunks == 1) ? 2 : 3;
-      last_fused_exact = 0; last_fused_fold = 0;
-      if (op_kind == OP_USER)
+      else if (r.path == logic::PP_FUSED_ROWS)
       {
+        FuseArgs<TD, FD> fz{};
+        fz.y = ys; fz.y_stride = n; fz.syn = d_syn.p; fz.sweight = tab.sweight; fz.op = op; fz.store = dfts ? 1 : 0;
+        fz.walked = walked_counter();
+        if (r.fold) { if (!fold_coefficients(op)) return false; } else coeff_ready = false;
+        last_process_path = 1;
+        if (!forward_device(n, xs, n, dfts, n * nbins, nullptr, &fz)) return false;
+      }
+      else
+      {
+        // two passes in segments of r.seg rows: analysis, then synthesis with the operation applied on the way in
+        // (batched plans take segments too: the workspace's channel stride is the segment, mstride below)
+        if (!dfts && !d_stage_fdx.reserve(channels * nbins * r.seg)) return false;
+        last_process_path = r.path;                            // PP_HOP_PAIR = 2, PP_SEGMENTS = 3
+        last_fused_exact = 0; last_fused_fold = 0;
         // every run-time-compiled kernel the segments below will ask for is resolved BEFORE the first launch: statements
         // that do not compile must not leave the stream advanced by an analysis whose synthesis then fails
-        const size_t m_first = std::min(seg, n), m_last = n - ((n - 1) / seg) * seg;
-        const bool hop_form = opt_exact_inverse && opt_inverse_rows <= 0;
-        const bool any_hop = hop_form && (channels * m_first <= 1024 || channels * m_last <= 1024);
-        const bool any_rows = !hop_form || channels * m_first > 1024 || channels * m_last > 1024 || dfts != nullptr;
-        hipFunction_t fn = nullptr;
-        char name[160];
-        if (any_hop)
+        if (r.rtc_hop || r.rtc_rows)
         {
-          snprintf(name, sizeof(name), "sdfthip::inverse_row_kernel<%s, %s, %s, true>", type_name<TD>(), type_name<FD>(), latency == 1 ? "true" : "false");
-          if (!rtc_kernel(user_expr.c_str(), name, device, &fn)) return false;
+          hipFunction_t fn = nullptr;
+          char hop_name[160], rows_name[96];
+          snprintf(hop_name, sizeof(hop_name), "sdfthip::inverse_row_kernel<%s, %s, %s, true>", type_name<TD>(), type_name<FD>(), latency == 1 ? "true" : "false");
+          snprintf(rows_name, sizeof(rows_name), "sdfthip::user_rows_kernel<%s>", type_name<FD>());
+          if (r.rtc_hop && !rtc_kernel(user_expr.c_str(), hop_name, device, &fn)) return false;
+          if (r.rtc_rows && !rtc_kernel(user_expr.c_str(), rows_name, device, &fn)) return false;
         }
-        if (any_rows)
+        const bool user = op.kind == OP_USER, user_hop_form = user && opt_exact_inverse && opt_inverse_rows <= 0;
+        for (size_t t = 0; t < n; t += r.seg)
         {
-          snprintf(name, sizeof(name), "sdfthip::user_rows_kernel<%s>", type_name<FD>());
-          if (!rtc_kernel(user_expr.c_str(), name, device, &fn)) return false;
-        }
-      }
-      ok = true;
-      for (size_t t = 0; t < n && ok; t += seg)
-      {
-        const size_t m = std::min(seg, n - t);
-        fdx* mat = dfts ? dfts + t * nbins : d_stage_fdx.p;
-        const size_t mstride = dfts ? n * nbins : m * nbins;
-        SpectralOp<FD> ops = op; ops.t0 = t;                  // gain vectors count from the start of the call
-        if (op_kind == OP_USER && opt_exact_inverse && opt_inverse_rows <= 0 && channels * m <= 1024)
-        {
-          // a hop: the statements run inside the row synthesis (two launches); a copy of the spectrum is processed afterwards
-          ok = forward_device(m, xs + t, n, mat, mstride, nullptr) && inverse_device(m, mat, mstride, nullptr, ys + t, n, &ops);
-          if (ok && dfts) ok = user_rows(mat, mstride, m, ops);
-        }
-        else if (op_kind == OP_USER)                          // the host's operation rewrites the rows in place, then plain synthesis
-          ok = forward_device(m, xs + t, n, mat, mstride, nullptr) && user_rows(mat, mstride, m, ops) && inverse_device(m, mat, mstride, nullptr, ys + t, n, nullptr);
-        else
-        {
-        ok = forward_device(m, xs + t, n, mat, mstride, nullptr) && inverse_device(m, mat, mstride, nullptr, ys + t, n, &ops);
-        if (ok && (op_kind == OP_GAIN || op_kind == OP_CGAIN || op_kind >= OP_GATE) && dfts) ok = scale_rows(mat, mstride, m, ops);
+          const size_t m = std::min(r.seg, n - t);
+          fdx* mat = dfts ? dfts + t * nbins : d_stage_fdx.p;
+          const size_t mstride = dfts ? n * nbins : m * nbins;
+          SpectralOp<FD> ops = op; ops.t0 = t;                  // gain vectors count from the start of the call
+          // the operation runs inside the synthesis -- the host's own statements only on a hop (row synthesis, two launches):
+          // on longer segments they rewrite the stored rows in place first, then plain synthesis
+          const bool in_synthesis = !user || (user_hop_form && channels * m <= 1024);
+          if (!forward_device(m, xs + t, n, mat, mstride, nullptr)) return false;
+          if (!in_synthesis && !user_rows(mat, mstride, m, ops)) return false;
+          if (!inverse_device(m, mat, mstride, nullptr, ys + t, n, in_synthesis ? &ops : nullptr)) return false;
+          // a copy of the spectrum is processed afterwards
+          if (in_synthesis && dfts && user && !user_rows(mat, mstride, m, ops)) return false;
+          if (in_synthesis && dfts && (op.kind == OP_GAIN || op.kind == OP_CGAIN || (op.kind >= OP_GATE && !user)) && !scale_rows(mat, mstride, m, ops)) return false;
         }
       }
     }
-    if (!ok) return false;
     if (!yd)
     {
       if (!to_host(y, ys, channels * n * sizeof(TD))) return false;

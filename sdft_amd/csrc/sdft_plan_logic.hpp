@@ -1,9 +1,10 @@
 // sdft_plan_logic.hpp -- the host-side DECISIONS of the engine, free of any HIP dependency: launch geometry (lanes, tiles,
 // row slots), time chunking, the block length of the exact-carry relay, which calls leave the plan's stream (call pattern,
-// row-stream ring, address-range overlap), time parts of a hop, rows per wave of the synthesis, the route of an analysis call
-// (forward_route) and the form of a synthesis call (inverse_route), the wait of a synchronous call, and the slot ring of the
-// host-copy engine.  sdft_plan.hpp (Plan<TD, FD>) builds the queries, asks these functions and does the HIP calls (a check that
-// needs one -- an allocation, the occupancy API -- is a callable the route asks only where it needs the answer);
+// row-stream ring, address-range overlap), time parts of a hop, rows per wave of the synthesis, the routes of an analysis call
+// (forward_route), a synthesis call (inverse_route), host memory through the entry points (host_route) and the fused call
+// (process_route), the wait of a synchronous call, and the slot ring of the host-copy engine.  sdft_plan.hpp (Plan<TD, FD>) builds
+// the queries, asks these functions and does the HIP calls (a check that needs one -- an allocation, the occupancy API -- is a
+// callable the route asks only where it needs the answer);
 // tests/cpp/plan_logic_test.cpp compiles this header alone with g++ -fsanitize=address,undefined (and the ring under
 // -fsanitize=thread) in the `-m "not gpu"` suite (sanitizers on the host side).
 // Citations are into /root/reference/c/src/sdft/sdft.h.
@@ -847,6 +848,161 @@ inline size_t stage_rows(size_t n, size_t row_bytes, size_t stage_bytes)
 {
   const size_t seg = std::max<size_t>(1, stage_bytes / std::max<size_t>(row_bytes, 1));
   return std::min(seg, std::max<size_t>(n, 1));
+}
+
+// ---- host memory: the route of an analysis or a synthesis call (Plan::sdft_n / isdft_n run it) -----------------------------
+// A call has a SAMPLES side ([channels][n] of TD: what the analysis reads and the synthesis writes) and a MATRIX side
+// ([channels][n][N] bins: what the analysis writes and the synthesis reads); either may be the caller's host memory.
+constexpr size_t kSmallHostBytes = (size_t)64 << 10;       // the plan's pinned scratch (h_io / d_io): host samples up to this size travel through it
+constexpr size_t kDirectBytes = (size_t)4 << 20;           // a hop-sized matrix the kernels write / read in the pinned pieces themselves (both)
+constexpr size_t kDefaultStageBytes = (size_t)1 << 30;     // option "stage_bytes": the staging segment of host-pointer calls
+enum HostRouteKind : int { HR_DEVICE = 0, HR_SCRATCH = 1, HR_MAPPED = 2, HR_DIRECT = 3, HR_STAGED = 4 };
+enum HostSamples : int { HS_AS_IS = 0, HS_IO = 1, HS_MAPPED = 2, HS_STAGE_TD = 3 };   // as they are, d_io, registered in place, d_stage_td
+enum HostEnd : int { HE_FINISH = 0, HE_FINISH_MAPPED = 1, HE_SYNCHRONIZE = 2 };
+struct HostQuery
+{
+  bool analysis = true;                                    // else synthesis
+  bool samples_device = false, matrix_device = false;
+  size_t samples_bytes = 0, matrix_bytes = 0;
+  bool by_value = false;                                   // the sample of sdft_sdft / the result of sdft_isdft: host memory of the call's duration
+  long pinned_io = 1, host_copy = 0, host_direct = 1;      // options
+  size_t stage_bytes = kDefaultStageBytes, n = 0, row_bytes = 0;
+};
+struct HostRoute
+{
+  int route = HR_STAGED, samples = HS_AS_IS, end = HE_SYNCHRONIZE;
+  bool flag_wanted = false, pipe_allowed = false, synchronous = false;
+  bool refused = false;                                    // HR_DIRECT: the pinned pieces are busy and could not be drained -- the call fails
+  size_t seg = 0;                                          // HR_STAGED: rows per time segment
+};
+
+// The callables are the checks with side effects, each asked at most once and only where the route needs the answer: Plan::ensure_io,
+// HostIo::map_host of either side (it counts host_register_hits / misses), HostIo::ensure_pin / pin_idle.
+template <class EnsureIo, class MapMatrix, class MapSamples, class EnsurePin, class PinIdle>
+inline HostRoute host_route(const HostQuery& q, EnsureIo&& ensure_io, MapMatrix&& map_matrix, MapSamples&& map_samples,
+                            EnsurePin&& ensure_pin, PinIdle&& pin_idle)
+{
+  HostRoute r;
+  const bool sd = q.samples_device, md = q.matrix_device;
+  // (a hop's samples are a different slice of the host's signal every call: a few hundred bytes go through the scratch or
+  // the staging buffer, only buffers beyond 64 KiB are worth a registration)
+  const bool small = q.samples_bytes <= kSmallHostBytes;
+  if (sd && md)
+  {
+    r.route = HR_DEVICE; r.end = HE_FINISH; r.pipe_allowed = true;
+    r.flag_wanted = true;                                  // a call of one time chunk may signal its own completion
+    return r;
+  }
+  // small host samples, device matrix (hop-wise streaming from or to a host signal, sdft_sdft / sdft_isdft on a device row): the
+  // kernel reads / writes the pinned scratch, completion by the kernel's word -- the call is complete on return like every
+  // host-pointer call (hence synchronous)
+  if (!sd && md && small && q.pinned_io && ensure_io())
+  {
+    r.route = HR_SCRATCH; r.samples = HS_IO; r.end = HE_FINISH; r.flag_wanted = r.synchronous = true;
+    return r;
+  }
+  // host buffers mapped in place (HostIo::map_host): the kernels work on the caller's memory.  The matrix first, and the samples
+  // whatever the matrix said: a matrix that was registered stays registered for the next call
+  const bool matrix_ok = md || map_matrix();
+  // analysis / synthesis: the by-value sample of sdft_sdft is never registered however many channels it has (it lives on the
+  // host's stack); the by-value result of sdft_isdft is a buffer like any other
+  const bool keep_off = q.analysis && q.by_value;
+  const bool samples_mapped = !sd && !small && !keep_off && map_samples();
+  if (matrix_ok && (sd || small || samples_mapped))
+  {
+    r.route = HR_MAPPED; r.samples = sd ? HS_AS_IS : small ? HS_STAGE_TD : HS_MAPPED;       // (small ones: one copy through device scratch)
+    r.end = HE_FINISH_MAPPED;                              // host memory: complete on return, through the stream
+    return r;
+  }
+  // a hop-sized matrix in host memory (the reference driver's 100 x 1000 bins = 1.6 MB, test/test.c:62-83): the kernels write it
+  // into / read it from the plan's pinned pieces over PCIe -- no staging matrix, no DMA launch -- and the host copies it out / in
+  // (scripts/host_hop_paths.py, profiles/r04_host_copy_paths.txt)
+  if (!md && q.host_copy == 0 && q.host_direct && q.matrix_bytes <= kDirectBytes && (sd || small) && ensure_pin())
+  {
+    r.route = HR_DIRECT; r.end = HE_FINISH_MAPPED;
+    if (!pin_idle()) { r.refused = true; return r; }
+    r.samples = sd ? HS_AS_IS : (q.pinned_io && ensure_io()) ? HS_IO : HS_STAGE_TD;
+    return r;
+  }
+  // staged (host pointers): time segments so that the staging matrix stays bounded; the stream state carries over from segment
+  // to segment exactly like hop-wise calls do
+  r.route = HR_STAGED; r.samples = sd ? HS_AS_IS : HS_STAGE_TD; r.end = HE_SYNCHRONIZE;
+  r.seg = stage_rows(q.n, q.row_bytes, q.stage_bytes);
+  return r;
+}
+
+// ---- fused analysis -> operation -> synthesis: the route of a call (Plan::process_n runs it) -----------------------------------
+// fused call: bins summed in the reference's order?  (-1: exactly when the host asked for exact carries at FD double)
+inline bool reference_order(long fused_exact, bool exact, size_t fd_bytes) { return fused_exact < 0 ? (exact && fd_bytes == 8) : fused_exact != 0; }
+struct ProcessQuery
+{
+  ChunkQuery chunk;                                        // of the call; chunk.rows_kernel: the row-group kernel takes the plan's rows
+  size_t fd_bytes = 8, fdx_bytes = 16;
+  bool linear = true, user = false;                        // the operation: linear (identity, gain, shift, complex gain); the host's own statements
+  size_t gain_rows = 1;                                    // gain vectors of a time-varying gain
+  bool spectrum = false;                                   // the caller wants the processed spectrum (dfts)
+  bool x_device = true, y_device = true;
+  long fused_exact = -1, fold = 1, hop_kernel = 1, exact_inverse = 1, inverse_rows = 0;   // options
+  size_t stage_bytes = kDefaultStageBytes;
+  size_t workspace = 0;                                    // bins the plan's staging matrix holds already
+};
+// one launch of the folded hop kernel (process_hop2_kernel); the fused row kernels through forward_device; hop kernel + row
+// synthesis (one time chunk, two launches); analysis and synthesis in time segments through a workspace
+enum ProcessPath : int { PP_HOP_FOLDED = 0, PP_FUSED_ROWS = 1, PP_HOP_PAIR = 2, PP_SEGMENTS = 3 };   // (get_option "last_process_path": 1, 1, 2, 3)
+struct ProcessRoute
+{
+  int path = PP_SEGMENTS;
+  bool fold = false;                                       // the coefficients are folded (Plan::fold_coefficients) before the launch
+  bool flag_wanted = false;
+  size_t seg = 0;                                          // two passes: rows per segment
+  bool rtc_hop = false, rtc_rows = false;                  // the host's statements: inverse_row_kernel / user_rows_kernel resolved up front
+};
+
+// free_bytes(): the device's free memory (0: unknown), asked only where a long call's workspace may outgrow stage_bytes
+template <class FreeBytes>
+inline ProcessRoute process_route(const ProcessQuery& q, FreeBytes&& free_bytes)
+{
+  ProcessRoute r;
+  const size_t n = q.chunk.n, nb = q.chunk.nbins, ch = std::max<size_t>(q.chunk.channels, 1);
+  const long chunks = choose_chunks(q.chunk).chunks;
+  const bool hop = chunks == 1 && n <= (size_t)kHopSamples;
+  const bool foldable = q.linear && !reference_order(q.fused_exact, q.chunk.exact, q.fd_bytes) && !q.spectrum && q.fold && nb >= 8;
+  // reference order asked for on two-slot rows at FD float: the ordered walk (N dependent additions shared
+  // by the four samples of a group) costs more than the synthesis pass it saves (N = 4096, n = 262144:
+  // 5.7 ms against 4.1 ms for the two passes, which give the same bits); fused_exact = 2 insists on the kernel
+  const bool walk_loses = row_slots(nb, q.fdx_bytes) == 2 && q.fd_bytes == 4 && q.chunk.exact && q.fused_exact == 1;
+  r.flag_wanted = q.x_device && q.y_device;
+  // calls of one time chunk: the folded form in one launch unless the reference's order is wanted -- then the hop kernel +
+  // row synthesis pair below, which is bit-identical
+  if (hop && foldable && q.hop_kernel && q.gain_rows <= 1) { r.path = PP_HOP_FOLDED; r.fold = true; return r; }
+  // the folded form carries up to four bins per lane whatever the bin type is (N <= 4096); the forms that keep the
+  // windowed rows in LDS stop at two slots of the row-group kernel (N <= 2048 double / 4096 float)
+  // (many channels: one chunk per channel, however long, is no hop)
+  if ((q.chunk.rows_kernel || (foldable && q.gain_rows <= 65535 && nb <= (size_t)4 * kLanes * kRowWaves)) && !hop && !walk_loses)
+  {
+    r.path = PP_FUSED_ROWS; r.fold = !q.spectrum;
+    return r;
+  }
+  // short calls (one time chunk: the hop kernel and the row-per-wave synthesis, two launches) and shapes the row-group
+  // kernel does not cover: analysis into the caller's matrix or a bounded workspace, synthesis with the operation applied
+  // on the way in
+  r.path = chunks == 1 ? PP_HOP_PAIR : PP_SEGMENTS; r.flag_wanted = false;
+  const size_t row_bytes = ch * nb * q.fdx_bytes;
+  r.seg = q.spectrum ? n : stage_rows(n, row_bytes, q.stage_bytes);
+  // long calls run best in one piece (time segments restart the carry pipeline): unless the host has bounded it (option
+  // stage_bytes), the workspace may take up to half of what the device has free
+  if (!q.spectrum && r.seg < n && q.stage_bytes == kDefaultStageBytes)
+    r.seg = q.workspace >= ch * nb * n ? n : std::max(r.seg, std::min(n, (free_bytes() / 2) / std::max<size_t>(row_bytes, 1)));
+  if (q.user)
+  {
+    // a segment of up to 1024 rows is a hop: the statements run inside the row synthesis; longer ones (and a copy of the
+    // spectrum) take user_rows_kernel.  The first and the last segment are the two lengths there are
+    const size_t m_first = std::min(r.seg, n), m_last = n - ((n - 1) / r.seg) * r.seg;
+    const bool hop_form = q.exact_inverse && q.inverse_rows <= 0;
+    r.rtc_hop = hop_form && (ch * m_first <= 1024 || ch * m_last <= 1024);
+    r.rtc_rows = !hop_form || ch * m_first > 1024 || ch * m_last > 1024 || q.spectrum;
+  }
+  return r;
 }
 
 // ---- host copies through pinned pieces: the slot ring --------------------------------------------------------------------------

@@ -7,6 +7,9 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <algorithm>
+#include <chrono>
+#include <string>
 #include <vector>
 
 using namespace sdfthip::logic;
@@ -529,8 +532,389 @@ static void test_inverse_shapes()
   CHECK(xcd_groups(true, 16) == 16 && xcd_groups(true, 15) == 0 && xcd_groups(false, 100) == 0, "xcd map");
 }
 
-int main()
+// ---- host memory: the route of an analysis / synthesis call (host_route) ------------------------------------------------------
+// what the callables answer, and the order in which they were asked: I ensure_io, M map matrix, S map samples, P ensure_pin, D pin_idle
+struct HostEnv { bool io = true, mat = false, smp = false, pin = true, idle = true; std::string asked; };
+struct HostTaken { int route, samples; bool refused; };
+static HostRoute take(const HostQuery& q, HostEnv& e)
 {
+  return host_route(q, [&] { e.asked += 'I'; return e.io; }, [&] { e.asked += 'M'; return e.mat; }, [&] { e.asked += 'S'; return e.smp; },
+                    [&] { e.asked += 'P'; return e.pin; }, [&] { e.asked += 'D'; return e.idle; });
+}
+// The two ladders of conditions as sdft_n and isdft_n spelled them before host_route replaced both (the scratch and the "small"
+// threshold were two constants of the same value): the models host_route is held against, callable by callable
+static HostTaken ladder_analysis(const HostQuery& q, HostEnv& e)
+{
+  const size_t kIo = (size_t)64 << 10, kSmall = (size_t)64 << 10, kDirect = (size_t)4 << 20;
+  const bool xd = q.samples_device, od = q.matrix_device;
+  const size_t xbytes = q.samples_bytes, obytes = q.matrix_bytes;
+  auto io = [&] { e.asked += 'I'; return e.io; };
+  if (xd && od) return {HR_DEVICE, HS_AS_IS, false};
+  if (!xd && od && xbytes <= kIo && q.pinned_io && io()) return {HR_SCRATCH, HS_IO, false};
+  {
+    const bool small_x = xbytes <= kSmall;
+    const bool om = od ? true : (e.asked += 'M', e.mat);
+    bool xm = xd ? true : ((q.by_value || small_x) ? false : (e.asked += 'S', e.smp));
+    bool staged = false;
+    if (om && !xm && !xd && small_x) { xm = true; staged = true; }
+    if (xm && om) return {HR_MAPPED, xd ? HS_AS_IS : staged ? HS_STAGE_TD : HS_MAPPED, false};
+  }
+  if (!od && q.host_copy == 0 && q.host_direct && obytes <= kDirect && (xd || xbytes <= kSmall) && (e.asked += 'P', e.pin))
+  {
+    if (!(e.asked += 'D', e.idle)) return {HR_DIRECT, HS_AS_IS, true};
+    int xm = HS_AS_IS;
+    if (!xd) xm = (xbytes <= kIo && q.pinned_io && io()) ? HS_IO : HS_STAGE_TD;
+    return {HR_DIRECT, xm, false};
+  }
+  return {HR_STAGED, xd ? HS_AS_IS : HS_STAGE_TD, false};
+}
+static HostTaken ladder_synthesis(const HostQuery& q, HostEnv& e)
+{
+  const size_t kIo = (size_t)64 << 10, kSmall = (size_t)64 << 10, kDirect = (size_t)4 << 20;
+  const bool yd = q.samples_device, id = q.matrix_device;
+  const size_t ybytes = q.samples_bytes, ibytes = q.matrix_bytes;
+  auto io = [&] { e.asked += 'I'; return e.io; };
+  if (id && yd) return {HR_DEVICE, HS_AS_IS, false};
+  if (id && !yd && ybytes <= kIo && q.pinned_io && io()) return {HR_SCRATCH, HS_IO, false};
+  {
+    const bool small_y = ybytes <= kSmall;
+    const bool im = id ? true : (e.asked += 'M', e.mat);
+    bool ym = yd ? true : (small_y ? false : (e.asked += 'S', e.smp));       // (y_class is not looked at: the one difference)
+    bool staged = false;
+    if (im && !ym && !yd && small_y) { ym = true; staged = true; }
+    if (im && ym) return {HR_MAPPED, yd ? HS_AS_IS : staged ? HS_STAGE_TD : HS_MAPPED, false};
+  }
+  if (!id && q.host_copy == 0 && q.host_direct && ibytes <= kDirect && (yd || ybytes <= kSmall) && (e.asked += 'P', e.pin))
+  {
+    if (!(e.asked += 'D', e.idle)) return {HR_DIRECT, HS_AS_IS, true};
+    const bool through_io = !yd && ybytes <= kIo && q.pinned_io && io();
+    return {HR_DIRECT, yd ? HS_AS_IS : through_io ? HS_IO : HS_STAGE_TD, false};
+  }
+  return {HR_STAGED, yd ? HS_AS_IS : HS_STAGE_TD, false};
+}
+
+static HostQuery hq(bool analysis, size_t n, size_t m, size_t ch, size_t td, size_t fd, bool samples_device, bool matrix_device)
+{
+  HostQuery q;
+  q.analysis = analysis; q.samples_device = samples_device; q.matrix_device = matrix_device; q.n = n;
+  q.samples_bytes = ch * n * td; q.row_bytes = ch * m * 2 * fd; q.matrix_bytes = n * q.row_bytes;
+  return q;
+}
+
+static void test_host_routes()
+{
+  static const size_t sizes[] = {0, 1, 400, ((size_t)64 << 10) - 1, (size_t)64 << 10, ((size_t)64 << 10) + 1, (size_t)1 << 20, ((size_t)4 << 20) - 1, (size_t)4 << 20,
+                                 ((size_t)4 << 20) + 1, (size_t)256 << 20, (size_t)3 << 30};
+  size_t differ = 0;
+  for (int it = 0; it < 200000; ++it)
+  {
+    HostQuery q;
+    q.samples_device = (rnd() & 3) == 0; q.matrix_device = (rnd() & 3) == 0; q.by_value = (rnd() & 3) == 0;
+    q.samples_bytes = (rnd() & 1) ? sizes[rnd() % 12] : rnd_in(1, (size_t)1 << 22);
+    q.matrix_bytes = (rnd() & 1) ? sizes[rnd() % 12] : rnd_in(1, (size_t)1 << 24);
+    q.pinned_io = (rnd() & 3) != 0; q.host_copy = (rnd() & 3) == 0; q.host_direct = (rnd() & 3) != 0;
+    q.n = rnd_in(1, 2000000); q.row_bytes = (rnd() & 7) ? rnd_in(1, 70000) : 0; q.stage_bytes = (rnd() & 1) ? kDefaultStageBytes : rnd_in(1, (size_t)1 << 26);
+    HostEnv e;
+    e.io = (rnd() & 7) != 0; e.mat = rnd() & 1; e.smp = rnd() & 1; e.pin = (rnd() & 7) != 0; e.idle = (rnd() & 7) != 0;
+    HostTaken both[2]; std::string asked[2];
+    for (int analysis = 0; analysis < 2; ++analysis)
+    {
+      q.analysis = analysis != 0;
+      HostEnv a = e, b = e;
+      const HostRoute r = take(q, a);
+      const HostTaken want = analysis ? ladder_analysis(q, b) : ladder_synthesis(q, b);
+      both[analysis] = HostTaken{r.route, r.samples, r.refused}; asked[analysis] = a.asked;
+      CHECK(r.route == want.route && r.refused == want.refused && (r.refused || r.samples == want.samples), "the ladder's route: %d / %d, samples %d / %d", r.route, want.route, r.samples, want.samples);
+      CHECK(a.asked == b.asked, "the ladder's questions in the ladder's order: '%s' / '%s'", a.asked.c_str(), b.asked.c_str());
+      const bool sd = q.samples_device, md = q.matrix_device, small = q.samples_bytes <= kSmallHostBytes;
+      // exactly one route, and what belongs to it
+      CHECK(r.route >= HR_DEVICE && r.route <= HR_STAGED, "a route");
+      CHECK(r.end == (r.route <= HR_SCRATCH ? HE_FINISH : r.route == HR_STAGED ? HE_SYNCHRONIZE : HE_FINISH_MAPPED), "route %d ends in %d", r.route, r.end);
+      CHECK(r.pipe_allowed == (r.route == HR_DEVICE) && r.flag_wanted == (r.route <= HR_SCRATCH) && r.synchronous == (r.route == HR_SCRATCH), "flags of route %d", r.route);
+      CHECK((r.route == HR_DEVICE) == (sd && md), "the device route exactly for device memory on both sides");
+      CHECK((r.samples == HS_AS_IS) == (sd || r.refused), "device samples are used where they are");
+      if (r.refused) CHECK(r.route == HR_DIRECT && !e.idle, "only busy pinned pieces refuse a call");
+      if (r.route == HR_SCRATCH || r.samples == HS_IO) CHECK(!sd && small && q.pinned_io && e.io, "the scratch only within its size");
+      if (r.samples == HS_MAPPED) CHECK(r.route == HR_MAPPED && !small && e.smp, "mapped samples");
+      if (r.route == HR_MAPPED) CHECK(md || e.mat, "mapped matrix");
+      if (r.route == HR_DIRECT) CHECK(!md && q.matrix_bytes <= kDirectBytes && q.host_copy == 0 && q.host_direct && (sd || small), "the pinned pieces only for a hop-sized matrix");
+      CHECK((r.route == HR_STAGED) == (r.seg != 0), "a segment length exactly on the staged route");
+      if (r.route == HR_STAGED) CHECK(r.seg >= 1 && r.seg <= q.n && r.seg == stage_rows(q.n, q.row_bytes, q.stage_bytes), "staged segments of %zu rows", r.seg);
+      // no callable twice, none where its precondition is false
+      for (char c : {'I', 'M', 'S', 'P', 'D'}) CHECK(std::count(a.asked.begin(), a.asked.end(), c) <= 1, "'%c' asked twice: %s", c, a.asked.c_str());
+      auto was = [&](char c) { return a.asked.find(c) != std::string::npos; };
+      if (was('I')) CHECK(!sd && small && q.pinned_io, "ensure_io without small host samples");
+      if (was('M')) CHECK(!md, "a device matrix mapped");
+      if (was('S')) CHECK(!sd && !small && !(q.analysis && q.by_value), "samples mapped that are not worth it");
+      const bool direct_ok = !md && q.host_copy == 0 && q.host_direct && q.matrix_bytes <= kDirectBytes && (sd || small);
+      if (was('P')) CHECK(direct_ok, "ensure_pin off the direct route");
+      if (was('D')) CHECK(direct_ok && e.pin && a.asked.find('P') < a.asked.find('D'), "pin_idle before ensure_pin");
+      if (was('M') && was('S')) CHECK(a.asked.find('M') < a.asked.find('S'), "the matrix is mapped before the samples");
+    }
+    // The two directions take the same route and ask the same questions -- but for the ONE difference of the two ladders: the
+    // by-value sample of sdft_sdft is never registered in place (x_class == 0 keeps map_host off it), the by-value result of
+    // sdft_isdft is (isdft_n does not look at y_class there); it shows only beyond 64 KiB of samples, that is 16 Ki channels
+    const bool named = q.by_value && !q.samples_device && q.samples_bytes > kSmallHostBytes;
+    const bool same = both[0].route == both[1].route && both[0].samples == both[1].samples && both[0].refused == both[1].refused && asked[0] == asked[1];
+    if (!named) CHECK(same, "analysis and synthesis disagree: route %d / %d, asked '%s' / '%s'", both[1].route, both[0].route, asked[1].c_str(), asked[0].c_str());
+    else { CHECK(asked[1].find('S') == std::string::npos && asked[0].find('S') != std::string::npos, "the by-value sample is not mapped, the by-value result is"); ++differ; }
+  }
+  CHECK(differ > 100, "the difference was exercised: %zu", differ);
+}
+
+// HostIo::map_host: option host_register on, buffers of 1 MiB ... 256 MiB
+static HostEnv registering(const HostQuery& q, bool on)
+{
+  HostEnv e;
+  auto ok = [&](size_t bytes) { return on && bytes >= ((size_t)1 << 20) && bytes <= ((size_t)256 << 20); };
+  e.mat = ok(q.matrix_bytes); e.smp = ok(q.samples_bytes);
+  return e;
+}
+static void test_host_shapes()
+{
+  struct Shape { const char* name; HostQuery q; bool host_register; int route, samples, end; const char* asked; };
+  const HostQuery hop = hq(true, 100, 1000, 1, 4, 8, false, false);                       // test/test.c: 100 x 1000 bins, malloc'ed buffers
+  HostQuery hop_copy = hop; hop_copy.host_copy = 1;
+  HostQuery hop_nodirect = hop; hop_nodirect.host_direct = 0;
+  HostQuery hop_nopinned = hop; hop_nopinned.pinned_io = 0;
+  HostQuery hop_dev = hq(true, 100, 1000, 1, 4, 8, false, true); 
+  HostQuery hop_dev_nopinned = hop_dev; hop_dev_nopinned.pinned_io = 0;
+  HostQuery sample = hq(true, 1, 1000, 1, 4, 8, false, true); sample.by_value = true;     // sdft_sdft on a device row
+  HostQuery result = sample; result.analysis = false;                                     // sdft_isdft
+  const Shape shapes[] = {
+    {"the reference driver's hop", hop, false, HR_DIRECT, HS_IO, HE_FINISH_MAPPED, "MPDI"},
+    {"the hop, synthesis", hq(false, 100, 1000, 1, 4, 8, false, false), false, HR_DIRECT, HS_IO, HE_FINISH_MAPPED, "MPDI"},
+    {"the hop, host_copy 1", hop_copy, false, HR_STAGED, HS_STAGE_TD, HE_SYNCHRONIZE, "M"},
+    {"the hop, host_direct 0", hop_nodirect, false, HR_STAGED, HS_STAGE_TD, HE_SYNCHRONIZE, "M"},
+    {"the hop, pinned_io 0", hop_nopinned, false, HR_DIRECT, HS_STAGE_TD, HE_FINISH_MAPPED, "MPD"},
+    {"the hop, host_register 1 (1.6 MB)", hop, true, HR_MAPPED, HS_STAGE_TD, HE_FINISH_MAPPED, "M"},
+    {"half the hop, host_register 1 (below 1 MiB)", hq(true, 50, 1000, 1, 4, 8, false, false), true, HR_DIRECT, HS_IO, HE_FINISH_MAPPED, "MPDI"},
+    {"n = 10000, host_register 1 (160 MB)", hq(true, 10000, 1000, 1, 4, 8, false, false), true, HR_MAPPED, HS_STAGE_TD, HE_FINISH_MAPPED, "M"},
+    {"n = 300000 f64 samples, host_register 1 (samples 2.4 MB, matrix beyond 256 MiB)", hq(true, 300000, 1000, 1, 8, 8, false, false), true, HR_STAGED, HS_STAGE_TD, HE_SYNCHRONIZE, "MS"},
+    {"n = 15000 f64 samples, host_register 1 (matrix 240 MB, samples below 1 MiB)", hq(true, 15000, 1000, 1, 8, 8, false, false), true, HR_STAGED, HS_STAGE_TD, HE_SYNCHRONIZE, "MS"},
+    {"n = 8000 x 20 channels, host_register 1 (both mapped)", hq(true, 8000, 64, 20, 8, 8, false, false), true, HR_MAPPED, HS_MAPPED, HE_FINISH_MAPPED, "MS"},
+    {"sdft_sdft, device row", sample, false, HR_SCRATCH, HS_IO, HE_FINISH, "I"},
+    {"sdft_isdft, device row", result, false, HR_SCRATCH, HS_IO, HE_FINISH, "I"},
+    {"host hop, device matrix", hop_dev, false, HR_SCRATCH, HS_IO, HE_FINISH, "I"},
+    {"host hop, device matrix, pinned_io 0", hop_dev_nopinned, false, HR_MAPPED, HS_STAGE_TD, HE_FINISH_MAPPED, ""},
+    {"device / device", hq(true, 48000, 1024, 1, 4, 8, true, true), false, HR_DEVICE, HS_AS_IS, HE_FINISH, ""},
+    {"device samples, host hop matrix", hq(true, 100, 1000, 1, 4, 8, true, false), false, HR_DIRECT, HS_AS_IS, HE_FINISH_MAPPED, "MPD"},
+    {"n = 1e6 x 1024, host / host", hq(true, 1000000, 1024, 1, 4, 8, false, false), false, HR_STAGED, HS_STAGE_TD, HE_SYNCHRONIZE, "MS"},
+  };
+  for (const Shape& s : shapes)
+  {
+    HostEnv e = registering(s.q, s.host_register);
+    const HostRoute r = take(s.q, e);
+    CHECK(r.route == s.route && r.samples == s.samples && r.end == s.end && !r.refused, "%s: route %d samples %d end %d", s.name, r.route, r.samples, r.end);
+    CHECK(e.asked == s.asked, "%s: asked '%s'", s.name, e.asked.c_str());
+  }
+  HostEnv e;
+  HostRoute r = take(sample, e);
+  CHECK(r.synchronous && r.flag_wanted && !r.pipe_allowed, "sdft_sdft on a device row: synchronous, completion word wanted");
+  e = HostEnv{}; r = take(hq(false, 48000, 1024, 1, 4, 8, true, true), e);
+  CHECK(r.pipe_allowed && r.flag_wanted && !r.synchronous, "device / device may leave the plan's stream");
+  e = HostEnv{}; r = take(hq(true, 1000000, 1024, 1, 4, 8, false, false), e);
+  CHECK(r.seg == stage_rows(1000000, 16384, kDefaultStageBytes) && r.seg == 65536, "n = 1e6 x 1024 in segments of %zu rows", r.seg);
+  // the scratch or the pinned pieces cannot be had, or are busy
+  e = HostEnv{}; e.io = false; r = take(hop_dev, e);
+  CHECK(r.route == HR_MAPPED && r.samples == HS_STAGE_TD && e.asked == "I", "no scratch: the hop's samples through device scratch (%d, %d)", r.route, r.samples);
+  e = HostEnv{}; e.io = false; r = take(hop, e);
+  CHECK(r.route == HR_DIRECT && r.samples == HS_STAGE_TD && e.asked == "MPDI", "no scratch beside the pinned pieces (%d, %d)", r.route, r.samples);
+  e = HostEnv{}; e.pin = false; r = take(hop, e);
+  CHECK(r.route == HR_STAGED && r.seg == 100 && e.asked == "MP", "no pinned pieces: staged (%d)", r.route);
+  e = HostEnv{}; e.idle = false; r = take(hop, e);
+  CHECK(r.route == HR_DIRECT && r.refused && e.asked == "MPD", "busy pinned pieces fail the call (%d)", r.route);
+  // a matrix that was registered stays registered when the samples then cannot be
+  e = HostEnv{}; e.mat = true; e.smp = false; r = take(hq(true, 300000, 64, 1, 8, 8, false, false), e);
+  CHECK(r.route == HR_STAGED && e.asked == "MS", "matrix mapped, samples not: falls through (%d)", r.route);
+}
+
+// ---- the fused call (process_route) ---------------------------------------------------------------------------------------------
+static ProcessQuery pq(size_t n, size_t m, size_t ch, size_t fd, bool exact)
+{
+  ProcessQuery q;
+  q.fd_bytes = fd; q.fdx_bytes = 2 * fd;
+  q.chunk.n = n; q.chunk.channels = ch; q.chunk.nbins = m; q.chunk.exact = exact; q.chunk.rows_kernel = rows_kernel_ok(m, 2 * fd, false, true, 2);
+  q.chunk.row_waves = row_waves(m, 2 * fd); q.chunk.tiles = tiles(m, kWindowHann, 2 * fd, 0);
+  return q;
+}
+// process_n's decisions as it spelled them in place before process_route
+static ProcessRoute process_in_place(const ProcessQuery& q, size_t free_b, int& asked)
+{
+  ProcessRoute r;
+  const size_t n = q.chunk.n, nbins = q.chunk.nbins, channels = q.chunk.channels;
+  const bool dfts = q.spectrum, ordered = q.fused_exact < 0 ? (q.chunk.exact && q.fd_bytes == 8) : q.fused_exact != 0;
+  const long chunks = choose_chunks(q.chunk).chunks;
+  const bool walk_loses = row_slots(nbins, q.fdx_bytes) == 2 && q.fd_bytes == 4 && q.chunk.exact && q.fused_exact == 1;
+  const bool one_chunk_folded = chunks == 1 && n <= 512 && !ordered && !dfts && q.fold && nbins >= 8 && q.hop_kernel && q.linear && q.gain_rows <= 1;
+  if (one_chunk_folded) { r.path = PP_HOP_FOLDED; r.fold = true; r.flag_wanted = q.x_device && q.y_device; return r; }
+  if ((q.chunk.rows_kernel || (q.linear && q.gain_rows <= 65535u && !ordered && !dfts && q.fold && nbins >= 8 && nbins <= (size_t)4 * 64 * 16)) && (chunks > 1 || n > 512) && !walk_loses)
+  { r.path = PP_FUSED_ROWS; r.fold = !dfts; r.flag_wanted = q.x_device && q.y_device; return r; }
+  const size_t row_elems = channels * nbins;
+  size_t seg = dfts ? n : std::min(n, std::max<size_t>(1, q.stage_bytes / std::max<size_t>(row_elems * q.fdx_bytes, 1)));
+  if (!dfts && seg < n && q.stage_bytes == ((size_t)1 << 30))
+  {
+    if (q.workspace >= row_elems * n) seg = n;
+    else { ++asked; if (free_b) seg = std::max(seg, std::min(n, (free_b / 2) / std::max<size_t>(row_elems * q.fdx_bytes, 1))); }
+  }
+  r.path = chunks == 1 ? PP_HOP_PAIR : PP_SEGMENTS; r.seg = seg;
+  if (q.user)
+  {
+    const size_t m_first = std::min(seg, n), m_last = n - ((n - 1) / seg) * seg;
+    const bool hop_form = q.exact_inverse && q.inverse_rows <= 0;
+    r.rtc_hop = hop_form && (channels * m_first <= 1024 || channels * m_last <= 1024);
+    r.rtc_rows = !hop_form || channels * m_first > 1024 || channels * m_last > 1024 || dfts;
+  }
+  return r;
+}
+
+static void test_process_routes()
+{
+  static const size_t ms[] = {4, 7, 8, 64, 1000, 1024, 2048, 2049, 4096, 4097, 8192};
+  for (int it = 0; it < 200000; ++it)
+  {
+    const size_t fd = (rnd() & 1) ? 8 : 4;
+    ProcessQuery q = pq((rnd() & 1) ? rnd_in(1, 1200) : rnd_in(1, 2000000), ms[rnd() % 11], (rnd() & 3) ? 1 : rnd_in(1, 64), fd, fd == 4 || (rnd() & 3) == 0);
+    if ((rnd() & 7) == 0) q.chunk.rows_kernel = false;
+    q.chunk.forced_chunk = (rnd() & 7) ? 0 : (long)rnd_in(1, 5000);
+    q.linear = (rnd() & 3) != 0; q.user = !q.linear && (rnd() & 1); q.gain_rows = (rnd() & 3) ? 1 : ((rnd() & 1) ? rnd_in(2, 65535) : rnd_in(65536, 100000));
+    q.spectrum = (rnd() & 3) == 0; q.x_device = rnd() & 1; q.y_device = rnd() & 1;
+    q.fused_exact = (long)rnd_in(0, 3) - 1; q.fold = (rnd() & 7) != 0; q.hop_kernel = (rnd() & 7) != 0; q.exact_inverse = (rnd() & 7) != 0; q.inverse_rows = (rnd() & 7) ? 0 : 4;
+    q.stage_bytes = (rnd() & 1) ? kDefaultStageBytes : rnd_in(1, (size_t)1 << 28);
+    q.workspace = (rnd() & 3) ? 0 : rnd_in(1, (size_t)1 << 34);
+    const size_t free_b = (rnd() & 7) ? rnd_in(1, (size_t)288 << 30) : 0;
+    int asked = 0, want_asked = 0;
+    const ProcessRoute r = process_route(q, [&] { ++asked; return free_b; });
+    const ProcessRoute w = process_in_place(q, free_b, want_asked);
+    CHECK(r.path == w.path && r.fold == w.fold && r.flag_wanted == w.flag_wanted && r.seg == w.seg && r.rtc_hop == w.rtc_hop && r.rtc_rows == w.rtc_rows && asked == want_asked,
+          "process_n's own decisions: path %d / %d fold %d / %d seg %zu / %zu asked %d / %d", r.path, w.path, (int)r.fold, (int)w.fold, r.seg, w.seg, asked, want_asked);
+    const size_t n = q.chunk.n;
+    const bool two_pass = r.path == PP_HOP_PAIR || r.path == PP_SEGMENTS;
+    CHECK(r.path >= PP_HOP_FOLDED && r.path <= PP_SEGMENTS && PP_HOP_PAIR == 2 && PP_SEGMENTS == 3, "exactly one path; last_process_path stays 1 / 1 / 2 / 3");
+    CHECK(two_pass == (r.seg != 0) && (!two_pass || (r.seg >= 1 && r.seg <= n)), "segments of the two passes: %zu of %zu", r.seg, n);
+    if (!two_pass) CHECK(r.flag_wanted == (q.x_device && q.y_device) && !r.rtc_hop && !r.rtc_rows && asked == 0, "one launch");
+    else CHECK(!r.flag_wanted && !r.fold, "two passes never fold and never wait for a word");
+    if (r.path == PP_HOP_FOLDED) CHECK(n <= (size_t)kHopSamples && q.linear && !q.spectrum && q.fold && q.hop_kernel && q.chunk.nbins >= 8 && q.gain_rows <= 1 && r.fold, "the folded hop");
+    if (r.path == PP_FUSED_ROWS) CHECK(r.fold == !q.spectrum && (q.chunk.rows_kernel || (q.linear && q.chunk.nbins <= 4096 && q.gain_rows <= 65535)), "the fused rows");
+    if (q.spectrum && two_pass) CHECK(r.seg == n, "the caller's matrix takes the call in one piece");
+    if (asked) CHECK(asked == 1 && two_pass && !q.spectrum && q.stage_bytes == kDefaultStageBytes && q.workspace < q.chunk.channels * q.chunk.nbins * n, "free memory asked where the workspace may grow");
+    CHECK((r.rtc_hop || r.rtc_rows) == (q.user && two_pass), "run-time-compiled kernels for the host's statements on the two passes only");
+    if (q.user && two_pass)
+      for (size_t t = 0; t < n; t += std::max<size_t>(r.seg, n / 64 + 1) / r.seg * r.seg)       // (a sample of the segments; always the first)
+      {
+        const size_t m = std::min(r.seg, n - t);
+        const bool hop_form = q.exact_inverse && q.inverse_rows <= 0 && q.chunk.channels * m <= 1024;
+        CHECK(hop_form ? r.rtc_hop : r.rtc_rows, "the kernel of segment %zu (%zu rows) was resolved up front", t, m);
+      }
+    if (q.user && two_pass) { const size_t m = n - ((n - 1) / r.seg) * r.seg; CHECK((q.exact_inverse && q.inverse_rows <= 0 && q.chunk.channels * m <= 1024) ? r.rtc_hop : r.rtc_rows, "the last segment's kernel"); }
+  }
+}
+
+static void test_process_shapes()
+{
+  struct Shape { const char* name; ProcessQuery q; int path, fold, flag; size_t seg; int rtc_hop, rtc_rows, asked; };
+  const size_t free_b = (size_t)280 << 30;
+  const ProcessQuery hop = pq(100, 1000, 1, 8, false), c0 = pq(48000, 1024, 1, 8, false), c1 = pq(1000000, 1024, 1, 8, false);
+  ProcessQuery host_hop = hop; host_hop.y_device = false;
+  // the shift operation is linear and never comes with a copy of the spectrum (the entry point refuses that): the query of the identity
+  ProcessQuery shift_hop = hop, shift_long = c0; shift_hop.linear = shift_long.linear = true; shift_hop.spectrum = shift_long.spectrum = false;
+  ProcessQuery fe[3] = {pq(262144, 4096, 1, 4, true), pq(262144, 4096, 1, 4, true), pq(262144, 4096, 1, 4, true)};      // FD float, two-slot rows
+  for (int i = 0; i < 3; ++i) fe[i].fused_exact = i;
+  ProcessQuery fe1_bounded = fe[1]; fe1_bounded.stage_bytes = (size_t)256 << 20;
+  ProcessQuery ordered_hop = hop; ordered_hop.fused_exact = 1;
+  ProcessQuery carry_exact = c0; carry_exact.chunk.exact = true;                                   // fused_exact -1 follows the carries at FD double
+  ProcessQuery spectrum = c0; spectrum.spectrum = true;
+  ProcessQuery spectrum_hop = hop; spectrum_hop.spectrum = true;
+  ProcessQuery table_hop = hop; table_hop.gain_rows = 70000;
+  ProcessQuery table_long = c0; table_long.gain_rows = 70000;
+  ProcessQuery wide_table = pq(48000, 4096, 1, 8, false); wide_table.gain_rows = 1000;               // beyond the row-group kernel: the folded form's four bins per lane
+  ProcessQuery wide_table_many = wide_table; wide_table_many.gain_rows = 70000;
+  ProcessQuery user_hop = hop; user_hop.linear = false; user_hop.user = true;
+  ProcessQuery user_hop_copy = user_hop; user_hop_copy.spectrum = true;
+  ProcessQuery user_fused = c0; user_fused.linear = false; user_fused.user = true;
+  ProcessQuery user_long = pq(48000, 4096, 1, 8, false); user_long.linear = false; user_long.user = true;
+  ProcessQuery user_1024 = user_long; user_1024.stage_bytes = (size_t)64 << 20;                      // segments of 1024 rows, the last of 896
+  ProcessQuery user_2048 = user_long; user_2048.stage_bytes = (size_t)128 << 20;                     // 2048 rows, the last of 896
+  ProcessQuery user_rows4 = user_1024; user_rows4.inverse_rows = 4;
+  ProcessQuery gate_hop = hop; gate_hop.linear = false;
+  ProcessQuery nofold_hop = hop; nofold_hop.fold = 0;
+  ProcessQuery nofold_long = c0; nofold_long.fold = 0;
+  ProcessQuery nohop = hop; nohop.hop_kernel = 0;
+  ProcessQuery kept = user_long; kept.user = false; kept.workspace = (size_t)48000 * 4096;
+  const Shape shapes[] = {
+    {"the hop: n = 100, m = 1000", hop, PP_HOP_FOLDED, 1, 1, 0, 0, 0, 0},
+    {"the hop, host samples out", host_hop, PP_HOP_FOLDED, 1, 0, 0, 0, 0, 0},
+    {"configs[0]", c0, PP_FUSED_ROWS, 1, 1, 0, 0, 0, 0},
+    {"the shift operation on the hop", shift_hop, PP_HOP_FOLDED, 1, 1, 0, 0, 0, 0},
+    {"the shift operation, configs[0]", shift_long, PP_FUSED_ROWS, 1, 1, 0, 0, 0, 0},
+    {"configs[1] fused", c1, PP_FUSED_ROWS, 1, 1, 0, 0, 0, 0},
+    {"FD float, two slots, fused_exact 0", fe[0], PP_FUSED_ROWS, 1, 1, 0, 0, 0, 0},
+    {"FD float, two slots, fused_exact 1: the walk loses", fe[1], PP_SEGMENTS, 0, 0, 262144, 0, 0, 1},
+    {"... with stage_bytes bounded", fe1_bounded, PP_SEGMENTS, 0, 0, 8192, 0, 0, 0},
+    {"FD float, two slots, fused_exact 2", fe[2], PP_FUSED_ROWS, 1, 1, 0, 0, 0, 0},
+    {"the hop in the reference's order", ordered_hop, PP_HOP_PAIR, 0, 0, 100, 0, 0, 0},
+    {"carry = 1 at FD double", carry_exact, PP_FUSED_ROWS, 1, 1, 0, 0, 0, 0},
+    {"dfts given", spectrum, PP_FUSED_ROWS, 0, 1, 0, 0, 0, 0},
+    {"dfts given, the hop", spectrum_hop, PP_HOP_PAIR, 0, 0, 100, 0, 0, 0},
+    {"70000 gain vectors, the hop", table_hop, PP_HOP_PAIR, 0, 0, 100, 0, 0, 0},
+    {"70000 gain vectors, configs[0]", table_long, PP_FUSED_ROWS, 1, 1, 0, 0, 0, 0},
+    {"1000 gain vectors, m = 4096", wide_table, PP_FUSED_ROWS, 1, 1, 0, 0, 0, 0},
+    {"70000 gain vectors, m = 4096", wide_table_many, PP_SEGMENTS, 0, 0, 48000, 0, 0, 1},
+    {"OP_USER on a hop", user_hop, PP_HOP_PAIR, 0, 0, 100, 1, 0, 0},
+    {"OP_USER on a hop, dfts given", user_hop_copy, PP_HOP_PAIR, 0, 0, 100, 1, 1, 0},
+    {"OP_USER, configs[0]", user_fused, PP_FUSED_ROWS, 1, 1, 0, 0, 0, 0},
+    {"OP_USER on long segments", user_long, PP_SEGMENTS, 0, 0, 48000, 0, 1, 1},
+    {"OP_USER, segments of 1024", user_1024, PP_SEGMENTS, 0, 0, 1024, 1, 0, 0},
+    {"OP_USER, segments of 2048 and a tail of 896", user_2048, PP_SEGMENTS, 0, 0, 2048, 1, 1, 0},
+    {"OP_USER, inverse_rows 4", user_rows4, PP_SEGMENTS, 0, 0, 1024, 0, 1, 0},
+    {"gate on a hop", gate_hop, PP_HOP_PAIR, 0, 0, 100, 0, 0, 0},
+    {"fold 0, the hop", nofold_hop, PP_HOP_PAIR, 0, 0, 100, 0, 0, 0},
+    {"fold 0, configs[0]", nofold_long, PP_FUSED_ROWS, 1, 1, 0, 0, 0, 0},
+    {"hop_kernel 0", nohop, PP_HOP_PAIR, 0, 0, 100, 0, 0, 0},
+    {"nbins < 8, a hop", pq(100, 4, 1, 8, false), PP_HOP_PAIR, 0, 0, 100, 0, 0, 0},
+    {"nbins < 8, long", pq(48000, 4, 1, 8, false), PP_SEGMENTS, 0, 0, 48000, 0, 0, 0},
+    {"the workspace is there already", kept, PP_SEGMENTS, 0, 0, 48000, 0, 0, 0},
+  };
+  for (const Shape& s : shapes)
+  {
+    int asked = 0;
+    const ProcessRoute r = process_route(s.q, [&] { ++asked; return free_b; });
+    CHECK(r.path == s.path && r.fold == (s.fold != 0) && r.flag_wanted == (s.flag != 0) && r.seg == s.seg, "%s: path %d fold %d flag %d seg %zu", s.name, r.path, (int)r.fold, (int)r.flag_wanted, r.seg);
+    CHECK(r.rtc_hop == (s.rtc_hop != 0) && r.rtc_rows == (s.rtc_rows != 0) && asked == s.asked, "%s: rtc %d %d asked %d", s.name, (int)r.rtc_hop, (int)r.rtc_rows, asked);
+  }
+  // option fused_exact: -1 follows the carries at FD double
+  CHECK(reference_order(-1, true, 8) && !reference_order(-1, true, 4) && !reference_order(-1, false, 8) && reference_order(2, false, 4) && !reference_order(0, true, 8), "fused_exact");
+  // free memory unknown: the segments stage_bytes gives
+  const ProcessRoute r = process_route(fe[1], [] { return (size_t)0; });
+  CHECK(r.seg == 32768, "free memory unknown: %zu rows", r.seg);
+}
+
+// nanoseconds per decision over the named shapes (argument "time")
+static void time_routes()
+{
+  const HostQuery hqs[] = {hq(true, 100, 1000, 1, 4, 8, false, false), hq(false, 100, 1000, 1, 4, 8, false, false), hq(true, 1, 1000, 1, 4, 8, false, true),
+                           hq(true, 100, 1000, 1, 4, 8, true, true), hq(true, 1000000, 1024, 1, 4, 8, false, false)};
+  const ProcessQuery pqs[] = {pq(100, 1000, 1, 8, false), pq(1000000, 1024, 1, 8, false), pq(262144, 4096, 1, 4, true), pq(48000, 4096, 1, 8, false)};
+  const int reps = 2000000;
+  volatile size_t sink = 0;
+  volatile bool yes = true;
+  for (const HostQuery& q : hqs)
+  {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int i = 0; i < reps; ++i) { HostQuery c = q; c.n += (size_t)(i & 1); const HostRoute r = host_route(c, [&] { return (bool)yes; }, [&] { return !yes; }, [&] { return !yes; }, [&] { return (bool)yes; }, [&] { return (bool)yes; }); sink = sink + (size_t)r.route + r.seg; }
+    printf("host_route    %s samples %8zu B matrix %12zu B: %6.1f ns\n", q.analysis ? "analysis " : "synthesis", q.samples_bytes, q.matrix_bytes, std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - t0).count() / reps);
+  }
+  for (const ProcessQuery& q : pqs)
+  {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int i = 0; i < reps; ++i) { ProcessQuery c = q; c.chunk.n += (size_t)(i & 1); const ProcessRoute r = process_route(c, [&] { return (size_t)1 << 38; }); sink = sink + (size_t)r.path + r.seg; }
+    printf("process_route n %8zu m %5zu: %6.1f ns\n", q.chunk.n, q.chunk.nbins, std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - t0).count() / reps);
+  }
+}
+
+int main(int argc, char** argv)
+{
+  if (argc > 1 && std::string(argv[1]) == "time") { time_routes(); return 0; }
   test_geometry();
   test_chunks();
   test_relay_and_radices();
@@ -544,6 +928,10 @@ int main()
   test_forward_shapes();
   test_inverse_routes();
   test_inverse_shapes();
+  test_host_routes();
+  test_host_shapes();
+  test_process_routes();
+  test_process_shapes();
   if (failures) { fprintf(stderr, "%d failure(s)\n", failures); return 1; }
   printf("plan logic: all properties hold\n");
   return 0;

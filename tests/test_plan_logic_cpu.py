@@ -1,6 +1,7 @@
 """Host-side logic of the engine on the CPU under sanitizers (round-4 review: "none of the product's host
 C++ runs under ASan/UBSan/TSan").  sdft_plan_logic.hpp holds every decision of the host side that needs no HIP call (launch
-geometry, time chunking, relay block length, the routes of analysis and synthesis calls, which calls leave the plan's stream,
+geometry, time chunking, relay block length, the routes of analysis and synthesis calls, the route host memory takes through the
+entry points (host_route) and the path of the fused call (process_route), which calls leave the plan's stream,
 hop parts, rows per wave, the synchronous wait, the slot ring of the host copies); sdft_copy_engine.hpp the worker pool and the pipelined copies through pinned slots,
 with the device as a policy.  Both are compiled here by g++ -- no hipcc, no GPU -- and run with their property tests."""
 
