@@ -1,13 +1,13 @@
 // spectrogram.cpp -- C++ host in the shape of the reference's cpp/examples/analysis.cpp (without the
 // plotting): sdft::SDFT<float, double> over a chirp, prints the strongest bin every 4000 samples.  Only those rows are
-// formed (sdft_every: 12 rows of 1000 bins instead of the 48000 x 1000 matrix).
+// formed, only as powers and only for the band the sweep crosses (power: 12 rows of 520 real numbers instead of the
+// 48000 x 1000 complex matrix).
 //
 //   make -C examples && ./examples/spectrogram
 
 #include <sdft/sdft.h>      // resolves to include/cpp/sdft/sdft.h -> sdft/sdft.hpp
 
 #include <cmath>
-#include <complex>
 #include <cstdio>
 #include <vector>
 
@@ -24,15 +24,17 @@ int main()
   }
   sdft::SDFT<float, double> sdft(m, sdft::Window::Hann, 1);
   const size_t first = 3999, every = 4000;
-  std::vector<std::complex<double>> dfts((n - first + every - 1) / every * m);
-  const size_t rows = sdft.sdft_every(n, x.data(), every, first, dfts.data());
+  const size_t bin0 = 0, nbins = 520;                   // 0 ... 12.5 kHz: bin k is k * sr / (2 m) Hz
+  std::vector<double> power((n - first + every - 1) / every * nbins);
+  const size_t rows = sdft.power(n, x.data(), every, first, bin0, nbins, power.data());
   for (size_t r = 0; r < rows; ++r)
   {
     const size_t t = first + r * every;
-    const std::complex<double>* row = dfts.data() + r * m;
+    const double* row = power.data() + r * nbins;
     size_t best = 0;
-    for (size_t k = 1; k < m; ++k)
-      if (std::abs(row[k]) > std::abs(row[best])) best = k;
+    for (size_t k = 1; k < nbins; ++k)
+      if (row[k] > row[best]) best = k;
+    best += bin0;
     std::printf("t=%6zu  peak bin %4zu  ~%7.1f Hz  (instantaneous sweep frequency %7.1f Hz, window centre ~%zu samples earlier)\n",
                 t, best, (double)best * sr / (2.0 * m), (double)t / n * sr / 4, m);
   }

@@ -32,7 +32,9 @@ const char* sdft_hip_last_error(void);
   TD sdft_hip_isdft_##SUF(void* plan, const void* dft);                                             \
   void sdft_hip_isdft_n_##SUF(void* plan, std::size_t n, const void* dfts, TD* samples);            \
   void sdft_hip_isdft_nd_##SUF(void* plan, std::size_t n, const void** dfts, TD* samples);            \
-  long sdft_hip_sdft_every_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, void* dfts);
+  long sdft_hip_sdft_every_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, void* dfts); \
+  long sdft_hip_sdft_power_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first,     \
+                                   std::size_t bin0, std::size_t nbins, void* power);
 SDFT_HPP_DECLARE(f32f64, float)
 SDFT_HPP_DECLARE(f32f32, float)
 SDFT_HPP_DECLARE(f64f64, double)
@@ -67,6 +69,7 @@ namespace sdft
       static void isdft_n(void* p, std::size_t n, const void* d, TD* y) { sdft_hip_isdft_n_##SUF(p, n, d, y); } \
       static void isdft_nd(void* p, std::size_t n, const void** d, TD* y) { sdft_hip_isdft_nd_##SUF(p, n, d, y); } \
       static long sdft_every_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, void* d) { return sdft_hip_sdft_every_n_##SUF(p, n, x, e, f, d); } \
+      static long sdft_power_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_power_n_##SUF(p, n, x, e, f, b, k, d); } \
     };
     SDFT_HPP_ABI(f32f64, float, double)
     SDFT_HPP_ABI(f32f32, float, float)
@@ -149,6 +152,23 @@ namespace sdft
       {
         const char* e = sdft_hip_last_error();
         throw std::runtime_error(std::string("sdft_hip_sdft_every_n: ") + (e ? e : "failed"));
+      }
+      return static_cast<std::size_t>(rows);
+    }
+
+    /**
+     * Power-spectrogram analysis (sdft_hip_sdft_power_n): re*re + im*im of the bins bin0 <= k < bin0 + nbins of the rows
+     * sdft() would write for the samples first, first + every, ... < nsamples, dense (rows, nbins) in out; the plan's state
+     * advances over all samples and all bins.  Returns the number of rows written; streaming as with sdft_every().
+     **/
+    std::size_t power(const std::size_t nsamples, const T* samples, const std::size_t every, const std::size_t first,
+                      const std::size_t bin0, const std::size_t nbins, F* const out)
+    {
+      const long rows = api::sdft_power_n(plan_, nsamples, samples, every, first, bin0, nbins, out);
+      if (rows < 0)
+      {
+        const char* e = sdft_hip_last_error();
+        throw std::runtime_error(std::string("sdft_hip_sdft_power_n: ") + (e ? e : "failed"));
       }
       return static_cast<std::size_t>(rows);
     }

@@ -168,6 +168,28 @@ int sdft_hip_process_n(sdft_t* sdft, const sdft_size_t nsamples, const sdft_td_t
 long sdft_hip_sdft_every_n(sdft_t* sdft, const sdft_size_t nsamples, const sdft_td_t* samples,
                            const sdft_size_t every, const sdft_size_t first, sdft_fdx_t* dfts) SDFT_HIP_SYMBOL(sdft_every_n);
 
+/* ---- power-spectrogram analysis ------------------------------------------------------------------
+   sdft_hip_sdft_power_n writes |X|^2 of a band of bins on the row grid of sdft_hip_sdft_every_n: for the rows sdft_sdft_n would
+   write for the call's samples first, first + every, ... < nsamples (rows, streaming and the next call's first exactly as above;
+   every == 1 with first == 0 keeps every row) and the bins bin0 <= k < bin0 + nbins of each,
+     power = re * re + im * im
+   of the windowed, weighted bin as sdft_sdft_n stores it, evaluated in sdft_fd_t with two roundings for the products and one for
+   the sum (no fused multiply-add) -- what numpy's d.real * d.real + d.imag * d.imag gives on that call's row.  The complex bin
+   never reaches memory: the call stores half the bytes per bin of sdft_sdft_n and no second pass reads them back.
+   power is [rows][nbins] real numbers, dense; batched plans: samples [channels][nsamples], power [channels][rows][nbins].  It
+   need only be aligned to sizeof(sdft_fd_t).  The value is bit-identical to that expression wherever sdft_sdft_n is bit-identical
+   to the reference (FD float, FD double with option "carry" = 1, calls shorter than 512 samples), else within 2.1e-11 of the
+   largest power.  The stream state afterwards is the one sdft_sdft_n of the same samples leaves -- bins outside the band step
+   every sample too -- so any other entry point may follow.  samples and power may each be host or device memory (option "async"
+   applies to device pointers); power may be NULL when the call keeps no row.  The full grid with the full band is not
+   sdft_sdft_n: the call always runs its own kernel ("last_kernel" = 5).  Returns the number of rows written (0 for
+   nsamples == 0), or -1 with sdft_hip_last_error() set and the stream state untouched: a NULL plan, every == 0, nbins == 0,
+   bin0 + nbins > dftsize, or power == NULL with rows > 0. */
+long sdft_hip_sdft_power_n(sdft_t* sdft, const sdft_size_t nsamples, const sdft_td_t* samples,
+                           const sdft_size_t every, const sdft_size_t first,
+                           const sdft_size_t bin0, const sdft_size_t nbins,
+                           sdft_fd_t* power) SDFT_HIP_SYMBOL(sdft_power_n);
+
 /* ---- streams ---------------------------------------------------------------------------------
    Every plan owns a HIP stream.  Calls with host pointers always return with the output
    complete.  Calls with device pointers do too unless option "async" is 1; then they return after
@@ -282,7 +304,7 @@ double sdft_hip_time_hops(sdft_t* sdft, size_t hops, size_t hop, const sdft_td_t
    "relay_flow", "relay_groups", "chain_debug", "inverse_nt", "inverse_nt_skip_mb", "inverse_step", "inverse_ordered", "host_direct", "copy_streams" (sdft_capi.inc names what each selects);
    get_option "test_hooks" = 1 in that build.
    get_option additionally answers "tiles", "bins_per_lane", "row_slots", "last_chunks",
-   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis), "last_segments", "last_fused",
+   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis), "last_segments", "last_fused",
    "last_chain", "last_fused_exact", "last_fused_fold", "last_process_path" (1 fused kernel, 2 hop pair, 3 two-pass),
    "last_self", "last_inverse_nt" / "last_inverse_skip" (what the last synthesis launch used: non-temporal loads, rows read with ordinary loads),
    "cursor", "device", "ring_recoveries" (calls re-run with the serial carry pass after a poll loop of

@@ -54,6 +54,7 @@ def typed_signatures(combo: str):
         "plan_tables": (C.c_int, [sz, C.c_double, vp, vp, vp, vp]),
         "process_n": (C.c_int, [vp, sz, vp, vp, C.c_int, vp, vp]),
         "sdft_every_n": (C.c_long, [vp, sz, vp, sz, sz, vp]),
+        "sdft_power_n": (C.c_long, [vp, sz, vp, sz, sz, sz, sz, vp]),
     }
 
 

@@ -11,6 +11,8 @@
 //                          LDS), forward_kernel (independent waves with halo lanes: any N, row-pointer outputs)
 //   sdft_forward_every.hpp K1e   forward_every_kernel: forward_kernel's tiles, acc and fid stepped for every sample, only the
 //                          rows of a call-local grid (every-th sample) demodulated, windowed and stored (sdft_hip_sdft_every_n)
+//   sdft_forward_power.hpp K1p   forward_power_kernel: forward_every_kernel's grid plus a band of bins, re^2 + im^2 of the windowed
+//                          bin formed in registers and stored as one real number (sdft_hip_sdft_power_n)
 //   sdft_forward_hop.hpp   K1h   calls of one time chunk: forward_hop_kernel, forward_hop2_kernel (two waves per tile)
 //   sdft_ops.hpp           spectral operations of the fused call, the synthesis term (sdft.h:641-651), user_rows_kernel
 //   sdft_forward_rows.hpp  K1    forward_rows_kernel: one workgroup per (chunk, row), LDS edge exchange, lockstep row
@@ -41,6 +43,7 @@
 #include "sdft_carry_exact.hpp"
 #include "sdft_forward.hpp"
 #include "sdft_forward_every.hpp"
+#include "sdft_forward_power.hpp"
 #include "sdft_forward_hop.hpp"
 #include "sdft_ops.hpp"
 #include "sdft_forward_rows.hpp"

@@ -21,29 +21,38 @@
 
   // A call in time segments of at most `seg` samples: a side that is host memory goes through device scratch (copied in before
   // the segment runs, out after it), a side that is device memory is used where it is.  run(Segment&) does the segment's device
-  // call on s.td / s.mat; an analysis that keeps fewer rows than samples (sdft_every_n) sets s.row0 / s.rows, the rows copied out.
+  // call on s.td / s.mat; an analysis that keeps fewer rows than samples (sdft_every_n, sdft_power_n) sets s.row0 / s.rows, the
+  // rows copied out.  The matrix side is rows of row_bytes bytes per channel -- complex bins (fdx rows of N) or the real numbers of
+  // a band (sdft_power_n) --; s.mat_rows is the number of rows from one channel to the next in s.mat.
   struct StagedCall
   {
-    bool analysis; TD* td; bool td_host; fdx* mat; bool mat_host;
+    bool analysis; TD* td; bool td_host; void* mat; bool mat_host;
     size_t mat_rows, seg_rows;                               // matrix rows of the whole call; of one segment, at most
+    size_t row_bytes;                                        // of one channel's row
   };
-  struct Segment { size_t t, m; TD* td; size_t td_stride; fdx* mat; size_t mat_stride, row0, rows; };
+  struct Segment
+  {
+    size_t t, m; TD* td; size_t td_stride; void* mat; size_t mat_rows, row0, rows;
+    fdx* bins() const { return static_cast<fdx*>(mat); }     // the matrix side as rows of complex bins
+  };
+  size_t bins_row_bytes() const { return nbins * sizeof(fdx); }
   template <class Run>
   bool staged_segments(size_t n, size_t seg, const StagedCall& c, Run&& run)
   {
-    const size_t nb = nbins;
+    const size_t rb = c.row_bytes;
+    char* const mat = static_cast<char*>(c.mat);
     if (c.td_host && !d_stage_td.reserve(channels * seg)) return false;
-    if (c.mat_host && !d_stage_fdx.reserve(channels * c.seg_rows * nb)) return false;
+    if (c.mat_host && !d_stage_fdx.reserve((channels * c.seg_rows * rb + sizeof(fdx) - 1) / sizeof(fdx))) return false;
     for (size_t t = 0; t < n; t += seg)
     {
       const size_t m = std::min(seg, n - t);
       Segment s{t, m, c.td_host ? d_stage_td.p : c.td + t, c.td_host ? m : n,
-                c.mat_host ? d_stage_fdx.p : (c.mat ? c.mat + t * nb : nullptr), (c.mat_host ? m : c.mat_rows) * nb, t, m};
+                c.mat_host ? static_cast<void*>(d_stage_fdx.p) : (mat ? static_cast<void*>(mat + t * rb) : nullptr), c.mat_host ? m : c.mat_rows, t, m};
       if (c.analysis && c.td_host && !copy2d(s.td, m * sizeof(TD), c.td + t, n * sizeof(TD), m * sizeof(TD), hipMemcpyHostToDevice)) return false;
-      if (!c.analysis && c.mat_host && !copy2d(s.mat, m * nb * sizeof(fdx), c.mat + t * nb, n * nb * sizeof(fdx), m * nb * sizeof(fdx), hipMemcpyHostToDevice)) return false;
+      if (!c.analysis && c.mat_host && !copy2d(s.mat, m * rb, mat + t * rb, n * rb, m * rb, hipMemcpyHostToDevice)) return false;
       if (!run(s)) return false;
       if (c.analysis && c.mat_host && s.rows &&
-          !copy2d(c.mat + s.row0 * nb, c.mat_rows * nb * sizeof(fdx), s.mat, s.rows * nb * sizeof(fdx), s.rows * nb * sizeof(fdx), hipMemcpyDeviceToHost)) return false;
+          !copy2d(mat + s.row0 * rb, c.mat_rows * rb, s.mat, s.rows * rb, s.rows * rb, hipMemcpyDeviceToHost)) return false;
       if (!c.analysis && c.td_host && !copy2d(c.td + t, n * sizeof(TD), s.td, m * sizeof(TD), m * sizeof(TD), hipMemcpyDeviceToHost)) return false;
       SDFT_TRY(hipStreamSynchronize(stream));                // scratch buffers are reused; host memory is complete on return
     }
@@ -72,8 +81,8 @@
     const logic::HostRoute r = host_route(true, n, x, xd, x_class == 0, dfts, od, x_map, o_map);
     if (r.refused) return copy_failed();
     if (r.route == logic::HR_STAGED)
-      return staged_segments(n, r.seg, StagedCall{true, const_cast<TD*>(x), !xd, dfts, !od, n, r.seg},
-                             [&](Segment& s) { return forward_device(s.m, s.td, s.td_stride, s.mat, s.mat_stride, nullptr); });
+      return staged_segments(n, r.seg, StagedCall{true, const_cast<TD*>(x), !xd, dfts, !od, n, r.seg, bins_row_bytes()},
+                             [&](Segment& s) { return forward_device(s.m, s.td, s.td_stride, s.bins(), s.mat_rows * nbins, nullptr); });
     // one launch on the whole call: the samples and the matrix as the kernels see them
     const size_t xbytes = channels * n * sizeof(TD), obytes = matrix_bytes(n);
     const bool direct = r.route == logic::HR_DIRECT;
@@ -127,14 +136,58 @@
     size_t seg = n;
     if (!od) seg = std::min(seg, logic::stage_rows(n, row_bytes, stage_bytes) * every);
     if (!xd) seg = std::min(seg, std::max<size_t>((size_t)logic::kHopSamples, logic::stage_rows(n, channels * sizeof(TD), stage_bytes)));
-    return staged_segments(n, seg, StagedCall{true, const_cast<TD*>(x), !xd, dfts, !od, rows, (seg + every - 1) / every}, [&](Segment& s) {
+    return staged_segments(n, seg, StagedCall{true, const_cast<TD*>(x), !xd, dfts, !od, rows, (seg + every - 1) / every, bins_row_bytes()}, [&](Segment& s) {
       const size_t f = logic::every_first_from(s.t, every, first);
       s.rows = logic::every_rows(s.m, every, f);
       s.row0 = s.rows ? (s.t + f - first) / every : 0;       // the segment's first row in the call's grid
       if (od) s.mat = s.rows ? dfts + s.row0 * nb : nullptr;
-      else s.mat_stride = s.rows * nb;
+      else s.mat_rows = s.rows;
       const EveryGrid g{(unsigned long long)every, (unsigned long long)f};
-      return forward_device(s.m, s.td, s.td_stride, s.mat, s.mat_stride, nullptr, nullptr, &g);
+      return forward_device(s.m, s.td, s.td_stride, s.bins(), s.mat_rows * nb, nullptr, nullptr, &g);
+    });
+  }
+
+  // power-spectrogram analysis (sdft_hip_sdft_power_n): re^2 + im^2 of the bins [bin0, bin0 + nbins_out) of the rows sdft_n would
+  // write at the call's samples first, first + every, ... < n, dense [channels][rows][nbins_out] real numbers; the stream state
+  // afterwards is the one sdft_n leaves (bins outside the band step all the same).  The call is sdft_every_n's in every other respect:
+  // never resident, pipelined or fused, one forward launch on the plan's stream -- forward_power_kernel, for the full grid and the
+  // full band too --, host memory in time segments through device scratch.
+  bool sdft_power_n(size_t n, const TD* x, size_t every, size_t first, size_t bin0, size_t nbins_out, FD* power, size_t& rows)
+  {
+    static const char* fn = "sdft_hip_sdft_power_n";
+    rows = 0;
+    if (every == 0) { set_error(fn, "every must be at least 1"); return false; }
+    if (nbins_out == 0) { set_error(fn, "nbins must be at least 1"); return false; }
+    if (!logic::power_band_ok(nbins, bin0, nbins_out)) { set_error(fn, "the band bin0 ... bin0 + nbins - 1 does not lie within the plan's bins"); return false; }
+    rows = logic::every_rows(n, every, first);
+    if (rows > 0 && !power) { set_error(fn, "power is NULL but the call keeps rows"); return false; }
+    if (n == 0) return true;
+    if (!bind()) return false;
+    if (!pipe_join()) return false;
+    if (every > n) every = n;                                // (the same grid: at most one row; keeps first + k * every in range)
+    const bool xd = on_device(x);
+    const bool od = rows == 0 || on_device(power);
+    const size_t row_bytes = channels * nbins_out * sizeof(FD);
+    auto band = [&](FD* out, size_t out_rows, size_t f) {
+      return PowerArgs<FD>{out, logic::power_channel_stride(out_rows, nbins_out), (unsigned long long)every, (unsigned long long)f, (unsigned)bin0, (unsigned)nbins_out};
+    };
+    if (xd && od)
+    {
+      const PowerArgs<FD> g = band(power, rows, first);
+      return forward_device(n, x, n, nullptr, 0, nullptr, nullptr, nullptr, &g) && finish(rows * row_bytes);
+    }
+    // host memory: segments of at most seg samples (rows kept and samples within stage_bytes), each one forward launch on device scratch
+    size_t seg = n;
+    if (!od) seg = std::min(seg, logic::stage_rows(n, row_bytes, stage_bytes) * every);
+    if (!xd) seg = std::min(seg, std::max<size_t>((size_t)logic::kHopSamples, logic::stage_rows(n, channels * sizeof(TD), stage_bytes)));
+    return staged_segments(n, seg, StagedCall{true, const_cast<TD*>(x), !xd, power, !od, rows, (seg + every - 1) / every, nbins_out * sizeof(FD)}, [&](Segment& s) {
+      const size_t f = logic::every_first_from(s.t, every, first);
+      s.rows = logic::every_rows(s.m, every, f);
+      s.row0 = s.rows ? (s.t + f - first) / every : 0;       // the segment's first row in the call's grid
+      if (od) s.mat = s.rows ? power + s.row0 * nbins_out : nullptr;
+      else s.mat_rows = s.rows;
+      const PowerArgs<FD> g = band(static_cast<FD*>(s.mat), s.mat_rows, f);
+      return forward_device(s.m, s.td, s.td_stride, nullptr, 0, nullptr, nullptr, nullptr, &g);
     });
   }
 
@@ -199,8 +252,8 @@
     const logic::HostRoute r = host_route(false, n, y, yd, y_class == 0, dfts, id, y_map, i_map);
     if (r.refused) return copy_failed();
     if (r.route == logic::HR_STAGED)
-      return staged_segments(n, r.seg, StagedCall{false, y, !yd, const_cast<fdx*>(dfts), !id, n, r.seg},
-                             [&](Segment& s) { return inverse_device(s.m, s.mat, s.mat_stride, nullptr, s.td, s.td_stride); });
+      return staged_segments(n, r.seg, StagedCall{false, y, !yd, const_cast<fdx*>(dfts), !id, n, r.seg, bins_row_bytes()},
+                             [&](Segment& s) { return inverse_device(s.m, s.bins(), s.mat_rows * nbins, nullptr, s.td, s.td_stride); });
     const size_t ibytes = matrix_bytes(n), ybytes = channels * n * sizeof(TD);
     const bool direct = r.route == logic::HR_DIRECT;
     double t1 = 0.0;

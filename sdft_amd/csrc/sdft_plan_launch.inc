@@ -309,6 +309,18 @@
       default:           hipLaunchKernelGGL((forward_every_kernel<FD, BPL, WIN_BOXCAR>), gr, b, 0, stream, fa, g); break;
     }
   }
+  void launch_forward_power(const ForwardArgs<FD>& fa, const PowerArgs<FD>& g, unsigned blocks)
+  {
+    constexpr int BPL = sizeof(fdx) == 16 ? 1 : 2;
+    const dim3 gr(blocks), b(kBlock);
+    switch (window)
+    {
+      case WIN_HANN:     hipLaunchKernelGGL((forward_power_kernel<FD, BPL, WIN_HANN>), gr, b, 0, stream, fa, g); break;
+      case WIN_HAMMING:  hipLaunchKernelGGL((forward_power_kernel<FD, BPL, WIN_HAMMING>), gr, b, 0, stream, fa, g); break;
+      case WIN_BLACKMAN: hipLaunchKernelGGL((forward_power_kernel<FD, BPL, WIN_BLACKMAN>), gr, b, 0, stream, fa, g); break;
+      default:           hipLaunchKernelGGL((forward_power_kernel<FD, BPL, WIN_BOXCAR>), gr, b, 0, stream, fa, g); break;
+    }
+  }
 
 
   // rows in step (inverse_rows_body; where: logic::rows_in_step_ok)

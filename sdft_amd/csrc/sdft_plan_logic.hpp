@@ -172,7 +172,7 @@ struct EveryQuery
   long forced_chunk = 0;         // option "chunk"
   int compute_units = 256;
 };
-inline Chunking choose_every_chunks(const EveryQuery& q)
+inline Chunking choose_grid_chunks(const EveryQuery& q, long min_len)
 {
   Chunking r;
   const size_t n = q.n;
@@ -185,7 +185,7 @@ inline Chunking choose_every_chunks(const EveryQuery& q)
     const long target = (long)std::max(q.compute_units, 1) * kEverySimds * kEveryWavesPerSimd;
     const long per = std::max(1L, (long)std::max<size_t>(q.channels, 1) * std::max(1L, q.tiles));
     long want = (target + per - 1) / per;
-    want = std::max(1L, std::min(want, (long)(n / (size_t)kEveryMinLen)));
+    want = std::max(1L, std::min(want, (long)(n / (size_t)min_len)));
     len = (long)((n + (size_t)want - 1) / (size_t)want);
     len = ((len + kTimeGroup - 1) / kTimeGroup) * kTimeGroup;
     if (q.exact) len = ((len + 127) / 128) * 128;
@@ -194,6 +194,37 @@ inline Chunking choose_every_chunks(const EveryQuery& q)
   r.len = len; r.chunks = (long)((n + (size_t)len - 1) / (size_t)len);
   return r;
 }
+inline Chunking choose_every_chunks(const EveryQuery& q) { return choose_grid_chunks(q, kEveryMinLen); }
+
+// ---- power-spectrogram analysis (sdft_hip_sdft_power_n) ------------------------------------------------------------------------
+// |X|^2 of the bins [bin0, bin0 + nbins_out) of the rows of an every-grid, dense [channels][rows][nbins_out] real numbers.
+// The band lies inside the plan's bins and is not empty (no overflow of bin0 + nbins_out)
+inline bool power_band_ok(size_t nbins, size_t bin0, size_t nbins_out)
+{
+  return nbins_out != 0 && bin0 <= nbins && nbins_out <= nbins - bin0;
+}
+// Tile t of the independent-tile geometry owns the bins [t * per, min((t + 1) * per, nbins)), per = interior lanes x bins per lane
+// (halo lanes own nothing); it forms rows only if one of them is in the band.  forward_power_kernel makes the same test per wave.
+inline bool power_tile_emits(long tile, long interior, int bins_per_lane, size_t nbins, size_t bin0, size_t nbins_out)
+{
+  const size_t per = (size_t)interior * (size_t)bins_per_lane;
+  const size_t own0 = (size_t)tile * per, own1 = std::min(own0 + per, nbins);
+  return own0 < own1 && own0 < bin0 + nbins_out && bin0 < own1;
+}
+// elements from one channel's first power to the next channel's, and the place of bin k of row r in a channel
+inline size_t power_channel_stride(size_t rows, size_t nbins_out) { return rows * nbins_out; }
+inline size_t power_offset(size_t row, size_t k, size_t bin0, size_t nbins_out) { return row * nbins_out + (k - bin0); }
+// Time chunks of forward_power_kernel.  A sparse grid is forward_every_kernel's case (arithmetic-bound: choose_every_chunks).  On
+// a dense grid (every <= kTimeGroup: the kernel's burst path) every sample or so is a row, as in the tile kernel, so a short call
+// is cut with the tile kernel's minimum (choose_chunks: 64 samples); both rules ask for the same number of waves, so long calls
+// get the same chunks either way.  Measured, the dense grid wants no rule of its own: the kernel is bound by the arithmetic of
+// its rows, not by their bytes, and is flat in the chunk length -- configs[1], all bins, this choice (863 chunks of 1160 samples)
+// against chunks of 256 / 512 / 1024 / 2048 / 4632 / 9264: every = 1 2.237 against 2.198 / 2.035 / 2.097 / 1.978 / 2.261 /
+// 2.908 ms (between two runs the best moved from 512 to 2048: noise), every = 16 0.664 against 0.711 / 0.641 / 0.622 / 0.656 /
+// 0.767 / 1.033, every = 100 0.483 against 0.550 / 0.486 / 0.472 / 0.499 / 0.570 / 0.713 (profiles/power_rates.txt).
+constexpr long kPowerDenseMinLen = 64;
+inline long power_min_len(size_t every) { return every <= (size_t)kTimeGroup ? kPowerDenseMinLen : kEveryMinLen; }
+inline Chunking choose_power_chunks(const EveryQuery& q, size_t every) { return choose_grid_chunks(q, power_min_len(every)); }
 
 // ---- exact carries, relay form: block length = seed distance -----------------------------------------------------------
 // divides 2N and the chunk length; L products live in L registers per lane (128 at FD float, 64 register pairs at FD double);
@@ -525,6 +556,8 @@ struct ForwardQuery
   bool reference_order = false;           // the fused call sums bins in the reference's order
   bool coeff_ready = false;               // the fused call's folded coefficients are built
   bool every = false;                     // decimated analysis (forward_every_kernel)
+  bool power = false;                     // power-spectrogram analysis (forward_power_kernel) on a grid of ...
+  size_t power_every = 1;                 // ... every power_every-th sample
   bool row_pointers = false;              // rows go to a table of row pointers
   uintptr_t out = 0; size_t out_stride = 0;
   bool analysis_batch = false;            // CallPattern: analyses come call after call
@@ -534,7 +567,7 @@ struct ForwardQuery
   long rows_kernel = 1, row_slots_max = 2, interior = 0, chunk = 0, self = 1, fused = 1, fold = 1, fft_carry = 1, hop_kernel = 1, chain = 1,
        chain_L = 0, relay_flow = 1, segments = 0, xcd_map = 1, rows_f32 = 1, pipeline = 1;
 };
-enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4 };     // = get_option "last_kernel"
+enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5 };     // = get_option "last_kernel"
 // carries: the single chunk's are the stream state (delta_kernel copies it); pre-pass partial sums + scan (carries from the
 // closed-form table); the serial exact pass (carry_exact_kernel); the relay form of the exact pass (carry_relay_kernel)
 enum CarryForm : int { CARRY_STATE = 0, CARRY_SUMS = 1, CARRY_SERIAL = 2, CARRY_RELAY = 3 };
@@ -581,8 +614,9 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   ForwardRoute r;
   const size_t nb = q.nbins, span = 2 * nb, n = q.n, ch = std::max<size_t>(q.channels, 1);
   const bool pow2 = (span & (span - 1)) == 0;
-  // the decimated analysis has the tile form only
-  const bool rows = !q.every && rows_kernel_ok(nb, q.fdx_bytes, q.row_pointers, q.rows_kernel != 0, q.row_slots_max);
+  // the decimated and the power-spectrogram analysis have the tile form only
+  const bool grid = q.every || q.power;
+  const bool rows = !grid && rows_kernel_ok(nb, q.fdx_bytes, q.row_pointers, q.rows_kernel != 0, q.row_slots_max);
   const bool folded = q.fuse && !q.reference_order && !q.fuse_store && q.fold && q.coeff_ready;
   // pipelined calls (forward_self): decided first because they take the self-carried form at any length and cut time differently
   // (calls of a few thousand rows gain a microsecond from it and cost the host seven runtime calls instead of one,
@@ -603,17 +637,17 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   }
   if (!self_form) r.pipelined = false;
   Chunking c;
-  if (q.every)
+  if (grid)
   {
     EveryQuery e;
     e.n = n; e.channels = ch; e.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); e.exact = q.exact; e.forced_chunk = q.chunk; e.compute_units = q.compute_units;
-    c = choose_every_chunks(e);
+    c = q.power ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
   }
   else c = choose_chunks(chunk_query(q, rows, r.pipelined));
   r.chunks = c.chunks; r.len = c.len;
   r.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); r.interior = interior_lanes(q.window, q.fdx_bytes, q.interior);
-  r.kernel = q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
-  if (r.chunks == 1 && q.hop_kernel && nb >= 2 && !q.fuse && !q.every) { r.kernel = FK_HOP; return r; }
+  r.kernel = q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
+  if (r.chunks == 1 && q.hop_kernel && nb >= 2 && !q.fuse && !grid) { r.kernel = FK_HOP; return r; }
 
   // self-carried chunks: every workgroup derives its carry-in from the raw samples (fold + one FFT in LDS) and forms
   // its own differences -- the call is ONE launch.  Kernels that have the form: the row-group forward kernel and the
@@ -667,7 +701,7 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
     // once the relays are through.  The forward launch is held back (relay_gate_kernel polls a word every relay workgroup
     // bumps at its start) until the relays are resident: a forward workgroup that waits for a relay which cannot start
     // would be a deadlock -- every wait in the kernels is bounded all the same, and a time-out re-runs the call (forward_device).
-    r.flow = r.relay_L && q.relay_flow && q.segments <= 0 && (q.fuse || rows) && !q.every && gate_ok();
+    r.flow = r.relay_L && q.relay_flow && q.segments <= 0 && (q.fuse || rows) && !grid && gate_ok();
     if (r.flow) r.segments = 1;
     r.segments = std::max(1L, std::min(r.segments, r.chunks));
   }

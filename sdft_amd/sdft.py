@@ -247,6 +247,45 @@ class SDFT:
         assert got == rows, (got, rows)
         return out
 
+    def power(self, x, every: int = 1, first: int = 0, bins=None, out=None):
+        """Power-spectrogram analysis (``sdft_hip_sdft_power_n``): ``re*re + im*im`` of the bins ``bins = (bin0, nbins)`` (``None``:
+        all) of the rows :meth:`sdft` would return for the samples ``first``, ``first + every``, ... < n -> real array of shape
+        (rows, nbins) [(channels, rows, nbins) if batched], numpy for numpy input, a device tensor for a device tensor.  The
+        complex rows are never stored.  The plan's state advances over all n samples and all bins, as with :meth:`sdft`; the grid is
+        local to the call and streams with :func:`every_next_first`, as that of :meth:`sdft_every`."""
+        self.api.clear()
+        every, first = int(every), int(first)
+        bin0, nb = (0, self.dftsize) if bins is None else (int(bins[0]), int(bins[1]))
+        if every < 1 or first < 0:
+            raise ValueError(f"every must be >= 1 and first >= 0, got every={every}, first={first}")
+        if bin0 < 0 or nb < 1 or bin0 + nb > self.dftsize:
+            raise ValueError(f"bins = (bin0, nbins) must select at least one of the {self.dftsize} bins, got {(bin0, nb)}")
+        if _is_tensor(x):
+            torch = _torch()
+            n = self._shape_x(x.shape)
+            self._check_tensor(x, "samples", self.td)
+            rows = every_rows(n, every, first)
+            shape = (rows, nb) if x.dim() == 1 else (self.channels, rows, nb)
+            if out is None:
+                out = torch.empty(shape, dtype=getattr(torch, np.dtype(self.fd).name), device=x.device)
+            self._check_tensor(out, "out", self.fd, shape)
+            got = self.api.sdft_power_n(self._p, n, C.c_void_p(x.data_ptr()), every, first, bin0, nb, C.c_void_p(out.data_ptr() if rows else None))
+        else:
+            x = np.ascontiguousarray(x, dtype=self.td)
+            n = self._shape_x(x.shape)
+            rows = every_rows(n, every, first)
+            shape = (rows, nb) if x.ndim == 1 else (self.channels, rows, nb)
+            if out is None:
+                out = np.empty(shape, dtype=self.fd)
+            assert out.flags.c_contiguous and out.shape == shape and out.dtype == self.fd
+            got = self.api.sdft_power_n(self._p, n, C.c_void_p(x.ctypes.data), every, first, bin0, nb, C.c_void_p(out.ctypes.data if rows else None))
+        if got < 0:
+            self.api.check()
+            raise SdftHipError("sdft_hip_sdft_power_n failed")
+        self.api.check()
+        assert got == rows, (got, rows)
+        return out
+
     def isdft(self, dfts, out=None):
         """Synthesise samples from a DFT matrix (n, dftsize) [(channels, n, dftsize)]."""
         self.api.clear()
