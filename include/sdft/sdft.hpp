@@ -34,7 +34,9 @@ const char* sdft_hip_last_error(void);
   void sdft_hip_isdft_nd_##SUF(void* plan, std::size_t n, const void** dfts, TD* samples);            \
   long sdft_hip_sdft_every_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, void* dfts); \
   long sdft_hip_sdft_power_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first,     \
-                                   std::size_t bin0, std::size_t nbins, void* power);
+                                   std::size_t bin0, std::size_t nbins, void* power);                                    \
+  long sdft_hip_sdft_power_sum_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, \
+                                       std::size_t bin0, std::size_t nbins, void* sums);
 SDFT_HPP_DECLARE(f32f64, float)
 SDFT_HPP_DECLARE(f32f32, float)
 SDFT_HPP_DECLARE(f64f64, double)
@@ -70,6 +72,7 @@ namespace sdft
       static void isdft_nd(void* p, std::size_t n, const void** d, TD* y) { sdft_hip_isdft_nd_##SUF(p, n, d, y); } \
       static long sdft_every_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, void* d) { return sdft_hip_sdft_every_n_##SUF(p, n, x, e, f, d); } \
       static long sdft_power_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_power_n_##SUF(p, n, x, e, f, b, k, d); } \
+      static long sdft_power_sum_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_power_sum_n_##SUF(p, n, x, e, f, b, k, d); } \
     };
     SDFT_HPP_ABI(f32f64, float, double)
     SDFT_HPP_ABI(f32f32, float, float)
@@ -169,6 +172,25 @@ namespace sdft
       {
         const char* e = sdft_hip_last_error();
         throw std::runtime_error(std::string("sdft_hip_sdft_power_n: ") + (e ? e : "failed"));
+      }
+      return static_cast<std::size_t>(rows);
+    }
+
+    /**
+     * Pooled power analysis (sdft_hip_sdft_power_sum_n): the grid points first, first + every, ... cut the samples into windows;
+     * row r of out, dense (rows, nbins), is the sum of power()'s every == 1 values over the r-th window for the bins
+     * bin0 <= k < bin0 + nbins.  first > 0 makes row 0 the head window [0, first), which completes the previous call's last
+     * row (add the two); the next call's first is sdft_every()'s.  Sums, not means: divide by the window's length for a mean.
+     * The plan's state advances over all samples and all bins.  Returns the number of rows written.
+     **/
+    std::size_t power_sum(const std::size_t nsamples, const T* samples, const std::size_t every, const std::size_t first,
+                          const std::size_t bin0, const std::size_t nbins, F* const out)
+    {
+      const long rows = api::sdft_power_sum_n(plan_, nsamples, samples, every, first, bin0, nbins, out);
+      if (rows < 0)
+      {
+        const char* e = sdft_hip_last_error();
+        throw std::runtime_error(std::string("sdft_hip_sdft_power_sum_n: ") + (e ? e : "failed"));
       }
       return static_cast<std::size_t>(rows);
     }

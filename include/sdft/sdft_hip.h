@@ -190,6 +190,37 @@ long sdft_hip_sdft_power_n(sdft_t* sdft, const sdft_size_t nsamples, const sdft_
                            const sdft_size_t bin0, const sdft_size_t nbins,
                            sdft_fd_t* power) SDFT_HIP_SYMBOL(sdft_power_n);
 
+/* ---- pooled power analysis -------------------------------------------------------------------------
+   sdft_hip_sdft_power_sum_n sums |X|^2 over windows of rows, in the manner of Welch.  Let p[t][k] be the value
+   sdft_hip_sdft_power_n stores for sample t and bin k at every == 1, first == 0 (formed the same way: in sdft_fd_t, two rounded
+   products, one rounded sum, no fused multiply-add).  The grid points first, first + every, ... cut the call's samples into windows:
+     head window  [0, min(first, nsamples))                                  present iff first > 0 and nsamples > 0: the end of
+                                                                             a window a previous call began
+     window j     [first + j * every, min(first + (j + 1) * every, nsamples))  for every j with first + j * every < nsamples;
+                                                                             the last one may be short
+   rows = (first > 0 && nsamples > 0 ? 1 : 0) + (rows of sdft_hip_sdft_every_n for the same nsamples, every, first).  Row r holds,
+   for bin0 <= k < bin0 + nbins, the sum of p[t][k] over the r-th window (the head is row 0 when present), accumulated in
+   sdft_fd_t.  sums is [rows][nbins], dense, aligned to sizeof(sdft_fd_t) only; batched plans: samples [channels][nsamples], sums
+   [channels][rows][nbins].  Sums are returned, not means, because partial windows add: the next call's first is the one
+   sdft_hip_sdft_every_n's contract gives (first + rows_of_the_grid * every - nsamples, or first - nsamples when first >=
+   nsamples), and when it is not 0 the next call's row 0 completes this call's last row -- the host adds the two.  Divide a row
+   by its window's length for a mean.  every == 1 with first == 0 gives sdft_hip_sdft_power_n's values bit for bit.
+   Accuracy: the order in which a window's terms are added is the library's (time chunks cut windows).  Every term is
+   non-negative, so with S the exact sum of the sdft_fd_t terms, L the window's length, u = 2^-24 (float) or 2^-53 (double) and
+   gamma_n = n u / (1 - n u):  |sum - S| <= gamma_(L-1) S, element by element, wherever sdft_sdft_n is bit-identical to the
+   reference (FD float, FD double with option "carry" = 1, calls shorter than 512 samples); elsewhere the term deviation of
+   sdft_hip_sdft_power_n comes on top: 2.1e-11 of the largest power, times L.  The same plan, options and input give the same bits
+   on every run (no floating-point atomics: pieces of a window are added in ascending time order).
+   The stream state afterwards is the one sdft_sdft_n of the same samples leaves, so any other entry point may follow.  samples
+   and sums may each be host or device memory (option "async" applies to device pointers).  The call is never resident,
+   pipelined or fused and always runs its own kernel ("last_kernel" = 6).  Returns the number of rows written (0 only for
+   nsamples == 0), or -1 with sdft_hip_last_error() set and the stream state untouched: a NULL plan, every == 0, nbins == 0,
+   bin0 + nbins > dftsize, or sums == NULL with rows > 0. */
+long sdft_hip_sdft_power_sum_n(sdft_t* sdft, const sdft_size_t nsamples, const sdft_td_t* samples,
+                               const sdft_size_t every, const sdft_size_t first,
+                               const sdft_size_t bin0, const sdft_size_t nbins,
+                               sdft_fd_t* sums) SDFT_HIP_SYMBOL(sdft_power_sum_n);
+
 /* ---- streams ---------------------------------------------------------------------------------
    Every plan owns a HIP stream.  Calls with host pointers always return with the output
    complete.  Calls with device pointers do too unless option "async" is 1; then they return after
@@ -304,7 +335,7 @@ double sdft_hip_time_hops(sdft_t* sdft, size_t hops, size_t hop, const sdft_td_t
    "relay_flow", "relay_groups", "chain_debug", "inverse_nt", "inverse_nt_skip_mb", "inverse_step", "inverse_ordered", "host_direct", "copy_streams" (sdft_capi.inc names what each selects);
    get_option "test_hooks" = 1 in that build.
    get_option additionally answers "tiles", "bins_per_lane", "row_slots", "last_chunks",
-   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis), "last_segments", "last_fused",
+   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis, 6 pooled power analysis), "last_segments", "last_fused",
    "last_chain", "last_fused_exact", "last_fused_fold", "last_process_path" (1 fused kernel, 2 hop pair, 3 two-pass),
    "last_self", "last_inverse_nt" / "last_inverse_skip" (what the last synthesis launch used: non-temporal loads, rows read with ordinary loads),
    "cursor", "device", "ring_recoveries" (calls re-run with the serial carry pass after a poll loop of

@@ -55,6 +55,7 @@ def typed_signatures(combo: str):
         "process_n": (C.c_int, [vp, sz, vp, vp, C.c_int, vp, vp]),
         "sdft_every_n": (C.c_long, [vp, sz, vp, sz, sz, vp]),
         "sdft_power_n": (C.c_long, [vp, sz, vp, sz, sz, sz, sz, vp]),
+        "sdft_power_sum_n": (C.c_long, [vp, sz, vp, sz, sz, sz, sz, vp]),
     }
 
 

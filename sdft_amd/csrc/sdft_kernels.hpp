@@ -13,6 +13,9 @@
 //                          rows of a call-local grid (every-th sample) demodulated, windowed and stored (sdft_hip_sdft_every_n)
 //   sdft_forward_power.hpp K1p   forward_power_kernel: forward_every_kernel's grid plus a band of bins, re^2 + im^2 of the windowed
 //                          bin formed in registers and stored as one real number (sdft_hip_sdft_power_n)
+//   sdft_forward_power_sum.hpp K1s forward_pooled_power_kernel: that power at every sample, summed in registers over the windows of the
+//                          grid, one store per window; pooled_power_rows_kernel adds the pieces of the windows a chunk boundary cuts
+//                          (sdft_hip_sdft_power_sum_n)
 //   sdft_forward_hop.hpp   K1h   calls of one time chunk: forward_hop_kernel, forward_hop2_kernel (two waves per tile)
 //   sdft_ops.hpp           spectral operations of the fused call, the synthesis term (sdft.h:641-651), user_rows_kernel
 //   sdft_forward_rows.hpp  K1    forward_rows_kernel: one workgroup per (chunk, row), LDS edge exchange, lockstep row
@@ -44,6 +47,7 @@
 #include "sdft_forward.hpp"
 #include "sdft_forward_every.hpp"
 #include "sdft_forward_power.hpp"
+#include "sdft_forward_power_sum.hpp"
 #include "sdft_forward_hop.hpp"
 #include "sdft_ops.hpp"
 #include "sdft_forward_rows.hpp"

@@ -195,7 +195,7 @@ class Plan
   long opt_self = 1;             // chunk-parallel FD double calls, 2N a power of two: self-carried chunks (no pre-pass launches; logic::kSelfMax)
   long last_self = 0;
 
-  long last_kernel = 0;          // 1 = forward_kernel (independent tiles), 2 = forward_rows_kernel, 3 = hop, 4 = forward_every_kernel, 5 = forward_power_kernel
+  long last_kernel = 0;          // 1 = forward_kernel (independent tiles), 2 = forward_rows_kernel, 3 = hop, 4 = forward_every_kernel, 5 = forward_power_kernel, 6 = forward_pooled_power_kernel
 
   // device-resident stream state
   DevBuf<fdx> d_tw, d_syn, d_wtab;
@@ -239,6 +239,7 @@ class Plan
   DevBuf<TD> d_stage_td;
   DevBuf<fdx> d_stage_fdx;
   DevBuf<fdx*> d_rowptr;
+  DevBuf<FD> d_psum_ws, d_psum_head;                       // pooled power analysis: pieces of cut windows [channels][chunks][2][band]; a segment's head row
 
   // profile: HIP events on the plan's stream, one pair per stage launch, collected lazily so
   // that back-to-back asynchronous calls are never serialised by the measurement
@@ -525,12 +526,14 @@ class Plan
   }
   // every: decimated analysis (sdft_every_n) -- only the rows of that grid are stored, by forward_every_kernel
   // power: power-spectrogram analysis (sdft_power_n) -- forward_power_kernel stores |X|^2 of its band on its grid (out is unused)
+  // psum: pooled power analysis (sdft_power_sum_n) -- forward_pooled_power_kernel sums it over the grid's windows (out is unused)
   bool forward_device(size_t n, const TD* x, size_t x_stride, fdx* out, size_t out_stride, fdx* const* rows,
-                      const FuseArgs<TD, FD>* fuse = nullptr, const EveryGrid* every = nullptr, const PowerArgs<FD>* power = nullptr)
+                      const FuseArgs<TD, FD>* fuse = nullptr, const EveryGrid* every = nullptr, const PowerArgs<FD>* power = nullptr,
+                      const PowerSumArgs<FD>* psum = nullptr)
   {
     const struct { size_t cursor; int st_cur, hist_cur; bool fid_canonical; } was{cursor, st_cur, hist_cur, fid_canonical};
     auto restore = [&] { cursor = was.cursor; st_cur = was.st_cur; hist_cur = was.hist_cur; fid_canonical = was.fid_canonical; };
-    if (!forward_launch(n, x, x_stride, out, out_stride, rows, fuse, every, power))
+    if (!forward_launch(n, x, x_stride, out, out_stride, rows, fuse, every, power, psum))
     {
       // a launch that failed half-way (a host expression that does not compile, a grid that does not fit, an allocation)
       // must not leave the stream half-advanced: what was queued wrote the OTHER buffer set and the workspace only
@@ -544,7 +547,7 @@ class Plan
     restore();
     const long saved = opt_chain;
     opt_chain = 0;
-    const bool ok = forward_launch(n, x, x_stride, out, out_stride, rows, fuse, every, power) && (hipStreamSynchronize(stream) == hipSuccess);
+    const bool ok = forward_launch(n, x, x_stride, out, out_stride, rows, fuse, every, power, psum) && (hipStreamSynchronize(stream) == hipSuccess);
     opt_chain = saved;
     ++ring_recoveries;
     // a recovered call is a valid call: it goes to the warning channel (and the counter), not to the error channel, so a
@@ -559,13 +562,13 @@ class Plan
   }
 
   logic::ForwardQuery forward_query(size_t n, const fdx* out, size_t out_stride, fdx* const* rows, const FuseArgs<TD, FD>* fuse, const EveryGrid* every,
-                                   const PowerArgs<FD>* power) const
+                                   const PowerArgs<FD>* power, const PowerSumArgs<FD>* psum) const
   {
     logic::ForwardQuery q;
     q.n = n; q.nbins = nbins; q.channels = channels; q.fd_bytes = sizeof(FD); q.fdx_bytes = sizeof(fdx);
     q.window = window; q.compute_units = compute_units; q.cursor = cursor; q.exact = carry_mode == CARRY_EXACT; q.fid_canonical = fid_canonical;
     q.fuse = fuse != nullptr; q.fuse_store = fuse && fuse->store; q.reference_order = fuse && wants_reference_order(); q.coeff_ready = coeff_ready;
-    q.every = every != nullptr; q.power = power != nullptr; q.power_every = power ? (size_t)power->every : 1; q.row_pointers = rows != nullptr; q.out = reinterpret_cast<uintptr_t>(out); q.out_stride = out_stride;
+    q.every = every != nullptr; q.power = power != nullptr; q.power_every = power ? (size_t)power->every : 1; q.power_sum = psum != nullptr; q.row_pointers = rows != nullptr; q.out = reinterpret_cast<uintptr_t>(out); q.out_stride = out_stride;
     q.analysis_batch = calls.analysis_batch; q.pipe_wanted = pipe_wanted(nullptr); q.prev_out = prev_out;
     q.rows_kernel = opt_rows_kernel; q.row_slots_max = opt_row_slots_max; q.interior = opt_interior; q.chunk = opt_chunk; q.self = opt_self;
     q.fused = opt_fused; q.fold = opt_fold; q.fft_carry = opt_fft_carry; q.hop_kernel = opt_hop_kernel; q.chain = opt_chain; q.chain_L = opt_chain_L;
@@ -576,13 +579,14 @@ class Plan
   // The route (logic::forward_route) decides; this runs it: the hop and self-carried routes in a launch of their own, every
   // other route as delta -> carries -> forward
   bool forward_launch(size_t n, const TD* x, size_t x_stride, fdx* out, size_t out_stride, fdx* const* rows,
-                      const FuseArgs<TD, FD>* fuse = nullptr, const EveryGrid* every = nullptr, const PowerArgs<FD>* power = nullptr)
+                      const FuseArgs<TD, FD>* fuse = nullptr, const EveryGrid* every = nullptr, const PowerArgs<FD>* power = nullptr,
+                      const PowerSumArgs<FD>* psum = nullptr)
   {
     if (n == 0 || nbins == 0) return true;
     SDFT_TRY(hipSetDevice(device));
     flag_pending = false;                                    // only the hop kernel signals its completion
     calls.on_analysis(fuse != nullptr);                      // (which kind of host is calling: logic::CallPattern)
-    const logic::ForwardRoute r = logic::forward_route(forward_query(n, out, out_stride, rows, fuse, every, power), [this] { return gate_ok(); });
+    const logic::ForwardRoute r = logic::forward_route(forward_query(n, out, out_stride, rows, fuse, every, power, psum), [this] { return gate_ok(); });
     pipe_this = r.pipelined;
     if (r.out.hi) prev_out = r.out;
     last_kernel = r.kernel; last_chunks = r.chunks; last_chunk_len = r.len; last_tiles = r.tiles; last_interior = r.interior;
@@ -611,7 +615,7 @@ class Plan
     }
 
     DeltaIn<TD, FD> din;
-    if (!forward_delta(r, n, x, x_stride, din) || !forward_carries(r, n, din) || !forward_rows_stage(r, n, out, out_stride, rows, fuse, every, power)) return false;
+    if (!forward_delta(r, n, x, x_stride, din) || !forward_carries(r, n, din) || !forward_rows_stage(r, n, out, out_stride, rows, fuse, every, power, psum)) return false;
 
     // fid stays on the canonical rotation sequence unless this call seeded chunks from the closed-form
     // table; a call that crosses the roll-over with serial fid arithmetic puts it back
@@ -767,10 +771,18 @@ class Plan
   // K1: the rows, one launch per time segment (the new state goes to the other buffer set: the one a call started from survives
   // it, see forward_device)
   bool forward_rows_stage(const logic::ForwardRoute& r, size_t n, fdx* out, size_t out_stride, fdx* const* rows,
-                          const FuseArgs<TD, FD>* fuse, const EveryGrid* every, const PowerArgs<FD>* power)
+                          const FuseArgs<TD, FD>* fuse, const EveryGrid* every, const PowerArgs<FD>* power, const PowerSumArgs<FD>* psum)
   {
     const size_t nb = nbins;
     const long chunks = r.chunks, segments = r.segments;
+    // pooled power analysis: the workspace of the windows a chunk boundary cuts (grown on demand, kept by the plan)
+    PowerSumArgs<FD> ps{};
+    if (psum)
+    {
+      ps = *psum;
+      if (!d_psum_ws.reserve(logic::power_sum_workspace(channels, (size_t)chunks, ps.nbins_out))) return false;
+      ps.ws = chunks > 1 ? d_psum_ws.p : nullptr;
+    }
     if (!prof_begin(ST_FORWARD)) return false;
     ForwardArgs<FD> fa{};
     fa.delta = d_delta.p; fa.tw = d_tw.p; fa.wtab = d_wtab.p; fa.carry = d_carry.p;
@@ -814,12 +826,18 @@ class Plan
         else if (!launch_syn(fa, *fuse, (unsigned)groups, threads, r.fused && !exact_order, exact_order)) return false;
       }
       else if (r.kernel == logic::FK_ROWS) launch_forward_rows(fa, (unsigned)groups, threads, r.fused, r.rows_f32);
+      else if (psum) { if (!grid_fits(blocks)) return false; launch_forward_power_sum(fa, ps, (unsigned)blocks); }
       else if (power) { if (!grid_fits(blocks)) return false; launch_forward_power(fa, *power, (unsigned)blocks); }
       else if (every) { if (!grid_fits(blocks)) return false; launch_forward_every(fa, *every, (unsigned)blocks); }
       else launch_forward(fa, (unsigned)blocks);
       SDFT_TRY(hipGetLastError());
     }
     SDFT_TRY(hipGetLastError());
+    if (psum && chunks > 1)
+    {
+      if (!launch_power_sum_rows(ps, n, chunks, r.len, r.shift)) return false;
+      SDFT_TRY(hipGetLastError());
+    }
     if (r.flow) SDFT_TRY(hipStreamWaitEvent(stream, seg_events[0], 0));          // the call ends when both launches have
     last_flow = r.flow;
     return prof_end(ST_FORWARD);

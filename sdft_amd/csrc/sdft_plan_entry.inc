@@ -199,6 +199,84 @@
     set_error(fn, "row-pointer variants take single-channel plans only (use sdft_sdft_n / sdft_isdft_n with a batched plan)");
     return false;
   }
+
+  // pooled power analysis (sdft_hip_sdft_power_sum_n): the sums of sdft_power_n's every == 1 powers over the windows the grid
+  // first, first + every, ... cuts the call into (logic::power_sum_window), dense [channels][rows][nbins_out] real numbers, row 0
+  // the head window [0, first) when first > 0.  State, pointers and launches as sdft_power_n: never resident, pipelined or fused,
+  // forward_pooled_power_kernel on the plan's stream, then pooled_power_rows_kernel for the windows a chunk boundary cut.
+  // Host memory goes in time segments through device scratch; each segment is a pooled call of its own under the streaming
+  // contract, with its own first: the head row of a later segment is kept apart (d_psum_head) and added to the row the segment
+  // before it ended with, on the host for a host buffer, by pooled_power_add_kernel for a device buffer.
+  bool sdft_power_sum_n(size_t n, const TD* x, size_t every, size_t first, size_t bin0, size_t nbins_out, FD* sums, size_t& rows)
+  {
+    static const char* fn = "sdft_hip_sdft_power_sum_n";
+    rows = 0;
+    if (every == 0) { set_error(fn, "every must be at least 1"); return false; }
+    if (nbins_out == 0) { set_error(fn, "nbins must be at least 1"); return false; }
+    if (!logic::power_band_ok(nbins, bin0, nbins_out)) { set_error(fn, "the band bin0 ... bin0 + nbins - 1 does not lie within the plan's bins"); return false; }
+    rows = logic::power_sum_rows(n, every, first);
+    if (rows > 0 && !sums) { set_error(fn, "sums is NULL but the call writes rows"); return false; }
+    if (n == 0) return true;
+    if (!bind()) return false;
+    if (!pipe_join()) return false;
+    if (every > n) every = n;                                // (the same windows; keeps first + k * every in range)
+    const bool xd = on_device(x);
+    const bool od = on_device(sums);
+    const size_t row_bytes = channels * nbins_out * sizeof(FD);
+    auto band = [&](FD* row0, size_t row0_stride, FD* rest, size_t rest_stride, size_t f) {
+      return PowerSumArgs<FD>{row0, row0_stride, rest, rest_stride, nullptr, (unsigned long long)every, (unsigned long long)f, (unsigned)bin0, (unsigned)nbins_out};
+    };
+    const size_t stride = logic::power_channel_stride(rows, nbins_out);
+    if (xd && od)
+    {
+      const PowerSumArgs<FD> g = band(sums, stride, sums + nbins_out, stride, first);
+      return forward_device(n, x, n, nullptr, 0, nullptr, nullptr, nullptr, nullptr, &g) && finish(rows * row_bytes);
+    }
+    // host memory: segments of at most seg samples (rows written and samples within stage_bytes); where the grid allows it, of
+    // whole windows, so that no row is made of two segments
+    size_t seg = n;
+    if (!od) seg = std::min(seg, logic::stage_rows(n, row_bytes, stage_bytes) * every);
+    if (!xd) seg = std::min(seg, std::max<size_t>((size_t)logic::kHopSamples, logic::stage_rows(n, channels * sizeof(TD), stage_bytes)));
+    if (seg < n && seg > every && first % every == 0) seg -= seg % every;
+    std::vector<FD> head;                                    // host buffers: a segment's head row on its way to the row it completes
+    return staged_segments(n, seg, StagedCall{true, const_cast<TD*>(x), !xd, sums, !od, rows, (seg + every - 1) / every + 1, nbins_out * sizeof(FD)}, [&](Segment& s) {
+      const size_t f = logic::every_first_from(s.t, every, first);
+      const logic::PowerSumWindow w0 = logic::power_sum_window(s.t, n, every, first);      // of the segment's row 0 in the call
+      const bool joins = w0.begin < s.t;                     // row 0 is a head: it completes row w0.row of the call
+      const size_t seg_rows = logic::power_sum_rows(s.m, every, f), kept = seg_rows - (joins ? 1 : 0);
+      if (joins && !d_psum_head.reserve(channels * nbins_out)) return false;
+      s.row0 = w0.row + (joins ? 1 : 0); s.rows = kept;
+      PowerSumArgs<FD> g;
+      if (od)
+      {
+        FD* const at = sums + s.row0 * nbins_out;            // the segment's first row of its own
+        s.mat = at;
+        g = joins ? band(d_psum_head.p, nbins_out, at, stride, f) : band(at, stride, at + nbins_out, stride, f);
+      }
+      else
+      {
+        FD* const at = static_cast<FD*>(s.mat);              // scratch, [channels][kept][nbins_out]
+        s.mat_rows = kept;
+        g = joins ? band(d_psum_head.p, nbins_out, at, kept * nbins_out, f) : band(at, kept * nbins_out, at + nbins_out, kept * nbins_out, f);
+      }
+      if (!forward_device(s.m, s.td, s.td_stride, nullptr, 0, nullptr, nullptr, nullptr, nullptr, &g)) return false;
+      if (!joins) return true;
+      if (od)
+      {
+        const unsigned long long threads = (unsigned long long)channels * nbins_out;
+        hipLaunchKernelGGL((pooled_power_add_kernel<FD>), dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
+                           sums + w0.row * nbins_out, stride, d_psum_head.p, (unsigned)nbins_out, (unsigned)channels);
+        SDFT_TRY(hipGetLastError());
+        return true;
+      }
+      head.resize(channels * nbins_out);
+      if (!to_host(head.data(), d_psum_head.p, head.size() * sizeof(FD))) return false;
+      SDFT_TRY(hipStreamSynchronize(stream));
+      for (size_t c = 0; c < channels; ++c)
+        for (size_t k = 0; k < nbins_out; ++k) sums[c * stride + w0.row * nbins_out + k] += head[c * nbins_out + k];
+      return true;
+    });
+  }
   // a host table of device rows goes to the device; nullptr: failed
   fdx* const* device_table(fdx* const* dfts, size_t n, bool table_on_device)
   {

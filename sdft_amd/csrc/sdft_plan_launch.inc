@@ -321,6 +321,27 @@
       default:           hipLaunchKernelGGL((forward_power_kernel<FD, BPL, WIN_BOXCAR>), gr, b, 0, stream, fa, g); break;
     }
   }
+  void launch_forward_power_sum(const ForwardArgs<FD>& fa, const PowerSumArgs<FD>& g, unsigned blocks)
+  {
+    constexpr int BPL = sizeof(fdx) == 16 ? 1 : 2;
+    const dim3 gr(blocks), b(kBlock);
+    switch (window)
+    {
+      case WIN_HANN:     hipLaunchKernelGGL((forward_pooled_power_kernel<FD, BPL, WIN_HANN>), gr, b, 0, stream, fa, g); break;
+      case WIN_HAMMING:  hipLaunchKernelGGL((forward_pooled_power_kernel<FD, BPL, WIN_HAMMING>), gr, b, 0, stream, fa, g); break;
+      case WIN_BLACKMAN: hipLaunchKernelGGL((forward_pooled_power_kernel<FD, BPL, WIN_BLACKMAN>), gr, b, 0, stream, fa, g); break;
+      default:           hipLaunchKernelGGL((forward_pooled_power_kernel<FD, BPL, WIN_BOXCAR>), gr, b, 0, stream, fa, g); break;
+    }
+  }
+  // the rows of the windows a chunk boundary cuts, from their pieces in the workspace (chunks > 1)
+  bool launch_power_sum_rows(const PowerSumArgs<FD>& g, size_t n, long chunks, long len, long shift)
+  {
+    const unsigned long long threads = (unsigned long long)channels * (unsigned long long)(chunks - 1) * g.nbins_out;
+    const unsigned long long blocks = (threads + kBlock - 1) / kBlock;
+    if (!grid_fits(blocks)) return false;
+    hipLaunchKernelGGL((pooled_power_rows_kernel<FD>), dim3((unsigned)blocks), dim3(kBlock), 0, stream, g, n, (unsigned)chunks, (unsigned)len, (unsigned)shift, (unsigned)channels);
+    return true;
+  }
 
 
   // rows in step (inverse_rows_body; where: logic::rows_in_step_ok)

@@ -226,6 +226,76 @@ constexpr long kPowerDenseMinLen = 64;
 inline long power_min_len(size_t every) { return every <= (size_t)kTimeGroup ? kPowerDenseMinLen : kEveryMinLen; }
 inline Chunking choose_power_chunks(const EveryQuery& q, size_t every) { return choose_grid_chunks(q, power_min_len(every)); }
 
+// ---- pooled power analysis (sdft_hip_sdft_power_sum_n) -------------------------------------------------------------------------
+// The grid points first, first + every, ... cut the call's samples into windows; row r is the sum over the r-th window of the
+// powers sdft_hip_sdft_power_n stores at every == 1.  A call with first > 0 begins with the head window [0, min(first, n)), the end
+// of a window the previous call began (row 0); window j is [first + j * every, min(first + (j + 1) * every, n)).
+inline size_t power_sum_head(size_t n, size_t first) { return first > 0 && n > 0 ? 1 : 0; }
+inline size_t power_sum_rows(size_t n, size_t every, size_t first) { return power_sum_head(n, first) + every_rows(n, every, first); }
+struct PowerSumWindow { size_t row, begin, end; };           // samples [begin, end) of the call, end <= n
+// the window sample t < n lies in (every >= 1), and the window of row r < power_sum_rows(n, every, first)
+inline PowerSumWindow power_sum_window(size_t t, size_t n, size_t every, size_t first)
+{
+  if (t < first) return {0, 0, std::min(first, n)};
+  const size_t j = (t - first) / every, b = first + j * every;
+  return {power_sum_head(n, first) + j, b, every < n - b ? b + every : n};
+}
+inline PowerSumWindow power_sum_row_window(size_t row, size_t n, size_t every, size_t first)
+{
+  const size_t head = power_sum_head(n, first);
+  if (row < head) return {0, 0, std::min(first, n)};
+  const size_t b = first + (row - head) * every;
+  return {row, b, every < n - b ? b + every : n};
+}
+// Time chunk c of a launch is the samples [chunk_begin, chunk_end) (the kernels' t0 and t1: chunks of len samples, all but the
+// first shifted down by `shift` in the ring form of the exact carries); chunk_of is the chunk of sample t
+inline size_t chunk_begin(long c, long len, long shift) { return c ? (size_t)c * (size_t)len - (size_t)shift : 0; }
+inline size_t chunk_end(long c, long len, long shift, size_t n) { return std::min((size_t)(c + 1) * (size_t)len - (size_t)shift, n); }
+inline long chunk_of(size_t t, long len, long shift) { return (long)((t + (size_t)shift) / (size_t)len); }
+// What a chunk [t0, t1) does with its windows.  A window that begins and ends inside the chunk is whole: the forward kernel stores
+// its row.  At most two windows are cut by the chunk's ends: the one that began before t0 leaves its samples of the chunk as the
+// chunk's head piece, the one that runs past t1 as its tail piece (a chunk that lies wholly inside one window has the head piece
+// only).  Pieces go to the plan's workspace [channels][chunks][2][nbins_out], head in slot 0, tail in slot 1.
+constexpr int kPowerSumHeadSlot = 0, kPowerSumTailSlot = 1;
+struct PowerSumChunk
+{
+  bool head = false, tail = false;
+  size_t head_row = 0, tail_row = 0;                         // the rows the pieces belong to
+  size_t whole_row0 = 0, whole_rows = 0;                     // rows whole_row0 ... whole_row0 + whole_rows - 1 are stored from this chunk
+};
+inline PowerSumChunk power_sum_chunk(size_t t0, size_t t1, size_t n, size_t every, size_t first)
+{
+  PowerSumChunk p;
+  if (t0 >= t1) return p;
+  const PowerSumWindow a = power_sum_window(t0, n, every, first), b = power_sum_window(t1 - 1, n, every, first);
+  p.head = a.begin < t0; p.head_row = a.row;
+  p.tail = b.end > t1 && !(p.head && a.row == b.row); p.tail_row = b.row;
+  p.whole_row0 = a.row + (p.head ? 1 : 0);
+  const size_t past = b.row + (b.end > t1 ? 0 : 1);          // the first row after the whole ones
+  p.whole_rows = past > p.whole_row0 ? past - p.whole_row0 : 0;
+  return p;
+}
+inline size_t power_sum_slot(size_t channel, size_t chunks, size_t chunk, int slot, size_t nbins_out)
+{
+  return ((channel * chunks + chunk) * 2 + (size_t)slot) * nbins_out;
+}
+inline size_t power_sum_workspace(size_t channels, size_t chunks, size_t nbins_out) { return chunks > 1 ? channels * chunks * 2 * nbins_out : 0; }
+// The chunks a row's window touches, c0 <= c1.  c1 == c0: the row is whole in that chunk.  Else the row is cut and is the sum, in
+// this order, of the tail piece of chunk c0 and the head pieces of the chunks c0 + 1 ... c1 (pooled_power_rows_kernel: the thread
+// of chunk c0 + 1 adds them; ascending order, so the same bits on every run).
+struct PowerSumRowChunks { long c0, c1; };
+inline PowerSumRowChunks power_sum_row_chunks(const PowerSumWindow& w, long len, long shift)
+{
+  return {chunk_of(w.begin, len, shift), chunk_of(w.end - 1, len, shift)};
+}
+// Time chunks of forward_pooled_power_kernel: every sample is a windowed power, whatever `every` is, so this is
+// forward_power_kernel's dense grid (choose_power_chunks at every == 1: the tile kernel's minimum of 64 samples, the wave count of
+// the arithmetic-bound kernels).  Shorter chunks than that cost a carry-in each and cut more windows; longer ones leave SIMDs idle.
+// Measured, configs[1], all bins, this choice (863 chunks of 1160 samples) against chunks of 256 / 512 / 1024 / 2048 / 4632 / 9264:
+// every = 100 1.520 against 1.566 / 1.508 / 1.537 / 1.658 / 1.850 / 2.348 ms, every = n (one window over all chunks: 863 pieces per
+// bin for pooled_power_rows_kernel) 1.495 against 1.712 / 1.577 / 1.556 / 1.637 / 1.845 / 2.343 ms (profiles/power_sum_rates.txt).
+inline Chunking choose_power_sum_chunks(const EveryQuery& q) { return choose_power_chunks(q, 1); }
+
 // ---- exact carries, relay form: block length = seed distance -----------------------------------------------------------
 // divides 2N and the chunk length; L products live in L registers per lane (128 at FD float, 64 register pairs at FD double);
 // the seed table (fid at every L-th cursor) stays below 256 MiB.  0: no block length fits (serial pass).
@@ -558,6 +628,7 @@ struct ForwardQuery
   bool every = false;                     // decimated analysis (forward_every_kernel)
   bool power = false;                     // power-spectrogram analysis (forward_power_kernel) on a grid of ...
   size_t power_every = 1;                 // ... every power_every-th sample
+  bool power_sum = false;                 // pooled power analysis (forward_pooled_power_kernel)
   bool row_pointers = false;              // rows go to a table of row pointers
   uintptr_t out = 0; size_t out_stride = 0;
   bool analysis_batch = false;            // CallPattern: analyses come call after call
@@ -567,7 +638,7 @@ struct ForwardQuery
   long rows_kernel = 1, row_slots_max = 2, interior = 0, chunk = 0, self = 1, fused = 1, fold = 1, fft_carry = 1, hop_kernel = 1, chain = 1,
        chain_L = 0, relay_flow = 1, segments = 0, xcd_map = 1, rows_f32 = 1, pipeline = 1;
 };
-enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5 };     // = get_option "last_kernel"
+enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6 };     // = get_option "last_kernel"
 // carries: the single chunk's are the stream state (delta_kernel copies it); pre-pass partial sums + scan (carries from the
 // closed-form table); the serial exact pass (carry_exact_kernel); the relay form of the exact pass (carry_relay_kernel)
 enum CarryForm : int { CARRY_STATE = 0, CARRY_SUMS = 1, CARRY_SERIAL = 2, CARRY_RELAY = 3 };
@@ -614,8 +685,8 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   ForwardRoute r;
   const size_t nb = q.nbins, span = 2 * nb, n = q.n, ch = std::max<size_t>(q.channels, 1);
   const bool pow2 = (span & (span - 1)) == 0;
-  // the decimated and the power-spectrogram analysis have the tile form only
-  const bool grid = q.every || q.power;
+  // the decimated, the power-spectrogram and the pooled power analysis have the tile form only
+  const bool grid = q.every || q.power || q.power_sum;
   const bool rows = !grid && rows_kernel_ok(nb, q.fdx_bytes, q.row_pointers, q.rows_kernel != 0, q.row_slots_max);
   const bool folded = q.fuse && !q.reference_order && !q.fuse_store && q.fold && q.coeff_ready;
   // pipelined calls (forward_self): decided first because they take the self-carried form at any length and cut time differently
@@ -641,12 +712,12 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   {
     EveryQuery e;
     e.n = n; e.channels = ch; e.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); e.exact = q.exact; e.forced_chunk = q.chunk; e.compute_units = q.compute_units;
-    c = q.power ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
+    c = q.power_sum ? choose_power_sum_chunks(e) : q.power ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
   }
   else c = choose_chunks(chunk_query(q, rows, r.pipelined));
   r.chunks = c.chunks; r.len = c.len;
   r.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); r.interior = interior_lanes(q.window, q.fdx_bytes, q.interior);
-  r.kernel = q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
+  r.kernel = q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
   if (r.chunks == 1 && q.hop_kernel && nb >= 2 && !q.fuse && !grid) { r.kernel = FK_HOP; return r; }
 
   // self-carried chunks: every workgroup derives its carry-in from the raw samples (fold + one FFT in LDS) and forms
