@@ -191,6 +191,7 @@ int SDFT_FN(set_option)(void* p, const char* key, long value)
   else if (!strcmp(key, "inverse_ordered")) q->opt_inverse_ordered = value;    // whole rows, ordered sum: 1 always where it applies, -1 never
   else if (!strcmp(key, "host_direct")) q->io.opt_host_direct = value;         // 0: a hop-sized host matrix by DMA between staging matrix and pinned pieces
   else if (!strcmp(key, "copy_streams")) q->io.opt_copy_streams = value;       // 1: the DMAs of long host copies on one stream
+  else if (!strcmp(key, "prefix_cells")) q->opt_prefix_cells = value;          // prefix-cell route of long calls: 0 never, 1 beyond 2^19 samples, 2 whatever the length
 #ifdef SDFT_SELF_STAMPS
   else if (!strcmp(key, "self_stamps")) q->opt_self_stamps = value;
 #endif
@@ -250,6 +251,10 @@ long SDFT_FN(get_option)(const void* p, const char* key)
   if (!strcmp(key, "last_hop_parts")) return q->last_hop_parts;
   if (!strcmp(key, "self_carry")) return q->opt_self;
   if (!strcmp(key, "last_self")) return q->last_self;
+  if (!strcmp(key, "last_prefix")) return q->last_prefix;
+#ifdef SDFT_HIP_TEST_HOOKS
+  if (!strcmp(key, "prefix_cells")) return q->opt_prefix_cells;
+#endif
   if (!strcmp(key, "host_register")) return q->io.opt_host_register;
   if (!strcmp(key, "host_register_hits")) return q->io.host_reg_hits;
   if (!strcmp(key, "host_copy")) return q->io.opt_host_copy;

@@ -351,4 +351,113 @@ __global__ __launch_bounds__(kScanBins * kScanSlices) void carry_scan_kernel(Car
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// K1s, long calls (prefix cells, FD double): the fold of the self-carried chunks (self_fold in sdft_forward.hpp), shared by all
+// chunks of a call.  Chunk j's workgroup needs cells_j[v] = sum of delta_t over the t < t0_j = j * chunk_len that arrive
+// at cursor v: a prefix over time of one real number per cursor.  This kernel walks, for every channel and every cursor
+// v < 2N, the samples tv, tv + 2N, ... < n in time order, adds delta_t = (FD)(x[t] - x[t - 2N]) (sdft.h:564, the
+// subtraction in TD precision) into ONE accumulator and stores the running sum to prefix[ch][j][v] whenever t passes
+// t0_j -- bit for bit what self_fold leaves in LDS for chunk j, so the rows are those of the self-carried route.
+// A workgroup owns kPrefixCells cursors; kPrefixSlices thread groups each load kPrefixRows consecutive samples of a cell
+// into registers up front (all loads of a workgroup in flight at once), then take the running sum in turn through LDS:
+// the additions stay in time order, slice totals are never added; only the additions are on that chain, the stores of
+// all slices follow together.  No workgroup waits for another.
+// The chain is serial in the rows of a cell, n / 2N of them (every kPrefixSlices * kPrefixRows rows one load phase and
+// kPrefixSlices turns), on 2N / kPrefixCells workgroups per channel: the route that takes this kernel is bounded by rows per
+// cell (logic::kPrefixRowsMax); beyond it the partial sums + scan stay.
+// (chunk 0 starts at sample 0 and needs no cells: prefix[ch][0] is not written.)
+// ------------------------------------------------------------------------------------------
+constexpr int kPrefixCells = 32;
+constexpr int kPrefixSlices = 32;
+constexpr int kPrefixRows = 16;
+
+template <typename TD, typename FD> struct PrefixArgs
+{
+  const TD* x;                // [channels][n] the call's samples
+  size_t x_stride;
+  const TD* hist_in;          // [channels][2N] delay line in time order
+  FD* prefix;                 // [channels][chunks][2N]
+  size_t n;
+  unsigned span, chunks, chunk_len, cursor0;
+};
+
+template <typename TD, typename FD>
+__global__ __launch_bounds__(kPrefixCells * kPrefixSlices) void prefix_cells_kernel(PrefixArgs<TD, FD> a)
+{
+  constexpr unsigned C = kPrefixCells, S = kPrefixSlices, R = kPrefixRows;
+  __shared__ FD run[C];
+  const unsigned m = a.span;
+  const unsigned cell_blocks = (m + C - 1) / C;
+  const unsigned c = threadIdx.x % C, slice = threadIdx.x / C;
+  const unsigned v = (blockIdx.x % cell_blocks) * C + c;
+  const size_t ch = blockIdx.x / cell_blocks;
+  const bool live = v < m;
+  const TD* xs = a.x + ch * a.x_stride;
+  const TD* hs = a.hist_in + ch * (size_t)m;
+  FD* out = a.prefix + ch * (size_t)a.chunks * m + (live ? v : 0u);     // chunk j at out[j * m]
+  const size_t n = a.n, len = a.chunk_len;
+  const size_t tv = (size_t)(((live ? v : 0u) + m - a.cursor0) % m);    // first sample that arrives at cursor v (cursor0 < m)
+  const size_t rows_v = tv < n ? (n - 1 - tv) / m + 1 : 0;              // samples of this cell
+  const size_t rows_max = (n + m - 1) / m;                              // workgroup-uniform bound of rows_v
+  if (slice == 0) run[c] = (FD)0;
+  __syncthreads();
+  for (size_t base = 0; base == 0 || base < rows_max; base += (size_t)S * R)
+  {
+    // rows g0 ... g0 + R - 1 of the cell: requested before the first is used, every load unconditional (an index past
+    // the call is clamped, its value ignored)
+    const size_t g0 = base + (size_t)slice * R;
+    const size_t tfirst = tv + g0 * m;
+    const size_t tp = tfirst - m;                                       // (g0 > 0) the sample before the slice's first
+    TD prev = g0 == 0 ? hs[tv] : xs[tp < n ? tp : n - 1];
+    TD cur[R];
+#pragma unroll
+    for (unsigned i = 0; i < R; ++i)
+    {
+      const size_t t = tfirst + (size_t)i * m;
+      cur[i] = xs[t < n ? t : n - 1];
+    }
+    const bool mine = live && (g0 < rows_v || g0 == 0);
+    FD d[R];
+#pragma unroll
+    for (unsigned i = 0; i < R; ++i)
+    {
+      const TD dd = cur[i] - (i ? cur[i - 1] : prev);                    // TD precision (sdft.h:564)
+      d[i] = (FD)dd;
+    }
+    // the running sum goes from slice to slice in time order; a slice keeps the sum BEFORE each of its rows (what a chunk
+    // that starts between the previous row and this one reads) -- additions only on this chain, the stores follow below
+    FD pre[R];
+    FD sum = (FD)0;
+    for (unsigned s = 0; s < S; ++s)
+    {
+      if (slice == s && mine)
+      {
+        sum = run[c];
+#pragma unroll
+        for (unsigned i = 0; i < R; ++i)
+        {
+          pre[i] = sum;
+          if (g0 + i < rows_v) sum += d[i];
+        }
+        run[c] = sum;
+      }
+      __syncthreads();
+    }
+    if (mine)
+    {
+      size_t jn = g0 == 0 ? 1 : tp / len + 1;                           // first chunk whose start lies after the previous row
+      size_t tj = jn * len;                                             // its start
+#pragma unroll
+      for (unsigned i = 0; i < R; ++i)
+      {
+        const size_t t = tfirst + (size_t)i * m;
+        if (g0 + i < rows_v)
+          for (; jn < a.chunks && tj <= t; ++jn, tj += len) out[jn * m] = pre[i];
+      }
+      if (g0 + R >= rows_v)                                             // the cell's last row: every later chunk starts behind it
+        for (; jn < a.chunks; ++jn) out[jn * m] = sum;
+    }
+  }
+}
+
 }  // namespace sdfthip

@@ -200,6 +200,7 @@ template <typename TD, typename FD> struct SelfArgs
   const cx<FD>* acc_in;       // [channels][N] accumulator before the call (ForwardArgs::acc_state receives the new one)
   unsigned log2m;             // 2N = 1 << log2m, or 0: 2N = product of rl's radices (2, 3, 4, 5), Stockham between two buffers
   unsigned lds_deltas;        // fused kernel: samples of a chunk whose differences are staged in dynamic LDS (0: formed in the loop)
+  const FD* prefix;           // [channels][chunks][2N] the folded cells of every chunk from prefix_cells_kernel; nullptr = the workgroup folds them itself
 #ifdef SDFT_SELF_STAMPS
   unsigned long long* stamps; // development build: cycle stamps of the last chunk's workgroup (scripts/self_stamps.py)
 #endif
@@ -369,7 +370,13 @@ SDFT_D cx<FD>* self_carry(const SelfArgs<TD, FD>& sa, const ForwardArgs<FD>& a, 
   const bool st_on = sa.stamps && chunk + 1 == a.chunks && threadIdx.x == 0;
   if (st_on) sa.stamps[1] = __builtin_readcyclecounter();
 #endif
-  self_fold<CP, QB>(sa, cells, m, a.cursor0, ch, t0);
+  if (sa.prefix)
+  {
+    // the cells self_fold would leave here, formed once for all chunks of the call (prefix_cells_kernel)
+    const FD* pc = sa.prefix + (ch * a.chunks + chunk) * (size_t)m;
+    for (unsigned v = threadIdx.x; v < m; v += blockDim.x) cells[v] = cmake<FD>(pc[v], (FD)0);
+  }
+  else self_fold<CP, QB>(sa, cells, m, a.cursor0, ch, t0);
   __syncthreads();
 #ifdef SDFT_SELF_STAMPS
   if (st_on) sa.stamps[2] = __builtin_readcyclecounter();

@@ -194,6 +194,8 @@ class Plan
   long opt_spin = 1;             // synchronous short calls poll the stream instead of sleeping on it
   long opt_self = 1;             // chunk-parallel FD double calls, 2N a power of two: self-carried chunks (no pre-pass launches; logic::kSelfMax)
   long last_self = 0;
+  long opt_prefix_cells = 1;     // test hook: the prefix-cell route of long calls (logic::ForwardQuery::prefix_cells)
+  long last_prefix = 0;          // the last analysis call took it (one pre-pass launch: prefix_cells_kernel)
 
   long last_kernel = 0;          // 1 = forward_kernel (independent tiles), 2 = forward_rows_kernel, 3 = hop, 4 = forward_every_kernel, 5 = forward_power_kernel, 6 = forward_pooled_power_kernel
 
@@ -236,6 +238,7 @@ class Plan
   // workspace
   DevBuf<FD> d_delta;
   DevBuf<fdx> d_carry, d_seed;
+  DevBuf<FD> d_prefix;                                     // prefix cells [channels][chunks][2N]
   DevBuf<TD> d_stage_td;
   DevBuf<fdx> d_stage_fdx;
   DevBuf<fdx*> d_rowptr;
@@ -287,7 +290,7 @@ class Plan
     d_tw.release(); d_syn.release(); d_wtab.release();
     release_pipe();
     for (int q = 0; q < 4; ++q) { d_accs[q].release(); d_fids[q].release(); d_hist[q].release(); }
-    d_delta.release(); d_carry.release(); d_seed.release();
+    d_delta.release(); d_carry.release(); d_seed.release(); d_prefix.release();
     d_stage_td.release(); d_stage_fdx.release(); d_rowptr.release(); d_fseed.release();
     d_gain.release(); d_stage_y.release(); d_chain_stats.release();
     d_alpha.release(); d_beta.release(); d_partial.release(); d_tickets.release();
@@ -573,6 +576,7 @@ class Plan
     q.rows_kernel = opt_rows_kernel; q.row_slots_max = opt_row_slots_max; q.interior = opt_interior; q.chunk = opt_chunk; q.self = opt_self;
     q.fused = opt_fused; q.fold = opt_fold; q.fft_carry = opt_fft_carry; q.hop_kernel = opt_hop_kernel; q.chain = opt_chain; q.chain_L = opt_chain_L;
     q.relay_flow = opt_relay_flow; q.segments = opt_segments; q.xcd_map = opt_xcd_map; q.rows_f32 = opt_rows_f32; q.pipeline = opt_pipeline;
+    q.prefix_cells = opt_prefix_cells;
     return q;
   }
 
@@ -590,9 +594,9 @@ class Plan
     pipe_this = r.pipelined;
     if (r.out.hi) prev_out = r.out;
     last_kernel = r.kernel; last_chunks = r.chunks; last_chunk_len = r.len; last_tiles = r.tiles; last_interior = r.interior;
-    last_segments = r.segments; last_fused = r.fused; last_self = r.self; last_chain = r.carry == logic::CARRY_RELAY ? 3 : 0;
+    last_segments = r.segments; last_fused = r.fused; last_self = r.self; last_prefix = r.prefix; last_chain = r.carry == logic::CARRY_RELAY ? 3 : 0;
     if (r.kernel == logic::FK_HOP) { if (!pipe_join()) return false; return forward_hop(n, x, x_stride, out, out_stride, rows); }
-    if (r.self) return forward_self(n, x, x_stride, out, out_stride, r.chunks, r.len, fuse);
+    if (r.self || r.prefix) return forward_self(n, x, x_stride, out, out_stride, r.chunks, r.len, fuse, r.prefix);
     if (!pipe_join()) return false;
 
     // workspace
@@ -1008,8 +1012,10 @@ class Plan
   }
 
   // ---- self-carried chunks: the whole chunk-parallel call in one launch (SelfArgs in sdft_kernels.hpp) ----
+  // prefix: the folded cells of every chunk come from one pre-pass launch (prefix_cells_kernel, logic::ForwardRoute::prefix);
+  // one stream, never fused
   bool forward_self(size_t n, const TD* x, size_t x_stride, fdx* out, size_t out_stride, long chunks, long len,
-                    const FuseArgs<TD, FD>* fuse)
+                    const FuseArgs<TD, FD>* fuse, bool prefix = false)
   {
     const size_t nb = nbins, span = 2 * nbins;
     SelfArgs<TD, FD> sa;
@@ -1020,6 +1026,7 @@ class Plan
     if ((span & (span - 1)) == 0) while (((size_t)1 << sa.log2m) < span) ++sa.log2m;
     else sa.rl = smooth_radices(span);
     sa.lds_deltas = 0;
+    sa.prefix = nullptr;
 #ifdef SDFT_SELF_STAMPS
     sa.stamps = reinterpret_cast<unsigned long long*>(opt_self_stamps);
 #endif
@@ -1093,6 +1100,23 @@ class Plan
       }
     }
     if (!pipe_join()) return false;
+    if constexpr (sizeof(FD) == 8)
+    {
+      if (prefix)
+      {
+        if (!d_prefix.reserve(channels * (size_t)chunks * span)) return false;
+        PrefixArgs<TD, FD> pa;
+        pa.x = x; pa.x_stride = x_stride; pa.hist_in = sa.hist_in; pa.prefix = d_prefix.p; pa.n = n;
+        pa.span = (unsigned)span; pa.chunks = (unsigned)chunks; pa.chunk_len = (unsigned)len; pa.cursor0 = (unsigned)cursor;
+        const size_t pblocks = ((span + kPrefixCells - 1) / kPrefixCells) * channels;
+        if (!grid_fits(pblocks)) return false;
+        if (!prof_begin(ST_CARRY)) return false;
+        hipLaunchKernelGGL((prefix_cells_kernel<TD, FD>), dim3((unsigned)pblocks), dim3(kPrefixCells * kPrefixSlices), 0, stream, pa);
+        SDFT_TRY(hipGetLastError());
+        if (!prof_end(ST_CARRY)) return false;
+        sa.prefix = d_prefix.p;
+      }
+    }
     if (!prof_begin(ST_FORWARD)) return false;
     if constexpr (sizeof(FD) == 8)
     {

@@ -605,6 +605,19 @@ inline ProcessGeometry process_geometry(size_t nbins, size_t channels, size_t n,
 // ---- analysis: the route of a call (Plan::forward_launch runs it) ------------------------------------------------------------
 constexpr int kWavesPerBlock = 4;                  // waves of a tile-kernel workgroup (kWavesPerBlock)
 constexpr int kProcGroup = 8, kProcRow = 72;       // the fused kernel's transpose tile: samples per group, row stride (kProcGroup, kProcRow)
+// (beyond kSelfMax a row-group analysis call takes the same kernel with the fold done once for all chunks by a pre-pass launch:
+// ForwardRoute::prefix; the fused call and every shape without the self-carried form keep the partial sums + scan)
+// That launch (prefix_cells_kernel) adds the n / 2N differences of a cell one after the other, on 2N / 32 workgroups per channel:
+// every 512 rows of a cell are one load phase and 32 turns of 16 dependent additions through LDS, so its time grows with the rows
+// per cell, which the partial sums + scan (parallel over the chunks, tens of microseconds whatever the length) do not.  The route
+// is therefore bounded by rows per cell, kPrefixRowsMax = 9 passes of 512 rows; beyond it the partial sums + scan stay.
+// MEASURED so far: the headline alone, 489 rows per cell, one pass: the launch takes 17 us where the partial sums + scan take 44 us
+// (profiles/prefix_cells_ab.txt).  The bound itself is REASONED from that one figure: nine passes, about
+// 5 us each, cost about what the partial sums + scan cost, and nine passes is the smallest bound under which m = 64 just beyond kSelfMax (4128
+// rows) keeps the route.  scripts/prefix_cells_rows_ab.py measures both pre-passes from 258 to 625 000 rows per cell and is what
+// should move this constant; its table has not been recorded yet.
+constexpr size_t kPrefixRowsMax = 9 * 512;
+inline size_t prefix_rows(size_t n, size_t nbins) { return (n + 2 * nbins - 1) / (2 * nbins); }   // rows per cell: the depth of prefix_cells_kernel's chain
 constexpr size_t kSelfMax = (size_t)1 << 19;       // self-carried chunks for calls of up to this many samples per channel (the fold of a chunk's past grows with n) ...
 constexpr size_t kSelfMaxFused = (size_t)1 << 16;  // ... of the fused call, which is bound by instruction issue (n = 131072: 99 -> 117 us self-carried)
 constexpr size_t kFlagMax = (size_t)1 << 24;       // bin-samples up to which a row-group analysis call signals its own completion ...
@@ -637,6 +650,7 @@ struct ForwardQuery
   // options
   long rows_kernel = 1, row_slots_max = 2, interior = 0, chunk = 0, self = 1, fused = 1, fold = 1, fft_carry = 1, hop_kernel = 1, chain = 1,
        chain_L = 0, relay_flow = 1, segments = 0, xcd_map = 1, rows_f32 = 1, pipeline = 1;
+  long prefix_cells = 1;                  // test hook: 0 = never the prefix-cell route, 1 = calls beyond kSelfMax, 2 = whatever the length
 };
 enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6 };     // = get_option "last_kernel"
 // carries: the single chunk's are the stream state (delta_kernel copies it); pre-pass partial sums + scan (carries from the
@@ -647,6 +661,7 @@ struct ForwardRoute
 {
   int kernel = FK_TILES;                  // FK_HOP: forward_hop takes the call
   bool self = false;                      // forward_self takes the call
+  bool prefix = false;                    // forward_self takes the call with the folded cells of all chunks from one pre-pass launch (prefix_cells_kernel); never with self
   bool pipelined = false;                 // ... on the two row streams (Plan::pipe_this)
   Range out;                              // the matrix of a dense row-group analysis (the next call's prev_out), else empty
   long chunks = 1, len = 0, tiles = 1, interior = 1;
@@ -728,7 +743,16 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   // instruction issue: n = 48000: 45.9 -> 42.3 us, n = 131072: 99 -> 117 us; hence kSelfMaxFused)
   // (2N = 2/3/5-smooth: five Stockham stages with table look-ups -- n = 12000, N = 1000, chunks of 64 samples: 47 us with
   // the pre-pass, 55 us self-carried; n = 48000, chunks of 192: 192 -> 173 us)
-  r.self = self_form && r.chunks > 1 && (pow2 || r.len > 64);
+  // Beyond kSelfMax (where the fold costs more than the other workgroups' stores hide) the fold is done ONCE: it is a prefix over
+  // time of one real number per cursor, which one small launch writes for all chunks (prefix_cells_kernel); the row-group kernel
+  // then reads its 2N cells instead of folding them and goes on as a self-carried chunk (FFT in LDS, own differences).  The fused
+  // and the pipelined calls keep their forms, and so does every call of more than kPrefixRowsMax rows per cell.
+  r.prefix = rows && !q.fuse && !r.pipelined && q.fd_bytes == 8 && !q.exact && q.self != 0 && self_cells(nb, q.self >= 1, q.fdx_bytes) != 0 &&
+             q.prefix_cells != 0 && ((n > kSelfMax && prefix_rows(n, nb) <= kPrefixRowsMax) || q.prefix_cells == 2) && r.chunks > 1 && (pow2 || r.len > 64);
+  // (a flag on top of the route below: Plan::forward_launch asks for it first and runs forward_self.  carry, sums, delta_in_carry,
+  // use_seed and fused go on naming the partial sums + scan the same call takes without the flag -- tests/cpp/plan_logic_test.cpp
+  // pins them for the headline and allows fused arithmetic only beside CARRY_SUMS -- and nothing reads them for a prefix call)
+  r.self = self_form && !r.prefix && r.chunks > 1 && (pow2 || r.len > 64);
   if (r.self) return r;
 
   // exact carries: relay form (seed table + identical waves that take the blocks of L steps in turn, a block's products in

@@ -184,7 +184,7 @@
     calls.on_analysis(false);
     prev_out = logic::Range{0, 0};
     hist_cur ^= 1; st_cur ^= 1;
-    last_kernel = 3; last_chunks = 1; last_chunk_len = (long)n; last_segments = 1; last_fused = 0; last_self = 0; last_chain = 0;
+    last_kernel = 3; last_chunks = 1; last_chunk_len = (long)n; last_segments = 1; last_fused = 0; last_self = 0; last_prefix = 0; last_chain = 0;
     last_hop_pipe = 1; last_hop_parts = hp.parts; last_pipelined = 0;
     if (cursor + n >= span) fid_canonical = true;
     cursor = (cursor + n) % span;
@@ -209,7 +209,7 @@
     calls.on_analysis(false);
     prev_out = logic::Range{0, 0};
     hist_cur ^= 1; st_cur ^= 1;
-    last_kernel = 3; last_chunks = 1; last_chunk_len = 1; last_segments = 1; last_fused = 0; last_self = 0; last_chain = 0;
+    last_kernel = 3; last_chunks = 1; last_chunk_len = 1; last_segments = 1; last_fused = 0; last_self = 0; last_prefix = 0; last_chain = 0;
     last_hop_pipe = 1; last_hop_parts = 1; last_pipelined = 0;
     if (cursor + 1 >= span) fid_canonical = true;
     cursor = (cursor + 1) % span;
