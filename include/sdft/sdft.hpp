@@ -36,7 +36,11 @@ const char* sdft_hip_last_error(void);
   long sdft_hip_sdft_power_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first,     \
                                    std::size_t bin0, std::size_t nbins, void* power);                                    \
   long sdft_hip_sdft_power_sum_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, \
-                                       std::size_t bin0, std::size_t nbins, void* sums);
+                                       std::size_t bin0, std::size_t nbins, void* sums);                               \
+  int sdft_hip_set_filterbank_##SUF(void* plan, std::size_t nbands, const std::size_t* band_bin0, const std::size_t* band_nbins, \
+                                    const void* weights);                                                               \
+  std::size_t sdft_hip_filterbank_bands_##SUF(const void* plan);                                                       \
+  long sdft_hip_sdft_filterbank_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, void* out);
 SDFT_HPP_DECLARE(f32f64, float)
 SDFT_HPP_DECLARE(f32f32, float)
 SDFT_HPP_DECLARE(f64f64, double)
@@ -73,6 +77,9 @@ namespace sdft
       static long sdft_every_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, void* d) { return sdft_hip_sdft_every_n_##SUF(p, n, x, e, f, d); } \
       static long sdft_power_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_power_n_##SUF(p, n, x, e, f, b, k, d); } \
       static long sdft_power_sum_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_power_sum_n_##SUF(p, n, x, e, f, b, k, d); } \
+      static int set_filterbank(void* p, std::size_t nb, const std::size_t* b0, const std::size_t* bn, const void* w) { return sdft_hip_set_filterbank_##SUF(p, nb, b0, bn, w); } \
+      static std::size_t filterbank_bands(const void* p) { return sdft_hip_filterbank_bands_##SUF(p); } \
+      static long sdft_filterbank_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, void* d) { return sdft_hip_sdft_filterbank_n_##SUF(p, n, x, e, f, d); } \
     };
     SDFT_HPP_ABI(f32f64, float, double)
     SDFT_HPP_ABI(f32f32, float, float)
@@ -191,6 +198,38 @@ namespace sdft
       {
         const char* e = sdft_hip_last_error();
         throw std::runtime_error(std::string("sdft_hip_sdft_power_sum_n: ") + (e ? e : "failed"));
+      }
+      return static_cast<std::size_t>(rows);
+    }
+
+    /**
+     * Installs (copies) a filterbank in the plan (sdft_hip_set_filterbank; host arrays): band b covers the bins
+     * band_bin0[b] <= k < band_bin0[b] + band_nbins[b] with the weights weights[off_b + (k - band_bin0[b])], off_b the sum of the
+     * band_nbins before it.  nbands == 0 removes it.
+     **/
+    void set_filterbank(const std::size_t nbands, const std::size_t* band_bin0, const std::size_t* band_nbins, const F* weights)
+    {
+      if (api::set_filterbank(plan_, nbands, band_bin0, band_nbins, weights) != 0)
+      {
+        const char* e = sdft_hip_last_error();
+        throw std::runtime_error(std::string("sdft_hip_set_filterbank: ") + (e ? e : "failed"));
+      }
+    }
+    /** Bands of the installed filterbank, 0 for none. */
+    std::size_t filterbank_bands() const { return api::filterbank_bands(plan_); }
+
+    /**
+     * Filterbank analysis (sdft_hip_sdft_filterbank_n): per band of the installed filterbank the sum of weight * power over the
+     * band's bins, for the rows power() would write for the samples first, first + every, ... < nsamples; out is dense
+     * (rows, filterbank_bands()).  The plan's state advances over all samples and all bins.  Returns the number of rows written.
+     **/
+    std::size_t filterbank(const std::size_t nsamples, const T* samples, const std::size_t every, const std::size_t first, F* const out)
+    {
+      const long rows = api::sdft_filterbank_n(plan_, nsamples, samples, every, first, out);
+      if (rows < 0)
+      {
+        const char* e = sdft_hip_last_error();
+        throw std::runtime_error(std::string("sdft_hip_sdft_filterbank_n: ") + (e ? e : "failed"));
       }
       return static_cast<std::size_t>(rows);
     }

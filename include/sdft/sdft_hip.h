@@ -221,6 +221,48 @@ long sdft_hip_sdft_power_sum_n(sdft_t* sdft, const sdft_size_t nsamples, const s
                                const sdft_size_t bin0, const sdft_size_t nbins,
                                sdft_fd_t* sums) SDFT_HIP_SYMBOL(sdft_power_sum_n);
 
+/* ---- filterbank analysis ---------------------------------------------------------------------------
+   Pooling of |X|^2 over frequency: mel, Bark and fractional-octave band energies, or the total power of a row, without storing
+   and re-reading the powers.  A filterbank belongs to the plan.  sdft_hip_set_filterbank installs (copies) one; all four pointers
+   are HOST memory.  Band b covers the bins band_bin0[b] <= k < band_bin0[b] + band_nbins[b] with the weights
+   weights[off_b + (k - band_bin0[b])], off_b = band_nbins[0] + ... + band_nbins[b - 1].  Bands may overlap, repeat, come in any
+   order and need not cover the spectrum; weights may be negative or zero.  nbands == 0 removes the filterbank.  Batched plans:
+   one filterbank for all channels.  Returns 0, or -1 with sdft_hip_last_error() set and the plan's previous filterbank untouched:
+   a NULL plan, a NULL array with nbands > 0, band_nbins[b] == 0, band_bin0[b] + band_nbins[b] > dftsize (or tables beyond 2^31
+   bands / 2^32 weights).  sdft_hip_filterbank_bands: the installed filterbank's bands, 0 for none or a NULL plan. */
+int         sdft_hip_set_filterbank(sdft_t* sdft, const sdft_size_t nbands, const sdft_size_t* band_bin0,
+                                    const sdft_size_t* band_nbins, const sdft_fd_t* weights) SDFT_HIP_SYMBOL(set_filterbank);
+sdft_size_t sdft_hip_filterbank_bands(const sdft_t* sdft) SDFT_HIP_SYMBOL(filterbank_bands);
+/* sdft_hip_sdft_filterbank_n writes the band sums of the installed filterbank on the row grid of sdft_hip_sdft_every_n and
+   sdft_hip_sdft_power_n: grid, rows, streaming and the next call's first are exactly theirs.  Let p[r][k] be what
+   sdft_hip_sdft_power_n stores for row r and bin k.  Then
+     out[r][b] = sum over the band's bins of fl(w * p)
+   formed in sdft_fd_t: each product is rounded once, then the rounded products are added (no fused multiply-add anywhere).
+   out is [rows][nbands] real numbers, dense, aligned to sizeof(sdft_fd_t) only; batched plans: samples [channels][nsamples], out
+   [channels][rows][nbands].  samples and out may each be host or device memory (option "async" applies to device pointers); out
+   may be NULL when the call keeps no row.
+   Order of additions: the order inside a band is the library's own (a band's bins are added in ascending order inside a tile of
+   bins, then the tiles' sums in ascending order).  Three things are promised.  (1) The same plan, options and input give the same
+   bits on every run: no floating-point atomics.  (2) A row's bits depend only on the plan, the filterbank and that row's powers --
+   not on nsamples, every, first, the time chunking, or where a stream was cut into calls.  (3) A band of one bin is exactly
+   fl(w p), a band of two bins exactly fl(fl(w0 p0) + fl(w1 p1)): a filterbank of dftsize one-bin bands of weight 1 returns
+   sdft_hip_sdft_power_n's values bit for bit on every route.
+   Accuracy: with L the band's bin count, u = 2^-24 (float) or 2^-53 (double), gamma_n = n u / (1 - n u), eta the smallest positive
+   subnormal of sdft_fd_t and T = sum |w_k| p_k in the reals:  |out - sum w_k p_k| <= gamma_L T + L eta, element by element (L
+   rounded products and at most L - 1 additions, in any order), where p is the reference's wherever sdft_sdft_n is bit-identical
+   to it (FD float, FD double with option "carry" = 1, calls shorter than 512 samples); elsewhere the term deviation of
+   sdft_hip_sdft_power_n comes on top: 2.1e-11 of the largest power of the call's grid, times sum |w_k|.
+   Bands that a tile boundary of the plan's geometry cuts pass through a plan-owned workspace of [channels][rows][pieces] numbers,
+   grown on demand; a call whose workspace would exceed 64 MiB runs its time chunks in row segments (several launches that reuse
+   the workspace), with the same bits and the same state.
+   The stream state afterwards is the one sdft_sdft_n of the same samples leaves, so any other entry point may follow.  The call
+   is never resident, pipelined or fused and always runs its own kernel ("last_kernel" = 7).  Returns the number of rows written
+   (0 for nsamples == 0), or -1 with sdft_hip_last_error() set and the stream state untouched: a NULL plan, no filterbank
+   installed, every == 0, or out == NULL with rows > 0. */
+long sdft_hip_sdft_filterbank_n(sdft_t* sdft, const sdft_size_t nsamples, const sdft_td_t* samples,
+                                const sdft_size_t every, const sdft_size_t first,
+                                sdft_fd_t* out) SDFT_HIP_SYMBOL(sdft_filterbank_n);
+
 /* ---- streams ---------------------------------------------------------------------------------
    Every plan owns a HIP stream.  Calls with host pointers always return with the output
    complete.  Calls with device pointers do too unless option "async" is 1; then they return after

@@ -108,6 +108,21 @@ long SDFT_FN(sdft_power_sum_n)(void* p, size_t n, const SDFT_TD* x, size_t every
   if (rows > (size_t)LONG_MAX) { sdfthip::set_error("sdft_hip_sdft_power_sum_n", "more rows than a long can count"); return -1; }
   return (long)rows;
 }
+// filterbank analysis: weighted band sums of those powers on the grid; see sdft_hip.h
+int SDFT_FN(set_filterbank)(void* p, size_t nbands, const size_t* band_bin0, const size_t* band_nbins, const SDFT_FD* weights)
+{
+  if (!p) { sdfthip::set_error("sdft_hip_set_filterbank", "NULL plan"); return -1; }
+  return P(p)->set_filterbank(nbands, band_bin0, band_nbins, weights) ? 0 : -1;
+}
+size_t SDFT_FN(filterbank_bands)(const void* p) { return p ? P(p)->filterbank_bands() : 0; }
+long SDFT_FN(sdft_filterbank_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, SDFT_FD* out)
+{
+  if (!p) { sdfthip::set_error("sdft_hip_sdft_filterbank_n", "NULL plan"); return -1; }
+  size_t rows = 0;
+  if (!P(p)->sdft_filterbank_n(n, x, every, first, out, rows)) return -1;
+  if (rows > (size_t)LONG_MAX) { sdfthip::set_error("sdft_hip_sdft_filterbank_n", "more rows than a long can count"); return -1; }
+  return (long)rows;
+}
 int SDFT_FN(set_stream)(void* p, void* hip_stream) { return p && P(p)->set_stream(static_cast<hipStream_t>(hip_stream)) ? 0 : -1; }
 // (a host that asks for the stream may queue work of its own behind a call: from here on every kernel of the plan is on it)
 void* SDFT_FN(get_stream)(void* p)

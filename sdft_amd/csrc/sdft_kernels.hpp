@@ -16,6 +16,9 @@
 //   sdft_forward_power_sum.hpp K1s forward_pooled_power_kernel: that power at every sample, summed in registers over the windows of the
 //                          grid, one store per window; pooled_power_rows_kernel adds the pieces of the windows a chunk boundary cuts
 //                          (sdft_hip_sdft_power_sum_n)
+//   sdft_forward_filterbank.hpp K1f forward_filterbank_kernel: the powers of a kept row go to a wave-private strip of LDS and the lanes
+//                          form the weighted sums of the pieces of the plan's bands that lie in the tile; filterbank_rows_kernel adds
+//                          the pieces of the bands a tile boundary cuts (sdft_hip_sdft_filterbank_n)
 //   sdft_forward_hop.hpp   K1h   calls of one time chunk: forward_hop_kernel, forward_hop2_kernel (two waves per tile)
 //   sdft_ops.hpp           spectral operations of the fused call, the synthesis term (sdft.h:641-651), user_rows_kernel
 //   sdft_forward_rows.hpp  K1    forward_rows_kernel: one workgroup per (chunk, row), LDS edge exchange, lockstep row
@@ -48,6 +51,7 @@
 #include "sdft_forward_every.hpp"
 #include "sdft_forward_power.hpp"
 #include "sdft_forward_power_sum.hpp"
+#include "sdft_forward_filterbank.hpp"
 #include "sdft_forward_hop.hpp"
 #include "sdft_ops.hpp"
 #include "sdft_forward_rows.hpp"

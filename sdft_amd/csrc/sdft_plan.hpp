@@ -95,6 +95,8 @@ static_assert(logic::kLanes == kWave && logic::kRowWaves == kRowWavesMax && logi
 static_assert(logic::kWindowHann == WIN_HANN && logic::kWindowBlackman == WIN_BLACKMAN && logic::kWindowBoxcar == WIN_BOXCAR, "window numbering");
 static_assert(logic::kWavesPerBlock == kWavesPerBlock && logic::kProcGroup == kProcGroup && logic::kProcRow == kProcRow, "sdft_plan_logic.hpp and the kernels disagree");
 static_assert(sizeof(logic::Radices) == sizeof(RadixList), "radix lists");
+static_assert(sizeof(logic::FilterbankPiece) == sizeof(FilterbankPiece) && sizeof(logic::FilterbankSplit) == sizeof(FilterbankSplit) &&
+              logic::kFilterbankToWorkspace == kFilterbankToWorkspace, "filterbank tables");
 
 enum CarryMode : int { CARRY_FAST = 0, CARRY_EXACT = 1 };
 
@@ -197,7 +199,7 @@ class Plan
   long opt_prefix_cells = 1;     // test hook: the prefix-cell route of long calls (logic::ForwardQuery::prefix_cells)
   long last_prefix = 0;          // the last analysis call took it (one pre-pass launch: prefix_cells_kernel)
 
-  long last_kernel = 0;          // 1 = forward_kernel (independent tiles), 2 = forward_rows_kernel, 3 = hop, 4 = forward_every_kernel, 5 = forward_power_kernel, 6 = forward_pooled_power_kernel
+  long last_kernel = 0;          // 1 = forward_kernel (independent tiles), 2 = forward_rows_kernel, 3 = hop, 4 = forward_every_kernel, 5 = forward_power_kernel, 6 = forward_pooled_power_kernel, 7 = forward_filterbank_kernel
 
   // device-resident stream state
   DevBuf<fdx> d_tw, d_syn, d_wtab;
@@ -243,6 +245,19 @@ class Plan
   DevBuf<fdx> d_stage_fdx;
   DevBuf<fdx*> d_rowptr;
   DevBuf<FD> d_psum_ws, d_psum_head;                       // pooled power analysis: pieces of cut windows [channels][chunks][2][band]; a segment's head row
+  // filterbank analysis: the installed filterbank (sdft_hip_set_filterbank) as the host gave it, its decomposition for the plan's
+  // tiles (logic::filterbank_layout), the device copies the kernels read, and the workspace of split bands [channels][rows][slots]
+  struct Filterbank
+  {
+    std::vector<size_t> bin0, nbins;
+    std::vector<FD> weights;
+    logic::FilterbankLayout layout;
+    long interior = -1;                                      // option "interior" the layout was made for
+  } fbank;
+  DevBuf<FilterbankPiece> d_fb_pieces;
+  DevBuf<unsigned> d_fb_tile0;
+  DevBuf<FilterbankSplit> d_fb_splits;
+  DevBuf<FD> d_fb_weights, d_fb_ws;
 
   // profile: HIP events on the plan's stream, one pair per stage launch, collected lazily so
   // that back-to-back asynchronous calls are never serialised by the measurement
@@ -292,6 +307,8 @@ class Plan
     for (int q = 0; q < 4; ++q) { d_accs[q].release(); d_fids[q].release(); d_hist[q].release(); }
     d_delta.release(); d_carry.release(); d_seed.release(); d_prefix.release();
     d_stage_td.release(); d_stage_fdx.release(); d_rowptr.release(); d_fseed.release();
+    d_psum_ws.release(); d_psum_head.release();
+    d_fb_pieces.release(); d_fb_tile0.release(); d_fb_splits.release(); d_fb_weights.release(); d_fb_ws.release();
     d_gain.release(); d_stage_y.release(); d_chain_stats.release();
     d_alpha.release(); d_beta.release(); d_partial.release(); d_tickets.release();
     if (h_done_flag) { (void)hipHostFree(h_done_flag); h_done_flag = nullptr; }
@@ -530,13 +547,14 @@ class Plan
   // every: decimated analysis (sdft_every_n) -- only the rows of that grid are stored, by forward_every_kernel
   // power: power-spectrogram analysis (sdft_power_n) -- forward_power_kernel stores |X|^2 of its band on its grid (out is unused)
   // psum: pooled power analysis (sdft_power_sum_n) -- forward_pooled_power_kernel sums it over the grid's windows (out is unused)
+  // fbk: filterbank analysis (sdft_filterbank_n) -- forward_filterbank_kernel stores the band sums of the plan's filterbank (out is unused)
   bool forward_device(size_t n, const TD* x, size_t x_stride, fdx* out, size_t out_stride, fdx* const* rows,
                       const FuseArgs<TD, FD>* fuse = nullptr, const EveryGrid* every = nullptr, const PowerArgs<FD>* power = nullptr,
-                      const PowerSumArgs<FD>* psum = nullptr)
+                      const PowerSumArgs<FD>* psum = nullptr, const FilterbankArgs<FD>* fbk = nullptr)
   {
     const struct { size_t cursor; int st_cur, hist_cur; bool fid_canonical; } was{cursor, st_cur, hist_cur, fid_canonical};
     auto restore = [&] { cursor = was.cursor; st_cur = was.st_cur; hist_cur = was.hist_cur; fid_canonical = was.fid_canonical; };
-    if (!forward_launch(n, x, x_stride, out, out_stride, rows, fuse, every, power, psum))
+    if (!forward_launch(n, x, x_stride, out, out_stride, rows, fuse, every, power, psum, fbk))
     {
       // a launch that failed half-way (a host expression that does not compile, a grid that does not fit, an allocation)
       // must not leave the stream half-advanced: what was queued wrote the OTHER buffer set and the workspace only
@@ -550,7 +568,7 @@ class Plan
     restore();
     const long saved = opt_chain;
     opt_chain = 0;
-    const bool ok = forward_launch(n, x, x_stride, out, out_stride, rows, fuse, every, power, psum) && (hipStreamSynchronize(stream) == hipSuccess);
+    const bool ok = forward_launch(n, x, x_stride, out, out_stride, rows, fuse, every, power, psum, fbk) && (hipStreamSynchronize(stream) == hipSuccess);
     opt_chain = saved;
     ++ring_recoveries;
     // a recovered call is a valid call: it goes to the warning channel (and the counter), not to the error channel, so a
@@ -565,13 +583,13 @@ class Plan
   }
 
   logic::ForwardQuery forward_query(size_t n, const fdx* out, size_t out_stride, fdx* const* rows, const FuseArgs<TD, FD>* fuse, const EveryGrid* every,
-                                   const PowerArgs<FD>* power, const PowerSumArgs<FD>* psum) const
+                                   const PowerArgs<FD>* power, const PowerSumArgs<FD>* psum, const FilterbankArgs<FD>* fbk) const
   {
     logic::ForwardQuery q;
     q.n = n; q.nbins = nbins; q.channels = channels; q.fd_bytes = sizeof(FD); q.fdx_bytes = sizeof(fdx);
     q.window = window; q.compute_units = compute_units; q.cursor = cursor; q.exact = carry_mode == CARRY_EXACT; q.fid_canonical = fid_canonical;
     q.fuse = fuse != nullptr; q.fuse_store = fuse && fuse->store; q.reference_order = fuse && wants_reference_order(); q.coeff_ready = coeff_ready;
-    q.every = every != nullptr; q.power = power != nullptr; q.power_every = power ? (size_t)power->every : 1; q.power_sum = psum != nullptr; q.row_pointers = rows != nullptr; q.out = reinterpret_cast<uintptr_t>(out); q.out_stride = out_stride;
+    q.every = every != nullptr; q.power = power != nullptr; q.power_every = power ? (size_t)power->every : fbk ? (size_t)fbk->every : 1; q.power_sum = psum != nullptr; q.filterbank = fbk != nullptr; q.row_pointers = rows != nullptr; q.out = reinterpret_cast<uintptr_t>(out); q.out_stride = out_stride;
     q.analysis_batch = calls.analysis_batch; q.pipe_wanted = pipe_wanted(nullptr); q.prev_out = prev_out;
     q.rows_kernel = opt_rows_kernel; q.row_slots_max = opt_row_slots_max; q.interior = opt_interior; q.chunk = opt_chunk; q.self = opt_self;
     q.fused = opt_fused; q.fold = opt_fold; q.fft_carry = opt_fft_carry; q.hop_kernel = opt_hop_kernel; q.chain = opt_chain; q.chain_L = opt_chain_L;
@@ -584,13 +602,13 @@ class Plan
   // other route as delta -> carries -> forward
   bool forward_launch(size_t n, const TD* x, size_t x_stride, fdx* out, size_t out_stride, fdx* const* rows,
                       const FuseArgs<TD, FD>* fuse = nullptr, const EveryGrid* every = nullptr, const PowerArgs<FD>* power = nullptr,
-                      const PowerSumArgs<FD>* psum = nullptr)
+                      const PowerSumArgs<FD>* psum = nullptr, const FilterbankArgs<FD>* fbk = nullptr)
   {
     if (n == 0 || nbins == 0) return true;
     SDFT_TRY(hipSetDevice(device));
     flag_pending = false;                                    // only the hop kernel signals its completion
     calls.on_analysis(fuse != nullptr);                      // (which kind of host is calling: logic::CallPattern)
-    const logic::ForwardRoute r = logic::forward_route(forward_query(n, out, out_stride, rows, fuse, every, power, psum), [this] { return gate_ok(); });
+    const logic::ForwardRoute r = logic::forward_route(forward_query(n, out, out_stride, rows, fuse, every, power, psum, fbk), [this] { return gate_ok(); });
     pipe_this = r.pipelined;
     if (r.out.hi) prev_out = r.out;
     last_kernel = r.kernel; last_chunks = r.chunks; last_chunk_len = r.len; last_tiles = r.tiles; last_interior = r.interior;
@@ -619,7 +637,7 @@ class Plan
     }
 
     DeltaIn<TD, FD> din;
-    if (!forward_delta(r, n, x, x_stride, din) || !forward_carries(r, n, din) || !forward_rows_stage(r, n, out, out_stride, rows, fuse, every, power, psum)) return false;
+    if (!forward_delta(r, n, x, x_stride, din) || !forward_carries(r, n, din) || !forward_rows_stage(r, n, out, out_stride, rows, fuse, every, power, psum, fbk)) return false;
 
     // fid stays on the canonical rotation sequence unless this call seeded chunks from the closed-form
     // table; a call that crosses the roll-over with serial fid arithmetic puts it back
@@ -775,7 +793,8 @@ class Plan
   // K1: the rows, one launch per time segment (the new state goes to the other buffer set: the one a call started from survives
   // it, see forward_device)
   bool forward_rows_stage(const logic::ForwardRoute& r, size_t n, fdx* out, size_t out_stride, fdx* const* rows,
-                          const FuseArgs<TD, FD>* fuse, const EveryGrid* every, const PowerArgs<FD>* power, const PowerSumArgs<FD>* psum)
+                          const FuseArgs<TD, FD>* fuse, const EveryGrid* every, const PowerArgs<FD>* power, const PowerSumArgs<FD>* psum,
+                          const FilterbankArgs<FD>* fbk)
   {
     const size_t nb = nbins;
     const long chunks = r.chunks, segments = r.segments;
@@ -786,6 +805,23 @@ class Plan
       ps = *psum;
       if (!d_psum_ws.reserve(logic::power_sum_workspace(channels, (size_t)chunks, ps.nbins_out))) return false;
       ps.ws = chunks > 1 ? d_psum_ws.p : nullptr;
+    }
+    // filterbank analysis: the workspace of the bands a tile boundary cuts, [channels][rows of a launch][slots] (likewise); the
+    // chunks go in launches whose rows keep it within its bound (logic::filterbank_next_span)
+    FilterbankArgs<FD> fb{};
+    const size_t fb_rows = fbk ? logic::filterbank_segment_rows(channels, fbk->nslots, sizeof(FD)) : 0;
+    if (fbk)
+    {
+      fb = *fbk;
+      size_t most = 0;
+      for (long sg = 0; sg < segments && fb.nslots; ++sg)
+        for (long ja = chunks * sg / segments, j1 = chunks * (sg + 1) / segments; ja < j1;)
+        {
+          const logic::FilterbankSpan sp = logic::filterbank_next_span(ja, j1, r.len, r.shift, n, (size_t)fb.every, (size_t)fb.first, fb_rows);
+          most = std::max(most, sp.rows); ja = sp.jb;
+        }
+      if (!d_fb_ws.reserve(logic::filterbank_workspace(channels, most, fb.nslots))) return false;
+      fb.ws = d_fb_ws.p;
     }
     if (!prof_begin(ST_FORWARD)) return false;
     ForwardArgs<FD> fa{};
@@ -830,6 +866,24 @@ class Plan
         else if (!launch_syn(fa, *fuse, (unsigned)groups, threads, r.fused && !exact_order, exact_order)) return false;
       }
       else if (r.kernel == logic::FK_ROWS) launch_forward_rows(fa, (unsigned)groups, threads, r.fused, r.rows_f32);
+      else if (fbk)
+      {
+        for (long ja = j0; ja < j1;)
+        {
+          const logic::FilterbankSpan sp = logic::filterbank_next_span(ja, j1, r.len, r.shift, n, (size_t)fb.every, (size_t)fb.first, fb_rows);
+          const size_t span_groups = channels * (size_t)(sp.jb - sp.ja);
+          fa.chunk0 = (unsigned)sp.ja; fa.launch_chunks = (unsigned)(sp.jb - sp.ja); fa.inv_chunks = inv32(fa.launch_chunks);
+          fa.xcd_map = logic::xcd_groups(r.xcd_map, span_groups);
+          fa.total_waves = (unsigned long long)span_groups * (unsigned long long)r.tiles;
+          const unsigned long long span_blocks = (fa.total_waves + kWavesPerBlock - 1) / kWavesPerBlock;
+          if (!grid_fits(span_blocks)) return false;
+          fb.ws_row0 = sp.row0; fb.ws_rows = sp.rows;
+          launch_forward_filterbank(fa, fb, (unsigned)span_blocks);
+          SDFT_TRY(hipGetLastError());
+          if (fb.nsplits && sp.rows && !launch_filterbank_rows(fb)) return false;   // the split bands of these rows, before the next launch reuses the workspace
+          ja = sp.jb;
+        }
+      }
       else if (psum) { if (!grid_fits(blocks)) return false; launch_forward_power_sum(fa, ps, (unsigned)blocks); }
       else if (power) { if (!grid_fits(blocks)) return false; launch_forward_power(fa, *power, (unsigned)blocks); }
       else if (every) { if (!grid_fits(blocks)) return false; launch_forward_every(fa, *every, (unsigned)blocks); }

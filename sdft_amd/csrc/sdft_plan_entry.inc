@@ -191,6 +191,101 @@
     });
   }
 
+  // ---- filterbank analysis ---------------------------------------------------------------------------------------------
+  // the decomposition of a filterbank for the plan's tiles and its device copies (through the plan's pinned slots, after whatever
+  // still reads the old tables has drained)
+  bool upload_filterbank(Filterbank& f)
+  {
+    f.layout = logic::filterbank_layout(tiles(), interior_lanes(), bins_per_lane(), f.bin0.size(), f.bin0.data(), f.nbins.data());
+    const logic::FilterbankLayout& l = f.layout;
+    if (!d_fb_pieces.reserve(l.pieces.size()) || !d_fb_tile0.reserve(l.tile_piece0.size()) || !d_fb_splits.reserve(l.splits.size()) ||
+        !d_fb_weights.reserve(f.weights.size())) return false;
+    std::vector<FD> tile_ordered(f.weights.size());          // the weights piece after piece (FilterbankPiece::woff)
+    for (size_t i = 0; i < l.pieces.size(); ++i) std::copy_n(f.weights.data() + l.wsrc[i], l.pieces[i].nbins, tile_ordered.data() + l.pieces[i].woff);
+    SDFT_TRY(hipStreamSynchronize(stream));
+    if (!to_device(d_fb_pieces.p, l.pieces.data(), l.pieces.size() * sizeof(FilterbankPiece)) ||
+        !to_device(d_fb_tile0.p, l.tile_piece0.data(), l.tile_piece0.size() * sizeof(unsigned)) ||
+        !to_device(d_fb_splits.p, l.splits.data(), l.splits.size() * sizeof(FilterbankSplit)) ||
+        !to_device(d_fb_weights.p, tile_ordered.data(), tile_ordered.size() * sizeof(FD))) return false;
+    SDFT_TRY(hipStreamSynchronize(stream));
+    f.interior = interior_lanes();
+    return true;
+  }
+  // sdft_hip_set_filterbank: the arrays are host memory and are copied; a refused filterbank leaves the installed one as it is
+  bool set_filterbank(size_t nbands, const size_t* band_bin0, const size_t* band_nbins, const FD* weights)
+  {
+    static const char* fn = "sdft_hip_set_filterbank";
+    switch (logic::filterbank_check(nbins, nbands, band_bin0, band_nbins, weights != nullptr))
+    {
+      case logic::FB_OK: break;
+      case logic::FB_NULL: set_error(fn, "band_bin0, band_nbins or weights is NULL but nbands is not 0"); return false;
+      case logic::FB_EMPTY_BAND: set_error(fn, "a band has no bins (band_nbins[b] == 0)"); return false;
+      case logic::FB_PAST_END: set_error(fn, "a band does not lie within the plan's bins (band_bin0[b] + band_nbins[b] > dftsize)"); return false;
+      default: set_error(fn, "the filterbank is too large: 2^31 bands or 2^32 weights"); return false;
+    }
+    if (!bind()) return false;
+    if (!pipe_join()) return false;
+    Filterbank f;
+    if (nbands)
+    {
+      f.bin0.assign(band_bin0, band_bin0 + nbands);
+      f.nbins.assign(band_nbins, band_nbins + nbands);
+      f.weights.assign(weights, weights + logic::filterbank_weights(nbands, band_nbins));
+      if (!upload_filterbank(f)) { fbank.interior = -1; return false; }      // (the device tables are rebuilt from fbank by its next call)
+    }
+    else SDFT_TRY(hipStreamSynchronize(stream));
+    fbank = std::move(f);
+    return true;
+  }
+  size_t filterbank_bands() const { return fbank.bin0.size(); }
+
+  // filterbank analysis (sdft_hip_sdft_filterbank_n): per band of the installed filterbank the sum of fl(weight * power) over the
+  // band's bins, of the rows of sdft_power_n's grid, dense [channels][rows][nbands] real numbers; state, pointers and launches as
+  // sdft_power_n: never resident, pipelined or fused, forward_filterbank_kernel on the plan's stream, then filterbank_rows_kernel
+  // for the bands a tile boundary cuts (forward_rows_stage: in as many launches as keep the workspace within its bound).  Host
+  // memory goes in time segments through device scratch.
+  bool sdft_filterbank_n(size_t n, const TD* x, size_t every, size_t first, FD* out, size_t& rows)
+  {
+    static const char* fn = "sdft_hip_sdft_filterbank_n";
+    rows = 0;
+    const size_t nbands = filterbank_bands();
+    if (nbands == 0) { set_error(fn, "no filterbank is installed (sdft_hip_set_filterbank)"); return false; }
+    if (every == 0) { set_error(fn, "every must be at least 1"); return false; }
+    rows = logic::every_rows(n, every, first);
+    if (rows > 0 && !out) { set_error(fn, "out is NULL but the call keeps rows"); return false; }
+    if (n == 0) return true;
+    if (!bind()) return false;
+    if (!pipe_join()) return false;
+    if (fbank.interior != interior_lanes() && !upload_filterbank(fbank)) { fbank.interior = -1; return false; }   // (option "interior" changed the tiles)
+    if (every > n) every = n;                                // (the same grid: at most one row; keeps first + k * every in range)
+    const bool xd = on_device(x);
+    const bool od = rows == 0 || on_device(out);
+    const size_t row_bytes = channels * nbands * sizeof(FD);
+    const logic::FilterbankLayout& l = fbank.layout;
+    auto bank = [&](FD* to, size_t out_rows, size_t f) {
+      return FilterbankArgs<FD>{to, out_rows * nbands, nullptr, 0, 0, (unsigned long long)every, (unsigned long long)f, d_fb_pieces.p, d_fb_tile0.p,
+                                d_fb_weights.p, d_fb_splits.p, (unsigned)nbands, (unsigned)l.nslots, (unsigned)l.splits.size()};
+    };
+    if (xd && od)
+    {
+      const FilterbankArgs<FD> g = bank(out, rows, first);
+      return forward_device(n, x, n, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &g) && finish(rows * row_bytes);
+    }
+    // host memory: segments of at most seg samples (rows kept and samples within stage_bytes), each one call on device scratch
+    size_t seg = n;
+    if (!od) seg = std::min(seg, logic::stage_rows(n, row_bytes, stage_bytes) * every);
+    if (!xd) seg = std::min(seg, std::max<size_t>((size_t)logic::kHopSamples, logic::stage_rows(n, channels * sizeof(TD), stage_bytes)));
+    return staged_segments(n, seg, StagedCall{true, const_cast<TD*>(x), !xd, out, !od, rows, (seg + every - 1) / every, nbands * sizeof(FD)}, [&](Segment& s) {
+      const size_t f = logic::every_first_from(s.t, every, first);
+      s.rows = logic::every_rows(s.m, every, f);
+      s.row0 = s.rows ? (s.t + f - first) / every : 0;       // the segment's first row in the call's grid
+      if (od) s.mat = s.rows ? out + s.row0 * nbands : nullptr;
+      else s.mat_rows = s.rows;
+      const FilterbankArgs<FD> g = bank(static_cast<FD*>(s.mat), s.mat_rows, f);
+      return forward_device(s.m, s.td, s.td_stride, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &g);
+    });
+  }
+
   // array-of-row-pointers variant (sdft.h:622-628).  Single-channel plans only: the reference's
   // table has one pointer per sample, a batched layout for it is not defined.
   bool single_channel(const char* fn)

@@ -333,6 +333,27 @@
       default:           hipLaunchKernelGGL((forward_pooled_power_kernel<FD, BPL, WIN_BOXCAR>), gr, b, 0, stream, fa, g); break;
     }
   }
+  void launch_forward_filterbank(const ForwardArgs<FD>& fa, const FilterbankArgs<FD>& g, unsigned blocks)
+  {
+    constexpr int BPL = sizeof(fdx) == 16 ? 1 : 2;
+    const dim3 gr(blocks), b(kBlock);
+    switch (window)
+    {
+      case WIN_HANN:     hipLaunchKernelGGL((forward_filterbank_kernel<FD, BPL, WIN_HANN>), gr, b, 0, stream, fa, g); break;
+      case WIN_HAMMING:  hipLaunchKernelGGL((forward_filterbank_kernel<FD, BPL, WIN_HAMMING>), gr, b, 0, stream, fa, g); break;
+      case WIN_BLACKMAN: hipLaunchKernelGGL((forward_filterbank_kernel<FD, BPL, WIN_BLACKMAN>), gr, b, 0, stream, fa, g); break;
+      default:           hipLaunchKernelGGL((forward_filterbank_kernel<FD, BPL, WIN_BOXCAR>), gr, b, 0, stream, fa, g); break;
+    }
+  }
+  // the bands a tile boundary cuts, from their pieces in the workspace: one thread per (channel, row of the launch, split band)
+  bool launch_filterbank_rows(const FilterbankArgs<FD>& g)
+  {
+    const unsigned long long threads = (unsigned long long)channels * (unsigned long long)g.ws_rows * g.nsplits;
+    const unsigned long long blocks = (threads + kBlock - 1) / kBlock;
+    if (!grid_fits(blocks)) return false;
+    hipLaunchKernelGGL((filterbank_rows_kernel<FD>), dim3((unsigned)blocks), dim3(kBlock), 0, stream, g, (unsigned)channels);
+    return true;
+  }
   // the rows of the windows a chunk boundary cuts, from their pieces in the workspace (chunks > 1)
   bool launch_power_sum_rows(const PowerSumArgs<FD>& g, size_t n, long chunks, long len, long shift)
   {

@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <vector>
 
 namespace sdfthip {
 namespace logic {
@@ -295,6 +296,127 @@ inline PowerSumRowChunks power_sum_row_chunks(const PowerSumWindow& w, long len,
 // every = 100 1.520 against 1.566 / 1.508 / 1.537 / 1.658 / 1.850 / 2.348 ms, every = n (one window over all chunks: 863 pieces per
 // bin for pooled_power_rows_kernel) 1.495 against 1.712 / 1.577 / 1.556 / 1.637 / 1.845 / 2.343 ms (profiles/power_sum_rates.txt).
 inline Chunking choose_power_sum_chunks(const EveryQuery& q) { return choose_power_chunks(q, 1); }
+
+// ---- filterbank analysis (sdft_hip_sdft_filterbank_n) --------------------------------------------------------------------------
+// Band b of a filterbank covers the bins [band_bin0[b], band_bin0[b] + band_nbins[b]) with one weight per bin; row r of the output
+// holds, per band, the sum of fl(weight * power) over the band's bins, the powers those sdft_hip_sdft_power_n stores for the row.
+// Bands may overlap, repeat and come in any order.  What is refused: a band without bins, a band that ends past the plan's bins
+// (no overflow of bin0 + nbins), and a filterbank whose tables would not fit the 32-bit fields of a piece.
+enum FilterbankCheck : int { FB_OK = 0, FB_NULL = 1, FB_EMPTY_BAND = 2, FB_PAST_END = 3, FB_TOO_LARGE = 4 };
+constexpr size_t kFilterbankMaxBands = (size_t)1 << 31;       // a piece's destination: 31 bits of band or slot, one flag
+constexpr size_t kFilterbankMaxWeights = ((size_t)1 << 32) - 1;
+inline int filterbank_check(size_t nbins, size_t nbands, const size_t* band_bin0, const size_t* band_nbins, bool weights_given)
+{
+  if (nbands == 0) return FB_OK;                            // (removes the filterbank)
+  if (!band_bin0 || !band_nbins || !weights_given) return FB_NULL;
+  if (nbands >= kFilterbankMaxBands) return FB_TOO_LARGE;
+  size_t total = 0;
+  for (size_t b = 0; b < nbands; ++b)
+  {
+    if (band_nbins[b] == 0) return FB_EMPTY_BAND;
+    if (band_bin0[b] > nbins || band_nbins[b] > nbins - band_bin0[b]) return FB_PAST_END;
+    if (band_nbins[b] > kFilterbankMaxWeights - total) return FB_TOO_LARGE;
+    total += band_nbins[b];
+  }
+  return FB_OK;
+}
+// weights of the bands before band b (the offset of its first weight) are a running sum; all of them:
+inline size_t filterbank_weights(size_t nbands, const size_t* band_nbins)
+{
+  size_t total = 0;
+  for (size_t b = 0; b < nbands; ++b) total += band_nbins[b];
+  return total;
+}
+// The independent-tile geometry gives tile t the bins [t * per, min((t + 1) * per, nbins)), per = interior lanes x bins per lane,
+// and one wave; waves share no workgroup.  So every band is cut at the tile boundaries into PIECES, once per filterbank: a piece is
+// the bins of one band inside one tile.  The wave of the tile forms the weighted sum of each of its pieces in ascending bin order.
+// A band inside one tile has one piece, which is the band's value and goes straight to the output (dst = the band).  A band that
+// crosses a boundary is SPLIT: its pieces get consecutive workspace slots in ascending tile order (dst = kFilterbankToWorkspace |
+// slot) and filterbank_rows_kernel adds them in that order.  Neither order depends on the call, so a row's bits depend only on
+// the plan, the filterbank and the row's powers.
+constexpr uint32_t kFilterbankToWorkspace = 0x80000000u;
+struct FilterbankPiece { uint32_t bin0, nbins, woff, dst; };      // bins [bin0, bin0 + nbins), weights from woff on in TILE order:
+                                                                  // the pieces' weights one after the other as the pieces are sorted, so
+                                                                  // that a tile's weights are one range (the kernel keeps its start in LDS)
+struct FilterbankSplit { uint32_t band, slot0, pieces; };         // a split band: slots slot0 ... slot0 + pieces - 1
+struct FilterbankLayout
+{
+  size_t nbands = 0, nslots = 0;                            // nslots: workspace slots per row and channel
+  std::vector<FilterbankPiece> pieces;                      // sorted by tile, in band order inside a tile
+  std::vector<size_t> wsrc;                                 // per piece: its first weight in the caller's band-ordered array
+  std::vector<uint32_t> tile_piece0;                        // [tiles + 1]: tile t forms pieces[tile_piece0[t] ... tile_piece0[t + 1])
+  std::vector<FilterbankSplit> splits;                      // in band order
+};
+// (of a filterbank filterbank_check has passed)
+inline FilterbankLayout filterbank_layout(long tiles, long interior, int bins_per_lane, size_t nbands, const size_t* band_bin0, const size_t* band_nbins)
+{
+  FilterbankLayout l;
+  l.nbands = nbands;
+  const size_t per = (size_t)interior * (size_t)bins_per_lane, nt = (size_t)std::max(tiles, 1L);
+  std::vector<size_t> count(nt + 1, 0);
+  for (size_t b = 0; b < nbands; ++b)
+    for (size_t t = band_bin0[b] / per; t <= (band_bin0[b] + band_nbins[b] - 1) / per; ++t) ++count[t + 1];
+  for (size_t t = 0; t < nt; ++t) count[t + 1] += count[t];
+  l.tile_piece0.resize(nt + 1);
+  for (size_t t = 0; t <= nt; ++t) l.tile_piece0[t] = (uint32_t)count[t];
+  l.pieces.resize(count[nt]);
+  l.wsrc.resize(count[nt]);
+  size_t woff = 0;
+  for (size_t b = 0; b < nbands; ++b)
+  {
+    const size_t lo = band_bin0[b], hi = lo + band_nbins[b], t0 = lo / per, t1 = (hi - 1) / per;
+    const size_t slot0 = l.nslots;
+    if (t1 > t0)
+    {
+      l.splits.push_back(FilterbankSplit{(uint32_t)b, (uint32_t)slot0, (uint32_t)(t1 - t0 + 1)});
+      l.nslots += t1 - t0 + 1;
+    }
+    for (size_t t = t0; t <= t1; ++t)
+    {
+      const size_t p0 = std::max(lo, t * per), p1 = std::min(hi, (t + 1) * per);
+      const uint32_t dst = t1 > t0 ? (kFilterbankToWorkspace | (uint32_t)(slot0 + (t - t0))) : (uint32_t)b;
+      l.wsrc[count[t]] = woff + (p0 - lo);
+      l.pieces[count[t]++] = FilterbankPiece{(uint32_t)p0, (uint32_t)(p1 - p0), 0u, dst};
+    }
+    woff += band_nbins[b];
+  }
+  uint32_t at = 0;
+  for (FilterbankPiece& p : l.pieces) { p.woff = at; at += p.nbins; }
+  return l;
+}
+// The workspace holds the rows of ONE forward launch: [channels][rows of the launch][nslots] numbers, grown on demand and kept by
+// the plan.  It is bounded: the time chunks of a call (whose carries exist before the first of them runs) go in as many launches,
+// one after the other on the plan's stream, as keep each launch's rows within kFilterbankWorkspaceBytes, each followed by
+// filterbank_rows_kernel on its rows -- row segments of one call, which change nothing in its values or its state.  A launch is
+// at least one chunk: only a single chunk whose rows exceed the bound makes the workspace larger than that.
+constexpr size_t kFilterbankWorkspaceBytes = (size_t)64 << 20;
+inline size_t filterbank_slot(size_t channel, size_t rows, size_t row, size_t nslots, size_t slot) { return (channel * rows + row) * nslots + slot; }
+inline size_t filterbank_workspace(size_t channels, size_t rows, size_t nslots) { return channels * rows * nslots; }
+inline size_t filterbank_segment_rows(size_t channels, size_t nslots, size_t fd_bytes, size_t bound_bytes = kFilterbankWorkspaceBytes)
+{
+  const size_t row_bytes = std::max<size_t>(channels, 1) * nslots * fd_bytes;
+  return row_bytes == 0 ? (size_t)-1 : std::max<size_t>(bound_bytes / row_bytes, 1);
+}
+// rows of the grid among the samples [0, t) of a call, and the rows the chunks [ja, jb) of a launch keep: row0 ... row0 + rows - 1
+inline size_t filterbank_rows_before(size_t t, size_t every, size_t first) { return every_rows(t, every, first); }
+struct FilterbankSpan { long ja, jb; size_t row0, rows; };
+inline FilterbankSpan filterbank_span(long ja, long jb, long len, long shift, size_t n, size_t every, size_t first)
+{
+  const size_t r0 = filterbank_rows_before(chunk_begin(ja, len, shift), every, first), r1 = filterbank_rows_before(chunk_end(jb - 1, len, shift, n), every, first);
+  return {ja, jb, r0, r1 - r0};
+}
+// the next launch of the chunks [ja, j1): as many chunks from ja on as keep at most max_rows rows, one at least
+inline FilterbankSpan filterbank_next_span(long ja, long j1, long len, long shift, size_t n, size_t every, size_t first, size_t max_rows)
+{
+  FilterbankSpan s = filterbank_span(ja, ja + 1, len, shift, n, every, first);
+  while (s.jb < j1)
+  {
+    const FilterbankSpan more = filterbank_span(ja, s.jb + 1, len, shift, n, every, first);
+    if (more.rows > max_rows) break;
+    s = more;
+  }
+  return s;
+}
 
 // ---- exact carries, relay form: block length = seed distance -----------------------------------------------------------
 // divides 2N and the chunk length; L products live in L registers per lane (128 at FD float, 64 register pairs at FD double);
@@ -642,6 +764,7 @@ struct ForwardQuery
   bool power = false;                     // power-spectrogram analysis (forward_power_kernel) on a grid of ...
   size_t power_every = 1;                 // ... every power_every-th sample
   bool power_sum = false;                 // pooled power analysis (forward_pooled_power_kernel)
+  bool filterbank = false;                // filterbank analysis (forward_filterbank_kernel) on the grid of power_every
   bool row_pointers = false;              // rows go to a table of row pointers
   uintptr_t out = 0; size_t out_stride = 0;
   bool analysis_batch = false;            // CallPattern: analyses come call after call
@@ -652,7 +775,7 @@ struct ForwardQuery
        chain_L = 0, relay_flow = 1, segments = 0, xcd_map = 1, rows_f32 = 1, pipeline = 1;
   long prefix_cells = 1;                  // test hook: 0 = never the prefix-cell route, 1 = calls beyond kSelfMax, 2 = whatever the length
 };
-enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6 };     // = get_option "last_kernel"
+enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6, FK_FILTERBANK = 7 };     // = get_option "last_kernel"
 // carries: the single chunk's are the stream state (delta_kernel copies it); pre-pass partial sums + scan (carries from the
 // closed-form table); the serial exact pass (carry_exact_kernel); the relay form of the exact pass (carry_relay_kernel)
 enum CarryForm : int { CARRY_STATE = 0, CARRY_SUMS = 1, CARRY_SERIAL = 2, CARRY_RELAY = 3 };
@@ -700,8 +823,8 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   ForwardRoute r;
   const size_t nb = q.nbins, span = 2 * nb, n = q.n, ch = std::max<size_t>(q.channels, 1);
   const bool pow2 = (span & (span - 1)) == 0;
-  // the decimated, the power-spectrogram and the pooled power analysis have the tile form only
-  const bool grid = q.every || q.power || q.power_sum;
+  // the decimated, the power-spectrogram, the pooled power and the filterbank analysis have the tile form only
+  const bool grid = q.every || q.power || q.power_sum || q.filterbank;
   const bool rows = !grid && rows_kernel_ok(nb, q.fdx_bytes, q.row_pointers, q.rows_kernel != 0, q.row_slots_max);
   const bool folded = q.fuse && !q.reference_order && !q.fuse_store && q.fold && q.coeff_ready;
   // pipelined calls (forward_self): decided first because they take the self-carried form at any length and cut time differently
@@ -727,12 +850,12 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   {
     EveryQuery e;
     e.n = n; e.channels = ch; e.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); e.exact = q.exact; e.forced_chunk = q.chunk; e.compute_units = q.compute_units;
-    c = q.power_sum ? choose_power_sum_chunks(e) : q.power ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
+    c = q.power_sum ? choose_power_sum_chunks(e) : (q.power || q.filterbank) ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
   }
   else c = choose_chunks(chunk_query(q, rows, r.pipelined));
   r.chunks = c.chunks; r.len = c.len;
   r.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); r.interior = interior_lanes(q.window, q.fdx_bytes, q.interior);
-  r.kernel = q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
+  r.kernel = q.filterbank ? FK_FILTERBANK : q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
   if (r.chunks == 1 && q.hop_kernel && nb >= 2 && !q.fuse && !grid) { r.kernel = FK_HOP; return r; }
 
   // self-carried chunks: every workgroup derives its carry-in from the raw samples (fold + one FFT in LDS) and forms

@@ -286,6 +286,70 @@ class SDFT:
         assert got == rows, (got, rows)
         return out
 
+    def set_filterbank(self, bin0, nbins, weights):
+        """Installs a filterbank in the plan (``sdft_hip_set_filterbank``; the arrays are copied): band b covers the bins
+        ``bin0[b] <= k < bin0[b] + nbins[b]`` with the weights ``weights[off_b + (k - bin0[b])]``, ``off_b = sum(nbins[:b])``.  Bands
+        may overlap, repeat and come in any order.  No bands removes the filterbank.  :mod:`sdft_amd.filterbank` builds mel and
+        fractional-octave filterbanks in this form."""
+        self.api.clear()
+        b0 = np.ascontiguousarray(bin0, dtype=np.uint64).ravel()
+        nb = np.ascontiguousarray(nbins, dtype=np.uint64).ravel()
+        w = np.ascontiguousarray(weights, dtype=self.fd).ravel()
+        if b0.size != nb.size:
+            raise ValueError(f"bin0 and nbins must have one entry per band, got {b0.size} and {nb.size}")
+        if w.size != int(nb.sum()):
+            raise ValueError(f"weights must hold sum(nbins) = {int(nb.sum())} numbers, got {w.size}")
+        # (empty arrays still have an address: the library is never handed NULL for a filterbank that has bands)
+        rc = self.api.set_filterbank(self._p, b0.size, C.c_void_p(b0.ctypes.data), C.c_void_p(nb.ctypes.data), C.c_void_p(w.ctypes.data))
+        if rc != 0:
+            self.api.check()
+            raise SdftHipError("sdft_hip_set_filterbank failed")
+        self.api.check()
+
+    @property
+    def filterbank_bands(self) -> int:
+        """Bands of the installed filterbank (``sdft_hip_filterbank_bands``), 0 for none."""
+        return int(self.api.filterbank_bands(self._p))
+
+    def filterbank(self, x, every: int = 1, first: int = 0, out=None):
+        """Filterbank analysis (``sdft_hip_sdft_filterbank_n``): per band of the installed filterbank (:meth:`set_filterbank`) the
+        sum of ``weight * power`` over the band's bins, of the rows :meth:`power` would return for the samples ``first``,
+        ``first + every``, ... < n -> real array of shape (rows, nbands) [(channels, rows, nbands) if batched], numpy for numpy
+        input, a device tensor for a device tensor.  Neither the complex rows nor the powers are stored.  State and grid as with
+        :meth:`power`."""
+        self.api.clear()
+        every, first = int(every), int(first)
+        if every < 1 or first < 0:
+            raise ValueError(f"every must be >= 1 and first >= 0, got every={every}, first={first}")
+        nb = self.filterbank_bands
+        if nb == 0:
+            raise ValueError("no filterbank is installed: call set_filterbank first")
+        if _is_tensor(x):
+            torch = _torch()
+            n = self._shape_x(x.shape)
+            self._check_tensor(x, "samples", self.td)
+            rows = every_rows(n, every, first)
+            shape = (rows, nb) if x.dim() == 1 else (self.channels, rows, nb)
+            if out is None:
+                out = torch.empty(shape, dtype=getattr(torch, np.dtype(self.fd).name), device=x.device)
+            self._check_tensor(out, "out", self.fd, shape)
+            got = self.api.sdft_filterbank_n(self._p, n, C.c_void_p(x.data_ptr()), every, first, C.c_void_p(out.data_ptr() if rows else None))
+        else:
+            x = np.ascontiguousarray(x, dtype=self.td)
+            n = self._shape_x(x.shape)
+            rows = every_rows(n, every, first)
+            shape = (rows, nb) if x.ndim == 1 else (self.channels, rows, nb)
+            if out is None:
+                out = np.empty(shape, dtype=self.fd)
+            assert out.flags.c_contiguous and out.shape == shape and out.dtype == self.fd
+            got = self.api.sdft_filterbank_n(self._p, n, C.c_void_p(x.ctypes.data), every, first, C.c_void_p(out.ctypes.data if rows else None))
+        if got < 0:
+            self.api.check()
+            raise SdftHipError("sdft_hip_sdft_filterbank_n failed")
+        self.api.check()
+        assert got == rows, (got, rows)
+        return out
+
     def power_sum(self, x, every: int = 1, first: int = 0, bins=None, out=None):
         """Pooled power analysis (``sdft_hip_sdft_power_sum_n``): the grid points ``first``, ``first + every``, ... cut the n samples
         into windows, and row r is the sum of :meth:`power`'s ``every = 1`` values over the r-th window, for the bins
