@@ -243,6 +243,7 @@ long SDFT_FN(get_option)(const void* p, const char* key)
   if (!strcmp(key, "fused")) return q->opt_fused;
   if (!strcmp(key, "last_fused")) return q->last_fused;
   if (!strcmp(key, "last_segments")) return q->last_segments;
+  if (!strcmp(key, "last_filterbank_launches")) return q->last_filterbank_launches;
   if (!strcmp(key, "row_slots")) return q->row_slots();
   if (!strcmp(key, "device")) return q->device;
   if (!strcmp(key, "last_chain")) return q->last_chain;

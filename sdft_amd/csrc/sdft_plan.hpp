@@ -268,6 +268,7 @@ class Plan
 
   // last launch geometry (introspection for tests / bench)
   long last_chunks = 0, last_chunk_len = 0, last_tiles = 0, last_interior = 0, last_pipelined = 0;
+  long last_filterbank_launches = 0;                         // forward_filterbank_kernel launches of the last filterbank call
 
   bool create(size_t dftsize, int win, double lat, size_t nch)
   {
@@ -880,6 +881,7 @@ class Plan
           fb.ws_row0 = sp.row0; fb.ws_rows = sp.rows;
           launch_forward_filterbank(fa, fb, (unsigned)span_blocks);
           SDFT_TRY(hipGetLastError());
+          ++last_filterbank_launches;
           if (fb.nsplits && sp.rows && !launch_filterbank_rows(fb)) return false;   // the split bands of these rows, before the next launch reuses the workspace
           ja = sp.jb;
         }

@@ -253,6 +253,7 @@
     if (every == 0) { set_error(fn, "every must be at least 1"); return false; }
     rows = logic::every_rows(n, every, first);
     if (rows > 0 && !out) { set_error(fn, "out is NULL but the call keeps rows"); return false; }
+    last_filterbank_launches = 0;                            // (forward_rows_stage counts, over all host segments of the call)
     if (n == 0) return true;
     if (!bind()) return false;
     if (!pipe_join()) return false;

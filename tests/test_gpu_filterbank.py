@@ -10,6 +10,8 @@ and on the inexact route (FD double with the default carries) the power call's t
 tests/test_gpu_power.py (2.1e-11) times the largest power on the call's grid times sum |w|.  Every element of every row is compared."""
 
 import ctypes as C
+import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -17,7 +19,7 @@ import pytest
 import guarded as G
 from oracle import oracle as O
 from sdft_amd import filterbank as F
-from test_gpu_power import BAR, WINDOWS, MS, exact_combo, expected, make, on_grid, rel, signal, to_dev
+from test_gpu_power import BAR, ROOT, WINDOWS, MS, exact_combo, expected, make, on_grid, power_of, rel, signal, to_dev
 
 pytestmark = pytest.mark.gpu
 GRIDS = [(1, 0), (7, 6), (100, 0), (1024, 1023)]
@@ -321,6 +323,485 @@ def test_filterbank_guarded_misaligned_output(combo, host):
 
 
 # ---------------------------------------------------------------------------------------------
+# calls whose pieces exceed the workspace bound: several forward launches, each followed by the rows kernel on its rows
+# ---------------------------------------------------------------------------------------------
+FB_BOUND = 64 << 20                                          # logic::kFilterbankWorkspaceBytes, as sdft_hip.h and DESIGN.md state it
+BOUNDED = [("f32f32", {}), ("f32f64", {"carry": 1})]         # the routes on which a row's bits do not depend on the time chunks
+
+
+def same_bits(a, b):
+    import torch
+    if hasattr(a, "cpu") and hasattr(b, "cpu"):              # (on the device: these matrices are tens of MB)
+        iv = torch.int32 if a.dtype == torch.float32 else torch.int64
+        return a.shape == b.shape and a.dtype == b.dtype and bool(torch.equal(a.contiguous().view(iv), b.contiguous().view(iv)))
+    a, b = (np.ascontiguousarray(v.cpu().numpy() if hasattr(v, "cpu") else v) for v in (a, b))
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def same_state(p, q):
+    a, b = p.state(), q.state()
+    return all(same_bits(u, v) for u, v in zip(a[:3], b[:3])) and a[3] == b[3]
+
+
+def geometry(p):
+    """(tiles, bins a tile owns) of a plan"""
+    return p.get_option("tiles"), p.get_option("interior") * p.get_option("bins_per_lane")
+
+
+def four_tile_plan(combo, channels=1, **opts):
+    """a plan of 256 bins, or of the fewest bins that make 4 tiles"""
+    p = make(256, "hann", combo, channels, **opts)
+    tiles, per = geometry(p)
+    if tiles < 4:
+        p.close()
+        p = make(3 * per + 1, "hann", combo, channels, **opts)
+    assert p.get_option("tiles") >= 4
+    return p
+
+
+def pieces_of(bank, per):
+    """pieces per band: the tiles it has bins in"""
+    b0, nb = np.asarray(bank[0]).astype(np.int64), np.asarray(bank[1]).astype(np.int64)
+    return (b0 + nb - 1) // per - b0 // per + 1
+
+
+def slots_of(bank, per):
+    """workspace slots per row and channel: the pieces of the split bands (logic::filterbank_layout)"""
+    k = pieces_of(bank, per)
+    return int(k[k > 1].sum())
+
+
+def split_bank(m, tiles, per, nslots, exact=False, seed=7):
+    """Split bands of at least nslots workspace slots (exact: of nslots), one unsplit band to four of them, in shuffled order.  The
+    split bands repeat one set: for every piece count 2 ... tiles and every first tile a band from the tile's first bin to the first
+    bin of its last tile (it starts and ends on a boundary bin), one from the last bin before a boundary to its last tile's last
+    bin, and one with both ends drawn.  The unsplit ones: a whole tile, one bin, a drawn range.  Weights as random_bands."""
+    rng = np.random.default_rng(seed)
+
+    def split_set():
+        out = []
+        for k in range(2, tiles + 1):
+            for t0 in range(tiles - k + 1):
+                t1 = t0 + k - 1
+                a0, a1 = t0 * per, (t0 + 1) * per                          # the bins [a0, a1) of the first tile
+                b0, b1 = t1 * per, min((t1 + 1) * per, m)                   # ... of the last
+                out.append((a0, b0 + 1 - a0))
+                out.append((a1 - 1, b1 - (a1 - 1)))
+                s, e = int(rng.integers(a0, a1)), int(rng.integers(b0, b1))
+                out.append((s, e + 1 - s))
+        return out
+
+    bands, slots = [], 0
+    while slots < nslots:
+        for s, k in split_set():
+            pieces, left = (s + k - 1) // per - s // per + 1, nslots - slots
+            if left <= 0:
+                break
+            if exact and left != pieces and left - pieces < 2:              # (what stays can still be made of bands of 2 and 3 pieces)
+                continue
+            bands.append((s, k))
+            slots += pieces
+    for i in range(len(bands) // 4 + tiles):
+        t = int(rng.integers(0, tiles))
+        a0, a1 = t * per, min((t + 1) * per, m)
+        s = int(rng.integers(a0, a1))
+        bands.append([(a0, a1 - a0), (s, 1), (s, int(rng.integers(s, a1)) + 1 - s)][i % 3])
+    bands = np.array(bands, dtype=np.int64)[rng.permutation(len(bands))]
+    start, length = bands[:, 0], bands[:, 1]
+    assert (length >= 1).all() and (start + length <= m).all()
+    total = int(length.sum())
+    kind = rng.integers(0, 4, total)
+    w = np.choose(kind, [np.zeros(total), np.ones(total), np.full(total, -0.5), rng.uniform(2.0 ** -10, 1.0, total)])
+    bank = start.astype(np.uint64), length.astype(np.uint64), w
+    k = pieces_of(bank, per)
+    assert set(k.tolist()) == set(range(1, tiles + 1)), sorted(set(k.tolist()))          # every piece count, 1 = unsplit
+    assert ((start % per == 0) & (k > 1)).any() and (((start + length) % per == 0) & (k > 1)).any()
+    assert slots_of(bank, per) == nslots if exact else slots_of(bank, per) >= nslots
+    split = k > 1
+    assert (split[1:] != split[:-1]).sum() > len(k) // 8                                  # direct and workspace stores alternate
+    return bank
+
+
+def launches_needed(channels, rows, nslots, size):
+    return -(-(channels * rows * nslots * size) // FB_BOUND)
+
+
+def run_beyond_the_bound(combo, opts, n, every, first):
+    """One device call whose pieces are at least 3 x 64 MiB, against the float64 W @ p, and bit for bit (rows and final state)
+    against a twin plan fed the same samples in calls of one launch each.  Returns (rows, launches, chunks)."""
+    import torch
+    from sdft_amd.sdft import every_next_first, every_rows
+    td, fd, _ = O.combo_types(combo)
+    size = np.dtype(fd).itemsize
+    rows = every_rows(n, every, first)
+    with four_tile_plan(combo, **opts) as p, four_tile_plan(combo, **opts) as q:
+        m = p.dftsize
+        tiles, per = geometry(p)
+        bank = in_fd(split_bank(m, tiles, per, -(-3 * FB_BOUND // (rows * size))), fd)
+        nslots = slots_of(bank, per)
+        assert rows * nslots * size >= 3 * FB_BOUND
+        x, pw = expected(combo, "hann", m, n)
+        p.set_filterbank(*bank); q.set_filterbank(*bank)
+        got = p.filterbank(to_dev(x), every, first)
+        launches, chunks = p.get_option("last_filterbank_launches"), p.get_option("last_chunks")
+        print(f"{(combo, m, n, every, first)}: {bank[0].size} bands, {nslots} slots, {chunks} chunks in {launches} launches")
+        assert p.get_option("last_kernel") == 7 and chunks > 1
+        assert launches >= launches_needed(1, rows, nslots, size)
+        assert 3 <= launches < chunks                        # several chunks to a launch, and the last launch ragged
+        R, T, L, sum_w = reference(bank, torch.from_numpy(np.array(on_grid(pw, every, first))).cuda().double())
+        check_rows(got, R, T, L, sum_w, fd, 0.0, ("beyond the bound", combo, m, n, every, first))
+        del R, T
+        # the same samples in calls whose rows fit the workspace
+        fit = FB_BOUND // (nslots * size)                    # rows of one launch
+        lengths = [1, 511, 512, 513]
+        while sum(lengths) < n:
+            lengths.append(min(fit * every - 5, n - sum(lengths)))
+        parts, t, f = [], 0, first
+        for k in lengths:
+            parts.append(q.filterbank(to_dev(x[t:t + k]), every, f))
+            assert q.get_option("last_filterbank_launches") == 1, (k, f)
+            f = every_next_first(k, every, f)
+            t += k
+        assert same_bits(torch.cat(parts), got), (combo, every, first)
+        assert same_state(p, q), (combo, every, first)
+    return rows, launches, chunks
+
+
+@pytest.mark.parametrize("combo,opts", BOUNDED)
+def test_filterbank_beyond_the_workspace_bound(combo, opts):
+    """(every, first) = (1, 0): launches begin at rows that are multiples of the chunk length"""
+    run_beyond_the_bound(combo, opts, 6000, 1, 0)
+
+
+@pytest.mark.parametrize("combo,opts", BOUNDED)
+def test_filterbank_beyond_the_workspace_bound_on_a_sparse_grid(combo, opts):
+    """(every, first) = (3, 2): a chunk of 128 samples keeps 42 or 43 rows, launches begin wherever those add up to"""
+    run_beyond_the_bound(combo, opts, 6000, 3, 2)
+
+
+@pytest.mark.parametrize("combo,opts", BOUNDED)
+def test_filterbank_beyond_the_workspace_bound_by_channels_alone(combo, opts):
+    """4096 rows x slots = 64 MiB exactly: one launch for one channel, three channels exceed the bound by their count alone (the
+    workspace is [channels][rows of the launch][slots], the channel stride changes from launch to launch).  Every channel against
+    its single-channel plan, bit for bit; channel 0 against the reference as well."""
+    import torch
+    td, fd, _ = O.combo_types(combo)
+    size = np.dtype(fd).itemsize
+    ch, n = 3, 4096
+    nslots = FB_BOUND // (n * size)
+    assert n * nslots * size == FB_BOUND
+    with four_tile_plan(combo, ch, **opts) as p:
+        m = p.dftsize
+        tiles, per = geometry(p)
+        bank = in_fd(split_bank(m, tiles, per, nslots, exact=True), fd)
+        x0, pw = expected(combo, "hann", m, n)
+        x = np.stack([x0] + [signal(n, td, 300 + c) for c in range(1, ch)])
+        p.set_filterbank(*bank)
+        got = p.filterbank(to_dev(x), 1, 0)
+        launches, chunks = p.get_option("last_filterbank_launches"), p.get_option("last_chunks")
+        assert p.get_option("last_kernel") == 7
+        assert ch * n * nslots * size >= 3 * FB_BOUND and launches >= launches_needed(ch, n, nslots, size)
+        assert 3 <= launches < chunks
+    R, T, L, sum_w = reference(bank, torch.from_numpy(np.array(pw)).cuda().double())
+    check_rows(got[0], R, T, L, sum_w, fd, 0.0, ("three channels, channel 0", combo, m))
+    del R, T
+    for c in range(ch):
+        with four_tile_plan(combo, **opts) as q:
+            q.set_filterbank(*bank)
+            one = q.filterbank(to_dev(x[c]), 1, 0)
+            assert q.get_option("last_filterbank_launches") == 1
+            assert same_bits(got[c], one), (combo, c)
+
+
+@pytest.mark.parametrize("combo,opts", BOUNDED)
+def test_filterbank_one_chunk_beyond_the_workspace_bound(combo, opts):
+    """chunk = 1024 with more than 64 MiB / 1024 slots: a launch is one chunk and the workspace grows past its bound; the rows of
+    the call with the library's own chunks (several to a launch), bit for bit"""
+    import torch
+    td, fd, _ = O.combo_types(combo)
+    size = np.dtype(fd).itemsize
+    n, forced = 3000, 1024
+    with four_tile_plan(combo, chunk=forced, **opts) as p, four_tile_plan(combo, **opts) as q:
+        m = p.dftsize
+        tiles, per = geometry(p)
+        bank = in_fd(split_bank(m, tiles, per, max(-(-3 * FB_BOUND // (n * size)), FB_BOUND // (forced * size) + 1)), fd)
+        nslots = slots_of(bank, per)
+        assert forced * nslots * size > FB_BOUND and n * nslots * size >= 3 * FB_BOUND
+        x, pw = expected(combo, "hann", m, n)
+        p.set_filterbank(*bank); q.set_filterbank(*bank)
+        got = p.filterbank(to_dev(x), 1, 0)
+        assert p.get_option("last_kernel") == 7 and p.get_option("last_chunk_len") == forced
+        assert p.get_option("last_filterbank_launches") == p.get_option("last_chunks") == -(-n // forced)
+        R, T, L, sum_w = reference(bank, torch.from_numpy(np.array(pw)).cuda().double())
+        check_rows(got, R, T, L, sum_w, fd, 0.0, ("one chunk beyond the bound", combo, m))
+        del R, T
+        want = q.filterbank(to_dev(x), 1, 0)
+        assert 3 <= q.get_option("last_filterbank_launches") < q.get_option("last_chunks")
+        assert same_bits(got, want), combo
+        assert same_state(p, q), combo
+
+
+def test_filterbank_beyond_the_workspace_bound_chunk_parallel_carries():
+    """FD double with its default carries (the inexact route), several launches: the contract's bar with the inexact term, and
+    the same bytes from two fresh plans"""
+    import torch
+    combo, n = "f64f64", 6000
+    td, fd, _ = O.combo_types(combo)
+    outs = []
+    for _ in range(2):
+        with four_tile_plan(combo) as p:
+            m = p.dftsize
+            tiles, per = geometry(p)
+            bank = in_fd(split_bank(m, tiles, per, -(-3 * FB_BOUND // (n * 8))), fd)
+            nslots = slots_of(bank, per)
+            assert n * nslots * 8 >= 3 * FB_BOUND
+            x, pw = expected(combo, "hann", m, n)
+            p.set_filterbank(*bank)
+            outs.append(p.filterbank(to_dev(x), 1, 0))
+            launches = p.get_option("last_filterbank_launches")
+            assert p.get_option("last_kernel") == 7 and launches >= launches_needed(1, n, nslots, 8)
+            assert 3 <= launches < p.get_option("last_chunks")
+    p64 = torch.from_numpy(np.array(pw)).cuda().double()
+    R, T, L, sum_w = reference(bank, p64)
+    check_rows(outs[0], R, T, L, sum_w, fd, float(p64.max()), ("beyond the bound, chunk-parallel carries", combo, m))
+    assert same_bits(outs[0], outs[1])
+
+
+# ---------------------------------------------------------------------------------------------
+# forced routes, host staging in segments, asynchronous calls
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("opts", [dict(chunk=128), dict(chunk=1000), dict(carry=1, segments=3), dict(carry=1, chain=2), dict(carry=1, chain=0)],
+                         ids=lambda o: "-".join(f"{k}{v}" for k, v in o.items()))
+def test_filterbank_forced_routes(opts):
+    """the option sets of test_power_sum_forced_routes; with exact carries the rows of the default exact route, bit for bit.  The
+    kernel polls for no relay carries: whatever the options, the call never takes the flow form."""
+    import torch
+    combo, m, n = "f32f64", 1000, 6000
+    fd = np.float64
+    exact = "carry" in opts
+    x, pw = expected(combo, "hann", m, n)
+    bank = in_fd(random_bands(m), fd)
+    p64 = torch.from_numpy(np.array(pw)).cuda().double()
+    R, T, L, sum_w = reference(bank, p64)
+    with make(m, "hann", combo, **opts) as p, make(m, "hann", combo, carry=1) as q:
+        p.set_filterbank(*bank); q.set_filterbank(*bank)
+        for every, first in ((1, 0), (100, 37)):
+            p.reset(); q.reset()
+            got = p.filterbank(to_dev(x), every, first)
+            assert p.get_option("last_chunks") > 1 and p.get_option("last_kernel") == 7 and p.get_option("last_flow") == 0
+            if "chunk" in opts:
+                assert p.get_option("last_chunk_len") == opts["chunk"]
+            if "segments" in opts:
+                assert p.get_option("last_segments") == opts["segments"]
+            if "chain" in opts:
+                assert p.get_option("last_chain") == (3 if opts["chain"] else 0)
+            inexact = 0.0 if exact else float(p64[first::every].max())
+            check_rows(got, R[first::every], T[first::every], L, sum_w, fd, inexact, ("forced route", opts, every, first))
+            if exact:
+                assert same_bits(got, q.filterbank(to_dev(x), every, first)), (opts, every, first)
+                assert same_state(p, q), (opts, every, first)
+
+
+def test_filterbank_beyond_the_workspace_bound_in_carry_segments():
+    """segments = 3 with pieces of 3 x 64 MiB: the launches of the workspace bound nest inside the carry segments (a launch never
+    spans two of them), more launches than segments"""
+    import torch
+    combo, n = "f32f64", 6000
+    fd = np.float64
+    with four_tile_plan(combo, carry=1, segments=3) as p, four_tile_plan(combo, carry=1) as q:
+        m = p.dftsize
+        tiles, per = geometry(p)
+        bank = in_fd(split_bank(m, tiles, per, -(-3 * FB_BOUND // (n * 8))), fd)
+        nslots = slots_of(bank, per)
+        assert n * nslots * 8 >= 3 * FB_BOUND
+        x, pw = expected(combo, "hann", m, n)
+        p.set_filterbank(*bank); q.set_filterbank(*bank)
+        got = p.filterbank(to_dev(x), 1, 0)
+        segments, launches = p.get_option("last_segments"), p.get_option("last_filterbank_launches")
+        assert p.get_option("last_kernel") == 7 and p.get_option("last_flow") == 0
+        assert segments > 1 and launches > segments and launches >= launches_needed(1, n, nslots, 8)
+        R, T, L, sum_w = reference(bank, torch.from_numpy(np.array(pw)).cuda().double())
+        check_rows(got, R, T, L, sum_w, fd, 0.0, ("beyond the bound in carry segments", combo, m))
+        del R, T
+        assert same_bits(got, q.filterbank(to_dev(x), 1, 0))
+        assert q.get_option("last_segments") == 1
+        assert same_state(p, q)
+
+
+@pytest.mark.parametrize("combo,opts", [("f32f64", {}), ("f32f32", {}), ("f32f64", {"carry": 1})])
+def test_filterbank_host_staging_in_segments(combo, opts):
+    """stage_bytes of 7 and of 2 output rows: host samples with host and with device output, grids whose rows fall on the first
+    and the last sample of a segment, before and after its end, and one row for all segments; on the exact routes the rows of the
+    unstaged call, bit for bit"""
+    import torch
+    from sdft_amd.sdft import every_rows
+    fd = O.combo_types(combo)[1]
+    m, n = 1000, 6000
+    exact = exact_combo(combo) or "carry" in opts
+    x, pw = expected(combo, "hann", m, n)
+    bank = in_fd(random_bands(m), fd)
+    nbands = bank[0].size
+    row = nbands * np.dtype(fd).itemsize
+    p64 = torch.from_numpy(np.array(pw)).cuda().double()
+    R, T, L, sum_w = reference(bank, p64)
+    with make(m, "hann", combo, **opts) as q:
+        q.set_filterbank(*bank)
+        # (the third: 700 samples' bytes, less than a row's -- the samples go in segments too, whatever memory the rows go to)
+        for stage, grids in [(7 * row, [(100, 37), (100, 0), (100, 99)]), (2 * row, [(1024, 1023), (6000, 0), (700, 0)]),
+                             (700 * x.itemsize, [(100, 37), (700, 699)])]:
+            with make(m, "hann", combo, stage_bytes=stage, **opts) as p:
+                p.set_filterbank(*bank)
+                for every, first in grids:
+                    rows = every_rows(n, every, first)
+                    inexact = 0.0 if exact else float(p64[first::every].max())
+                    q.reset()
+                    want = q.filterbank(to_dev(x), every, first)
+                    p.reset()
+                    got = p.filterbank(x, every, first)
+                    assert p.get_option("last_kernel") == 7
+                    check_rows(got, R[first::every], T[first::every], L, sum_w, fd, inexact, (combo, opts, stage // row, every, first, "host"))
+                    assert not exact or same_bits(got, want.cpu().numpy()), (combo, stage // row, every, first, "host")
+                    assert same_state(p, q) if exact else p.state()[3] == q.state()[3]
+                    p.reset()
+                    out = torch.zeros((rows, nbands), dtype=getattr(torch, np.dtype(fd).name), device="cuda")
+                    ret = p.api.sdft_filterbank_n(p._p, n, C.c_void_p(x.ctypes.data), every, first, C.c_void_p(out.data_ptr()))
+                    p.synchronize()
+                    assert ret == rows, p.api.last_error()
+                    check_rows(out, R[first::every], T[first::every], L, sum_w, fd, inexact, (combo, opts, stage // row, every, first, "host samples, device rows"))
+                    assert not exact or same_bits(out, want), (combo, stage // row, every, first, "device rows")
+
+
+def test_filterbank_async_device_pointers():
+    import torch
+    combo, m, n, every, first = "f32f64", 1000, 6000, 100, 37
+    x, pw = expected(combo, "hann", m, n)
+    bank = in_fd(random_bands(m), np.float64)
+    p64 = torch.from_numpy(np.array(on_grid(pw, every, first))).cuda().double()
+    R, T, L, sum_w = reference(bank, p64)
+    with make(m, "hann", combo, **{"async": 1}) as p:
+        p.set_filterbank(*bank)
+        got = p.filterbank(to_dev(x), every, first)
+        p.synchronize()
+        assert p.get_option("last_kernel") == 7
+        check_rows(got, R, T, L, sum_w, np.float64, float(p64.max()), "async")
+
+
+# ---------------------------------------------------------------------------------------------
+# option "interior" changes the tiles after the filterbank was installed: the bands are cut again
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("combo,opts", [("f32f32", {}), ("f32f64", {"carry": 1}), ("f64f64", {})])
+def test_filterbank_is_cut_again_when_the_tiles_change(combo, opts):
+    import torch
+    from sdft_amd.sdft import SDFT
+    td, fd, _ = O.combo_types(combo)
+    m, n, every, first, other = 1024, 6000, 7, 6, 62
+    exact = exact_combo(combo) or "carry" in opts
+    x, pw = expected(combo, "hann", m, n)
+    bank = in_fd(random_bands(m), fd)
+    p64 = torch.from_numpy(np.array(on_grid(pw, every, first))).cuda().double()
+    R, T, L, sum_w = reference(bank, p64)
+    inexact = 0.0 if exact else float(p64.max())
+    with SDFT(m, "hann", 1.0, combo, hooks=True) as p:
+        for k, v in opts.items():
+            p.set_option(k, v)
+        assert p.get_option("test_hooks") == 1
+        p.set_filterbank(*bank)
+        tiles0, interior0 = p.get_option("tiles"), p.get_option("interior")
+        outs = []
+        for step, lanes in enumerate((interior0, other, interior0)):
+            p.set_option("interior", lanes)
+            assert p.get_option("interior") == lanes and (p.get_option("tiles") != tiles0) == (lanes != interior0)
+            p.reset()
+            outs.append(p.filterbank(to_dev(x) if step % 2 else x, every, first))
+            assert p.get_option("last_kernel") == 7 and p.get_option("last_chunks") > 1
+            assert p.filterbank_bands == bank[0].size
+            check_rows(outs[-1], R, T, L, sum_w, fd, inexact, (combo, "interior", lanes))
+        assert same_bits(outs[0], outs[2]), combo
+    if exact:
+        # one-bin bands installed under the default tiles, cut again for the other ones: still the power call
+        with SDFT(m, "hann", 1.0, combo, hooks=True) as p, SDFT(m, "hann", 1.0, combo, hooks=True) as q:
+            for k, v in opts.items():
+                p.set_option(k, v); q.set_option(k, v)
+            p.set_filterbank(*in_fd(one_bin_bands(m), fd))
+            p.filterbank(x[:700], every, first)
+            p.set_option("interior", other); q.set_option("interior", other)
+            assert p.get_option("tiles") != tiles0
+            p.reset()
+            got, want = p.filterbank(to_dev(x), every, first), q.power(to_dev(x), every, first)
+            assert p.get_option("last_kernel") == 7 and q.get_option("last_kernel") == 5
+            assert same_bits(got, want), combo
+
+
+# ---------------------------------------------------------------------------------------------
+# the five analysis entry points interleaved on one plan
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seed", [0, 1, 2])
+@pytest.mark.parametrize("m", [125, 1000])
+@pytest.mark.parametrize("combo,opts", BOUNDED)
+def test_analysis_entry_points_interleaved_on_one_plan(combo, opts, m, seed):
+    """12 000 samples in 25 to 40 calls, each to one of sdft, sdft_every, power, power_sum, filterbank with a drawn grid, host and
+    device memory in turn.  A twin plan takes the same cuts through sdft alone; a call's output is what numpy derives from the
+    twin's rows of that call -- the rows on the grid, re * re + im * im of them -- and for the two calls that add (their order of
+    addition is the library's) the library's own value from a plan that has seen none of the other entry points.  A filterbank
+    row's bits depend on the plan, the filterbank and the row's powers alone: a third plan gives them for that call alone from the
+    twin's state before it (sdft_hip_set_state).  A pooled row's bits depend on where the time chunks cut its window, and an
+    installed state moves the chunks (its fid does not count as canonical, so the relay form, whose chunks begin on its block
+    boundaries, is not taken): there the other plan follows the stream through sdft and makes only the pooled calls itself, with
+    the same kind of memory; every == 1, first == 0 is numpy's powers as well.  After every call the plan's state is the twin's."""
+    from sdft_amd.sdft import every_rows
+    td, fd, _ = O.combo_types(combo)
+    rng = np.random.default_rng(100 * m + seed)
+    n = 12000
+    special = [1, 2, 99, 100, 511, 512, 513, 2 * m - 1, 2 * m, 2 * m + 1]
+    calls = int(rng.integers(25, 41))
+    cuts = np.sort(rng.choice(np.arange(1, n - sum(special)), calls - len(special) - 1, replace=False))
+    drawn = np.diff(np.concatenate([[0], cuts, [n - sum(special)]]))
+    lengths = rng.permutation(np.concatenate([special, drawn]).astype(np.int64))
+    assert lengths.size == calls and lengths.sum() == n and (lengths >= 1).all()
+    x = signal(n, td, 50 + seed)
+    bank = in_fd(random_bands(m), fd)
+    names = ("sdft", "every", "power", "power_sum", "filterbank")
+    seen = set()
+    with make(m, "hann", combo, **opts) as p, make(m, "hann", combo, **opts) as twin, make(m, "hann", combo, **opts) as lone, \
+            make(m, "hann", combo, **opts) as pool:
+        p.set_filterbank(*bank); lone.set_filterbank(*bank)
+        t = 0
+        for i, k in enumerate(lengths.tolist()):
+            kind = names[int(rng.integers(0, len(names)))]
+            every = int(rng.choice([1, 2, 3, 7, 100, int(rng.integers(1, 600))]))
+            first = int(rng.integers(0, every + 2))
+            b0 = int(rng.integers(0, m))
+            band = (b0, int(rng.integers(1, m - b0 + 1)))
+            xs = x[t:t + k]
+            xin = to_dev(xs) if i % 2 else xs
+            what = (combo, m, seed, i, kind, k, every, first, band)
+            before = twin.state()
+            rows = twin.sdft(xs)
+            if kind == "sdft":
+                got, want = p.sdft(xin), rows
+            elif kind == "every":
+                got, want = p.sdft_every(xin, every, first), rows[first::every]
+            elif kind == "power":
+                got, want = p.power(xin, every, first, bins=band), power_of(rows)[first::every, band[0]:band[0] + band[1]]
+            elif kind == "power_sum":
+                got, want = p.power_sum(xin, every, first, bins=band), pool.power_sum(xin, every, first, bins=band)
+                assert (p.get_option("last_chunks"), p.get_option("last_chunk_len")) == (pool.get_option("last_chunks"), pool.get_option("last_chunk_len")), what
+                if every == 1 and first == 0:
+                    assert same_bits(got, np.ascontiguousarray(power_of(rows)[:, band[0]:band[0] + band[1]])), what
+            else:
+                lone.set_state(*before)
+                got, want = p.filterbank(xin, every, first), lone.filterbank(xs, every, first)
+                assert got.shape == (every_rows(k, every, first), bank[0].size), what
+            if kind != "power_sum":
+                pool.sdft(xs)
+            assert same_bits(got, want if hasattr(want, "cpu") else np.ascontiguousarray(want)), what
+            assert same_state(p, twin) and same_state(pool, twin), what
+            seen.add(kind)
+            t += k
+    assert len(seen) == len(names), seen
+
+
+# ---------------------------------------------------------------------------------------------
 # errors
 # ---------------------------------------------------------------------------------------------
 def test_filterbank_errors_leave_state_and_filterbank_untouched():
@@ -389,3 +870,66 @@ def test_filterbank_errors_leave_state_and_filterbank_untouched():
         api.clear()
         assert api.sdft_filterbank_n(p._p, 100, x.ctypes.data, 10, 0, big.ctypes.data) == -1
         api.clear()
+
+
+# ---------------------------------------------------------------------------------------------
+# a plain C host and a C++ host
+# ---------------------------------------------------------------------------------------------
+def host_link(hip_library):
+    libdir = os.path.dirname(hip_library)
+    rt = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib")
+    return ["-L", libdir, "-lsdft_hip", "-L", rt, "-lamdhip64", "-lm", f"-Wl,-rpath,{libdir}", f"-Wl,-rpath,{rt}"]
+
+
+@pytest.mark.parametrize("flags,combo", [([], "f32f64"), (["-DSDFT_FD_FLOAT"], "f32f32")])
+def test_c_host_filterbank(tmp_path, hip_library, flags, combo):
+    """tests/c/host_filterbank.c: a stream in calls of ragged lengths, each with the documented next first, and the error returns
+    through sdft_hip_last_error; its rows against SDFT.filterbank of the whole signal in one call (FD float: bit for bit)"""
+    import torch
+    td, fd, _ = O.combo_types(combo)
+    exe = tmp_path / "host_filterbank"
+    cmd = ["gcc", "-std=c99", "-O1", "-Wall", "-I", os.path.join(ROOT, "include"), *flags,
+           os.path.join(ROOT, "tests", "c", "host_filterbank.c"), "-o", str(exe), *host_link(hip_library)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    m, n, every, nbands = 1000, 6000, 7, 24
+    x, pw = expected(combo, "hann", m, n)
+    x.tofile(tmp_path / "x.raw")
+    r = subprocess.run([str(exe), str(m), str(every), str(tmp_path / "x.raw"), str(tmp_path / "rows.raw")], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
+    assert "C-HOST-FILTERBANK ok" in r.stdout
+    got = np.fromfile(tmp_path / "rows.raw", dtype=fd).reshape(-1, nbands)
+    # the host's filterbank (host_filterbank.c): overlapping bands, wider than a tile
+    start = np.arange(nbands) * m // 32
+    length = np.minimum(m // 8 + 7 * np.arange(nbands), m - start)
+    w = np.concatenate([(1 + (b * 31 + np.arange(length[b]) * 7) % 13) / 16 - 0.25 for b in range(nbands)])
+    bank = in_fd((start.astype(np.uint64), length.astype(np.uint64), w), fd)
+    p64 = torch.from_numpy(np.array(on_grid(pw, every, 0))).cuda().double()
+    R, T, L, sum_w = reference(bank, p64)
+    check_rows(got, R, T, L, sum_w, fd, 0.0 if exact_combo(combo) else float(p64.max()), ("C host", combo))
+    with make(m, "hann", combo) as p:
+        p.set_filterbank(*bank)
+        tiles, per = geometry(p)
+        assert (pieces_of(bank, per) > 1).sum() > nbands // 2
+        want = p.filterbank(x, every, 0)
+    assert got.shape == want.shape
+    if exact_combo(combo):
+        assert same_bits(got, want)
+
+
+@pytest.mark.parametrize("t,f,combo", [("float", "double", "f32f64"), ("double", "double", "f64f64"), ("float", "float", "f32f32")])
+def test_cpp_facade_filterbank(tmp_path, hip_library, t, f, combo):
+    """tests/cpp/host_filterbank.cpp: sdft::SDFT<T, F>::set_filterbank, filterbank_bands, filterbank and power_sum, for the type
+    pairs of test_cpp_facade_host; the host checks a whole-row band against the row sums of power_sum within the contract's bar
+    and a one-bin bank against its rows bit for bit (calls of one time chunk: the powers of both calls are the same bits)"""
+    td = O.combo_types(combo)[0]
+    exe = tmp_path / "host_filterbank_cpp"
+    cmd = ["g++", "-std=c++11", "-O1", "-Wall", f"-DHOST_T={t}", f"-DHOST_F={f}", "-I", os.path.join(ROOT, "include", "cpp"),
+           os.path.join(ROOT, "tests", "cpp", "host_filterbank.cpp"), "-o", str(exe), *host_link(hip_library)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    m, n = 1000, 441
+    signal(n, td, 9).tofile(tmp_path / "x.raw")
+    r = subprocess.run([str(exe), str(m), str(tmp_path / "x.raw")], capture_output=True, text=True, timeout=120)
+    print(r.stdout.strip())
+    assert r.returncode == 0 and "CPP-FILTERBANK ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
