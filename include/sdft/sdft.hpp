@@ -40,7 +40,11 @@ const char* sdft_hip_last_error(void);
   int sdft_hip_set_filterbank_##SUF(void* plan, std::size_t nbands, const std::size_t* band_bin0, const std::size_t* band_nbins, \
                                     const void* weights);                                                               \
   std::size_t sdft_hip_filterbank_bands_##SUF(const void* plan);                                                       \
-  long sdft_hip_sdft_filterbank_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, void* out);
+  long sdft_hip_sdft_filterbank_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, void* out); \
+  int sdft_hip_set_pairs_##SUF(void* plan, std::size_t npairs, const std::size_t* pair_a, const std::size_t* pair_b);    \
+  std::size_t sdft_hip_pairs_##SUF(const void* plan);                                                                  \
+  long sdft_hip_sdft_cross_sum_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, \
+                                       std::size_t bin0, std::size_t nbins, void* sums);
 SDFT_HPP_DECLARE(f32f64, float)
 SDFT_HPP_DECLARE(f32f32, float)
 SDFT_HPP_DECLARE(f64f64, double)
@@ -80,6 +84,9 @@ namespace sdft
       static int set_filterbank(void* p, std::size_t nb, const std::size_t* b0, const std::size_t* bn, const void* w) { return sdft_hip_set_filterbank_##SUF(p, nb, b0, bn, w); } \
       static std::size_t filterbank_bands(const void* p) { return sdft_hip_filterbank_bands_##SUF(p); } \
       static long sdft_filterbank_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, void* d) { return sdft_hip_sdft_filterbank_n_##SUF(p, n, x, e, f, d); } \
+      static int set_pairs(void* p, std::size_t np, const std::size_t* a, const std::size_t* b) { return sdft_hip_set_pairs_##SUF(p, np, a, b); } \
+      static std::size_t pairs(const void* p) { return sdft_hip_pairs_##SUF(p); } \
+      static long sdft_cross_sum_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_cross_sum_n_##SUF(p, n, x, e, f, b, k, d); } \
     };
     SDFT_HPP_ABI(f32f64, float, double)
     SDFT_HPP_ABI(f32f32, float, float)
@@ -230,6 +237,40 @@ namespace sdft
       {
         const char* e = sdft_hip_last_error();
         throw std::runtime_error(std::string("sdft_hip_sdft_filterbank_n: ") + (e ? e : "failed"));
+      }
+      return static_cast<std::size_t>(rows);
+    }
+
+    /**
+     * Installs (copies) a list of channel pairs in the plan (sdft_hip_set_pairs; host arrays): pair p is the channels
+     * (pair_a[p], pair_b[p]); pairs may repeat and have a == b (the auto-spectrum).  npairs == 0 removes the list.
+     **/
+    void set_pairs(const std::size_t npairs, const std::size_t* pair_a, const std::size_t* pair_b)
+    {
+      if (api::set_pairs(plan_, npairs, pair_a, pair_b) != 0)
+      {
+        const char* e = sdft_hip_last_error();
+        throw std::runtime_error(std::string("sdft_hip_set_pairs: ") + (e ? e : "failed"));
+      }
+    }
+    /** Pairs of the installed list, 0 for none. */
+    std::size_t pairs() const { return api::pairs(plan_); }
+
+    /**
+     * Pooled cross-spectrum analysis (sdft_hip_sdft_cross_sum_n): per pair (a, b) of the installed list the sum of
+     * X_a conj(X_b) over the windows of power_sum()'s grid, for the bins bin0 <= k < bin0 + nbins; samples is
+     * (channels, nsamples), out is dense (pairs(), rows, nbins).  Sums, not means; first > 0 makes row 0 the head window that
+     * completes the previous call's last row.  The state of every channel advances over all samples and all bins.  Returns the
+     * number of rows written.
+     **/
+    std::size_t cross_sum(const std::size_t nsamples, const T* samples, const std::size_t every, const std::size_t first,
+                          const std::size_t bin0, const std::size_t nbins, std::complex<F>* const out)
+    {
+      const long rows = api::sdft_cross_sum_n(plan_, nsamples, samples, every, first, bin0, nbins, out);
+      if (rows < 0)
+      {
+        const char* e = sdft_hip_last_error();
+        throw std::runtime_error(std::string("sdft_hip_sdft_cross_sum_n: ") + (e ? e : "failed"));
       }
       return static_cast<std::size_t>(rows);
     }

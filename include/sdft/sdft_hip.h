@@ -263,6 +263,56 @@ long sdft_hip_sdft_filterbank_n(sdft_t* sdft, const sdft_size_t nsamples, const 
                                 const sdft_size_t every, const sdft_size_t first,
                                 sdft_fd_t* out) SDFT_HIP_SYMBOL(sdft_filterbank_n);
 
+/* ---- pooled cross-spectrum analysis ----------------------------------------------------------------
+   What relates the channels of a batched plan (sdft_hip_alloc_batch): the cross power spectral density
+     S_ab[k] = sum over the samples t of a window of X_a[t][k] * conj(X_b[t][k])
+   over Welch windows, without storing the complex rows of either channel.  With the auto-spectra S_aa and S_bb it gives
+   coherence, transfer-function estimates, GCC-PHAT delays and the spatial covariance a beamformer needs.
+   A list of channel pairs belongs to the plan.  sdft_hip_set_pairs installs (copies) one; both arrays are HOST memory.  Pairs may
+   repeat, come in any order and have a == b (the auto-spectrum), so one call delivers S_aa, S_bb and S_ab from the same rows; a
+   single-channel plan accepts only (0, 0).  npairs == 0 removes the list.  Returns 0, or -1 with sdft_hip_last_error() set and
+   the previous list untouched: a NULL plan, a NULL array with npairs > 0, a channel index >= channels, more than 2^31 pairs.
+   sdft_hip_pairs: the installed list's length, 0 for none or a NULL plan.
+   Cost: every pair steps the recurrences of its two channels (one for a == b), so P pairs cost up to 2 P channels of
+   sdft_hip_sdft_power_sum_n; a channel in no pair is stepped once more to keep its state.  The call is built for a few pairs per
+   channel, not for an all-pairs covariance of many channels. */
+int         sdft_hip_set_pairs(sdft_t* sdft, const sdft_size_t npairs,
+                               const sdft_size_t* pair_a, const sdft_size_t* pair_b) SDFT_HIP_SYMBOL(set_pairs);
+sdft_size_t sdft_hip_pairs(const sdft_t* sdft) SDFT_HIP_SYMBOL(pairs);
+/* sdft_hip_sdft_cross_sum_n takes its grid, windows, head row, row count, streaming rule and the next call's first from
+   sdft_hip_sdft_power_sum_n, unchanged: rows = (first > 0 && nsamples > 0 ? 1 : 0) + (rows of sdft_hip_sdft_every_n); sums are
+   returned, not means; with first > 0, row 0 completes the previous call's last row (the host adds the two).
+   Let A = (ar, ai) and B = (br, bi) be the windowed, weighted bins of the channels a and b of a pair as sdft_sdft_n stores them
+   at sample t.  The term is A * conj(B), formed in sdft_fd_t with no fused multiply-add:
+     re = fl( fl(ar*br) + fl(ai*bi) )        im = fl( fl(ai*br) - fl(ar*bi) )
+   Row r of pair p holds, for bin0 <= k < bin0 + nbins, the sum of these terms over the r-th window, each component accumulated
+   separately in sdft_fd_t; pieces of a window that a time chunk cuts are added in ascending time order (no floating-point
+   atomics).  sums is [npairs][rows][nbins] complex numbers (re, im), dense, aligned to sizeof(sdft_fd_t) only; samples is
+   [channels][nsamples].  samples and sums may each be host or device memory (option "async" applies to device pointers).
+   Six things are promised.
+   (1) The same plan, options and input give the same bits on every run.
+   (2) Pair (a, a) has im == +0 exactly (for finite bins), and its re is formed from the same terms as sdft_hip_sdft_power_n's
+       value: at every == 1, first == 0 it is that value bit for bit wherever the two calls start from the same carries -- on the
+       bit-identical routes of (4) always, elsewhere when both cut time into chunks of the same length ("last_chunk_len").
+   (3) Within one call, pair (b, a) is the complex conjugate of pair (a, b) bit for bit: the same re, im negated (as numbers: where
+       two products cancel exactly both hold +0).  A repeated pair gives identical bits.
+   (4) At every == 1, first == 0, each value is exactly the expression above on the two channels' sdft_sdft_n rows, wherever
+       that call is bit-identical to the reference: FD float, FD double with option "carry" = 1, calls shorter than 512 samples.
+   (5) Accuracy elsewhere on those bit-identical routes, per component: with L the window's length, u = 2^-24 (float) or 2^-53
+       (double), gamma_n = n u / (1 - n u), T = sum |term| in the reals over the sdft_fd_t terms and S their exact sum,
+       |sum - S| <= gamma_(L-1) T.  On the other routes the term deviation comes on top: the constant sdft_hip_sdft_power_n
+       documents, 2.1e-11, times max|X_a| * max|X_b| over the call, times L (that call's derivation with |A||dB| + |B||dA| in
+       place of 2|X||dX|).
+   (6) The stream state afterwards is the one sdft_sdft_n of the same samples leaves for EVERY channel of the plan, whether it
+       appears in no pair, in one or in many.  Any other entry point may follow.
+   The call is never resident, pipelined or fused and always runs its own kernel ("last_kernel" = 8).  Returns the number of rows
+   written (0 for nsamples == 0), or -1 with sdft_hip_last_error() set and the stream state untouched: a NULL plan, no pairs
+   installed, every == 0, nbins == 0, bin0 + nbins > dftsize, or sums == NULL with rows > 0. */
+long sdft_hip_sdft_cross_sum_n(sdft_t* sdft, const sdft_size_t nsamples, const sdft_td_t* samples,
+                               const sdft_size_t every, const sdft_size_t first,
+                               const sdft_size_t bin0, const sdft_size_t nbins,
+                               sdft_fdx_t* sums) SDFT_HIP_SYMBOL(sdft_cross_sum_n);
+
 /* ---- streams ---------------------------------------------------------------------------------
    Every plan owns a HIP stream.  Calls with host pointers always return with the output
    complete.  Calls with device pointers do too unless option "async" is 1; then they return after
@@ -377,7 +427,7 @@ double sdft_hip_time_hops(sdft_t* sdft, size_t hops, size_t hop, const sdft_td_t
    "relay_flow", "relay_groups", "chain_debug", "inverse_nt", "inverse_nt_skip_mb", "inverse_step", "inverse_ordered", "host_direct", "copy_streams", "prefix_cells" (sdft_capi.inc names what each selects);
    get_option "test_hooks" = 1 in that build.
    get_option additionally answers "tiles", "bins_per_lane", "row_slots", "last_chunks",
-   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis, 6 pooled power analysis, 7 filterbank analysis), "last_segments", "last_fused",
+   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis, 6 pooled power analysis, 7 filterbank analysis, 8 pooled cross-spectrum analysis), "last_segments", "last_fused",
    "last_filterbank_launches" (forward_filterbank_kernel launches of the last filterbank call, over all of its host segments: more than its carry segments once its pieces exceed the workspace bound),
    "last_chain", "last_fused_exact", "last_fused_fold", "last_process_path" (1 fused kernel, 2 hop pair, 3 two-pass),
    "last_self" (no pre-pass launch), "last_prefix" (long calls: one pre-pass launch, prefix_cells_kernel), "last_inverse_nt" / "last_inverse_skip" (what the last synthesis launch used: non-temporal loads, rows read with ordinary loads),

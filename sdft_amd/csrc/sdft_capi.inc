@@ -123,6 +123,21 @@ long SDFT_FN(sdft_filterbank_n)(void* p, size_t n, const SDFT_TD* x, size_t ever
   if (rows > (size_t)LONG_MAX) { sdfthip::set_error("sdft_hip_sdft_filterbank_n", "more rows than a long can count"); return -1; }
   return (long)rows;
 }
+// pooled cross-spectrum analysis: A conj(B) of the plan's channel pairs summed over the windows of the grid; see sdft_hip.h
+int SDFT_FN(set_pairs)(void* p, size_t npairs, const size_t* pair_a, const size_t* pair_b)
+{
+  if (!p) { sdfthip::set_error("sdft_hip_set_pairs", "NULL plan"); return -1; }
+  return P(p)->set_pairs(npairs, pair_a, pair_b) ? 0 : -1;
+}
+size_t SDFT_FN(pairs)(const void* p) { return p ? P(p)->pairs_count() : 0; }
+long SDFT_FN(sdft_cross_sum_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, size_t bin0, size_t nbins, SDFT_FD* sums)
+{
+  if (!p) { sdfthip::set_error("sdft_hip_sdft_cross_sum_n", "NULL plan"); return -1; }
+  size_t rows = 0;
+  if (!P(p)->sdft_cross_sum_n(n, x, every, first, bin0, nbins, sums, rows)) return -1;
+  if (rows > (size_t)LONG_MAX) { sdfthip::set_error("sdft_hip_sdft_cross_sum_n", "more rows than a long can count"); return -1; }
+  return (long)rows;
+}
 int SDFT_FN(set_stream)(void* p, void* hip_stream) { return p && P(p)->set_stream(static_cast<hipStream_t>(hip_stream)) ? 0 : -1; }
 // (a host that asks for the stream may queue work of its own behind a call: from here on every kernel of the plan is on it)
 void* SDFT_FN(get_stream)(void* p)

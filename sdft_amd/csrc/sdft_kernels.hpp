@@ -16,6 +16,8 @@
 //   sdft_forward_power_sum.hpp K1s forward_pooled_power_kernel: that power at every sample, summed in registers over the windows of the
 //                          grid, one store per window; pooled_power_rows_kernel adds the pieces of the windows a chunk boundary cuts
 //                          (sdft_hip_sdft_power_sum_n)
+//   sdft_forward_cross_sum.hpp K1x forward_cross_sum_kernel: the pooled power kernel with a second channel -- A conj(B) of the windowed
+//                          bins of two channels of a plan, summed in registers over the windows of the grid (sdft_hip_sdft_cross_sum_n)
 //   sdft_forward_filterbank.hpp K1f forward_filterbank_kernel: the powers of a kept row go to a wave-private strip of LDS and the lanes
 //                          form the weighted sums of the pieces of the plan's bands that lie in the tile; filterbank_rows_kernel adds
 //                          the pieces of the bands a tile boundary cuts (sdft_hip_sdft_filterbank_n)
@@ -51,6 +53,7 @@
 #include "sdft_forward_every.hpp"
 #include "sdft_forward_power.hpp"
 #include "sdft_forward_power_sum.hpp"
+#include "sdft_forward_cross_sum.hpp"
 #include "sdft_forward_filterbank.hpp"
 #include "sdft_forward_hop.hpp"
 #include "sdft_ops.hpp"

@@ -373,6 +373,121 @@
       return true;
     });
   }
+  // ---- pooled cross-spectrum analysis ------------------------------------------------------------------------------------------
+  // sdft_hip_set_pairs: the arrays are host memory and are copied; a refused list leaves the installed one as it is.  The work
+  // items of the list (logic::cross_items) go to the device once, here.
+  bool set_pairs(size_t npairs, const size_t* pair_a, const size_t* pair_b)
+  {
+    static const char* fn = "sdft_hip_set_pairs";
+    switch (logic::cross_pairs_check(channels, npairs, pair_a, pair_b))
+    {
+      case logic::CX_OK: break;
+      case logic::CX_NULL: set_error(fn, "pair_a or pair_b is NULL but npairs is not 0"); return false;
+      case logic::CX_CHANNEL: set_error(fn, "a pair names a channel the plan does not have (index >= channels)"); return false;
+      default: set_error(fn, "the list is too long: more than 2^31 pairs"); return false;
+    }
+    if (!bind()) return false;
+    if (!pipe_join()) return false;
+    Pairs f;
+    if (npairs)
+    {
+      f.a.assign(pair_a, pair_a + npairs);
+      f.b.assign(pair_b, pair_b + npairs);
+      f.items = logic::cross_items(channels, npairs, pair_a, pair_b);
+      // (a fresh table: whatever still reads the installed one has drained before it is replaced, and a failure leaves it alone)
+      DevBuf<CrossItem> table;
+      SDFT_TRY(hipStreamSynchronize(stream));
+      if (!table.reserve(f.items.size())) return false;
+      static_assert(sizeof(CrossItem) == sizeof(logic::CrossItem), "one table for the host and the kernel");
+      if (!to_device(table.p, f.items.data(), f.items.size() * sizeof(CrossItem)) || hipStreamSynchronize(stream) != hipSuccess) { table.release(); return false; }
+      d_cross_items.release();
+      d_cross_items = table;
+    }
+    else SDFT_TRY(hipStreamSynchronize(stream));
+    pairs = std::move(f);
+    return true;
+  }
+  size_t pairs_count() const { return pairs.a.size(); }
+
+  // pooled cross-spectrum analysis (sdft_hip_sdft_cross_sum_n): per pair (a, b) of the installed list the sums of A conj(B) over the
+  // windows of sdft_power_sum_n's grid, dense [npairs][rows][nbins_out] complex numbers, row 0 the head window [0, first) when
+  // first > 0.  State, pointers and launches as sdft_power_sum_n: never resident, pipelined or fused, forward_cross_sum_kernel on
+  // the plan's stream, then pooled_power_rows_kernel for the windows a chunk boundary cut.  Host memory goes in time segments
+  // through device scratch; each segment is a call of its own under the streaming contract, with its own first: the head rows of
+  // a later segment are kept apart (d_cross_head) and added to the rows the segment before it ended with, on the host for a host
+  // buffer, by pooled_power_add_kernel for a device buffer.  The matrix side of a segment is per PAIR, not per channel, so it
+  // does not go through staged_segments' own copy (which is per channel): the sums of a host buffer pass d_cross_stage here.
+  bool sdft_cross_sum_n(size_t n, const TD* x, size_t every, size_t first, size_t bin0, size_t nbins_out, FD* sums, size_t& rows)
+  {
+    static const char* fn = "sdft_hip_sdft_cross_sum_n";
+    rows = 0;
+    const size_t npairs = pairs_count();
+    if (npairs == 0) { set_error(fn, "no pairs are installed (sdft_hip_set_pairs)"); return false; }
+    if (every == 0) { set_error(fn, "every must be at least 1"); return false; }
+    if (nbins_out == 0) { set_error(fn, "nbins must be at least 1"); return false; }
+    if (!logic::power_band_ok(nbins, bin0, nbins_out)) { set_error(fn, "the band bin0 ... bin0 + nbins - 1 does not lie within the plan's bins"); return false; }
+    rows = logic::power_sum_rows(n, every, first);
+    if (rows > 0 && !sums) { set_error(fn, "sums is NULL but the call writes rows"); return false; }
+    if (n == 0) return true;
+    if (!bind()) return false;
+    if (!pipe_join()) return false;
+    if (every > n) every = n;                                // (the same windows; keeps first + k * every in range)
+    const bool xd = on_device(x);
+    const bool od = on_device(sums);
+    const size_t nb2 = 2 * nbins_out;                        // numbers of a row of one pair
+    const size_t row_bytes = npairs * nb2 * sizeof(FD);
+    auto band = [&](FD* row0, size_t row0_stride, FD* rest, size_t rest_stride, size_t f) {
+      return CrossSumArgs<FD>{row0, row0_stride, rest, rest_stride, nullptr, d_cross_items.p, (unsigned)pairs.items.size(), (unsigned)npairs,
+                              (unsigned long long)every, (unsigned long long)f, (unsigned)bin0, (unsigned)nbins_out};
+    };
+    const size_t stride = logic::cross_pair_stride(rows, nbins_out);
+    if (xd && od)
+    {
+      const CrossSumArgs<FD> g = band(sums, stride, sums + nb2, stride, first);
+      return forward_device(n, x, n, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &g) && finish(rows * row_bytes);
+    }
+    // host memory: segments of at most seg samples (rows written and samples within stage_bytes); where the grid allows it, of
+    // whole windows, so that no row is made of two segments
+    size_t seg = n;
+    if (!od) seg = std::min(seg, logic::stage_rows(n, row_bytes, stage_bytes) * every);
+    if (!xd) seg = std::min(seg, std::max<size_t>((size_t)logic::kHopSamples, logic::stage_rows(n, channels * sizeof(TD), stage_bytes)));
+    if (seg < n && seg > every && first % every == 0) seg -= seg % every;
+    const size_t seg_rows_max = (seg + every - 1) / every + 1;
+    if (!od && !d_cross_stage.reserve(npairs * seg_rows_max * nb2)) return false;
+    std::vector<FD> head;                                    // host buffers: a segment's head rows on their way to the rows they complete
+    return staged_segments(n, seg, StagedCall{true, const_cast<TD*>(x), !xd, nullptr, false, rows, seg_rows_max, nb2 * sizeof(FD)}, [&](Segment& s) {
+      const size_t f = logic::every_first_from(s.t, every, first);
+      const logic::PowerSumWindow w0 = logic::power_sum_window(s.t, n, every, first);      // of the segment's row 0 in the call
+      const bool joins = w0.begin < s.t;                     // row 0 is a head: it completes row w0.row of the call
+      const size_t seg_rows = logic::power_sum_rows(s.m, every, f), kept = seg_rows - (joins ? 1 : 0);
+      if (joins && !d_cross_head.reserve(npairs * nb2)) return false;
+      const size_t r0 = w0.row + (joins ? 1 : 0);            // the segment's first row of its own
+      s.rows = 0;                                            // (nothing for staged_segments to copy)
+      FD* const at = od ? sums + r0 * nb2 : d_cross_stage.p; // scratch: [npairs][kept][nbins_out] complex
+      const size_t at_stride = od ? stride : kept * nb2;
+      const CrossSumArgs<FD> g = joins ? band(d_cross_head.p, nb2, at, at_stride, f) : band(at, at_stride, at + nb2, at_stride, f);
+      if (!forward_device(s.m, s.td, s.td_stride, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &g)) return false;
+      if (od)
+      {
+        if (!joins) return true;
+        const unsigned long long threads = (unsigned long long)npairs * nb2;
+        hipLaunchKernelGGL((pooled_power_add_kernel<FD>), dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
+                           sums + w0.row * nb2, stride, d_cross_head.p, (unsigned)nb2, (unsigned)npairs);
+        SDFT_TRY(hipGetLastError());
+        return true;
+      }
+      for (size_t p = 0; p < npairs && kept; ++p)
+        if (!to_host(sums + p * stride + r0 * nb2, d_cross_stage.p + p * kept * nb2, kept * nb2 * sizeof(FD))) return false;
+      if (!joins) return true;
+      head.resize(npairs * nb2);
+      if (!to_host(head.data(), d_cross_head.p, head.size() * sizeof(FD))) return false;
+      SDFT_TRY(hipStreamSynchronize(stream));
+      for (size_t p = 0; p < npairs; ++p)
+        for (size_t k = 0; k < nb2; ++k) sums[p * stride + w0.row * nb2 + k] += head[p * nb2 + k];
+      return true;
+    });
+  }
+
   // a host table of device rows goes to the device; nullptr: failed
   fdx* const* device_table(fdx* const* dfts, size_t n, bool table_on_device)
   {

@@ -354,13 +354,26 @@
     hipLaunchKernelGGL((filterbank_rows_kernel<FD>), dim3((unsigned)blocks), dim3(kBlock), 0, stream, g, (unsigned)channels);
     return true;
   }
-  // the rows of the windows a chunk boundary cuts, from their pieces in the workspace (chunks > 1)
-  bool launch_power_sum_rows(const PowerSumArgs<FD>& g, size_t n, long chunks, long len, long shift)
+  void launch_forward_cross_sum(const ForwardArgs<FD>& fa, const CrossSumArgs<FD>& g, unsigned blocks)
   {
-    const unsigned long long threads = (unsigned long long)channels * (unsigned long long)(chunks - 1) * g.nbins_out;
+    constexpr int BPL = sizeof(fdx) == 16 ? 1 : 2;
+    const dim3 gr(blocks), b(kBlock);
+    switch (window)
+    {
+      case WIN_HANN:     hipLaunchKernelGGL((forward_cross_sum_kernel<FD, BPL, WIN_HANN>), gr, b, 0, stream, fa, g); break;
+      case WIN_HAMMING:  hipLaunchKernelGGL((forward_cross_sum_kernel<FD, BPL, WIN_HAMMING>), gr, b, 0, stream, fa, g); break;
+      case WIN_BLACKMAN: hipLaunchKernelGGL((forward_cross_sum_kernel<FD, BPL, WIN_BLACKMAN>), gr, b, 0, stream, fa, g); break;
+      default:           hipLaunchKernelGGL((forward_cross_sum_kernel<FD, BPL, WIN_BOXCAR>), gr, b, 0, stream, fa, g); break;
+    }
+  }
+  // the rows of the windows a chunk boundary cuts, from their pieces in the workspace (chunks > 1); nch: the plan's channels, or the
+  // pairs of a cross-spectrum call
+  bool launch_power_sum_rows(const PowerSumArgs<FD>& g, size_t n, long chunks, long len, long shift, size_t nch)
+  {
+    const unsigned long long threads = (unsigned long long)nch * (unsigned long long)(chunks - 1) * g.nbins_out;
     const unsigned long long blocks = (threads + kBlock - 1) / kBlock;
     if (!grid_fits(blocks)) return false;
-    hipLaunchKernelGGL((pooled_power_rows_kernel<FD>), dim3((unsigned)blocks), dim3(kBlock), 0, stream, g, n, (unsigned)chunks, (unsigned)len, (unsigned)shift, (unsigned)channels);
+    hipLaunchKernelGGL((pooled_power_rows_kernel<FD>), dim3((unsigned)blocks), dim3(kBlock), 0, stream, g, n, (unsigned)chunks, (unsigned)len, (unsigned)shift, (unsigned)nch);
     return true;
   }
 

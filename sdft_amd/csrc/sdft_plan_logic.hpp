@@ -297,6 +297,57 @@ inline PowerSumRowChunks power_sum_row_chunks(const PowerSumWindow& w, long len,
 // bin for pooled_power_rows_kernel) 1.495 against 1.712 / 1.577 / 1.556 / 1.637 / 1.845 / 2.343 ms (profiles/power_sum_rates.txt).
 inline Chunking choose_power_sum_chunks(const EveryQuery& q) { return choose_power_chunks(q, 1); }
 
+// ---- pooled cross-spectrum analysis (sdft_hip_sdft_cross_sum_n) ------------------------------------------------------------------
+// Row r of pair p = (a, b) is the sum over the r-th window of the pooled power call's grid of A conj(B), A and B the windowed bins
+// of the channels a and b.  A wave of forward_cross_sum_kernel steps the recurrences of the two channels of ONE work item, so the
+// pair list becomes a table of items, once per sdft_hip_set_pairs: item p < npairs is pair p (out = p); after them comes one
+// advance-only item {c, c, none} for every channel c that no pair names, so that every channel's state moves with the call.
+// Exactly one item and side per channel writes that channel's state back: the first item that names it, side a before side b.
+// (P pairs step up to 2P recurrences: a channel that is in many pairs is stepped once per pair.)
+constexpr int kCrossNone = -1;
+struct CrossItem
+{
+  unsigned a, b;
+  int out;                                // the pair whose sums the item forms, kCrossNone: it only advances channel a (== b)
+  unsigned short writes_a, writes_b;      // this side stores its channel's state on the last chunk
+};
+enum CrossCheck : int { CX_OK = 0, CX_NULL = 1, CX_CHANNEL = 2, CX_TOO_MANY = 3 };
+// a pair list sdft_hip_set_pairs may install (npairs == 0 removes the list)
+inline int cross_pairs_check(size_t channels, size_t npairs, const size_t* pair_a, const size_t* pair_b)
+{
+  if (npairs == 0) return CX_OK;
+  if (!pair_a || !pair_b) return CX_NULL;
+  if (npairs > ((size_t)1 << 31)) return CX_TOO_MANY;
+  const size_t ch = std::max<size_t>(channels, 1);
+  for (size_t p = 0; p < npairs; ++p)
+    if (pair_a[p] >= ch || pair_b[p] >= ch) return CX_CHANNEL;
+  return CX_OK;
+}
+// (of a list cross_pairs_check has passed)
+inline std::vector<CrossItem> cross_items(size_t channels, size_t npairs, const size_t* pair_a, const size_t* pair_b)
+{
+  const size_t ch = std::max<size_t>(channels, 1);
+  std::vector<CrossItem> items;
+  std::vector<char> written(ch, 0);
+  items.reserve(npairs + ch);
+  for (size_t p = 0; p < npairs; ++p)
+  {
+    CrossItem it{(unsigned)pair_a[p], (unsigned)pair_b[p], (int)p, 0, 0};
+    if (!written[it.a]) { it.writes_a = 1; written[it.a] = 1; }
+    if (!written[it.b]) { it.writes_b = 1; written[it.b] = 1; }      // (a == b: side a has taken it)
+    items.push_back(it);
+  }
+  for (size_t c = 0; c < ch; ++c)
+    if (!written[c]) items.push_back(CrossItem{(unsigned)c, (unsigned)c, kCrossNone, 1, 0});
+  return items;
+}
+// The workspace of the windows a chunk boundary cuts: power_sum_workspace / power_sum_slot with items for channels and, a complex
+// sum being two real ones, 2 * nbins_out numbers for nbins_out (advance-only items come last and use none of it)
+inline size_t cross_sum_workspace(size_t items, size_t chunks, size_t nbins_out) { return power_sum_workspace(items, chunks, 2 * nbins_out); }
+inline size_t cross_sum_slot(size_t item, size_t chunks, size_t chunk, int slot, size_t nbins_out) { return power_sum_slot(item, chunks, chunk, slot, 2 * nbins_out); }
+// numbers (not complex numbers) from one pair's first sum to the next pair's
+inline size_t cross_pair_stride(size_t rows, size_t nbins_out) { return power_channel_stride(rows, 2 * nbins_out); }
+
 // ---- filterbank analysis (sdft_hip_sdft_filterbank_n) --------------------------------------------------------------------------
 // Band b of a filterbank covers the bins [band_bin0[b], band_bin0[b] + band_nbins[b]) with one weight per bin; row r of the output
 // holds, per band, the sum of fl(weight * power) over the band's bins, the powers those sdft_hip_sdft_power_n stores for the row.
@@ -765,6 +816,8 @@ struct ForwardQuery
   size_t power_every = 1;                 // ... every power_every-th sample
   bool power_sum = false;                 // pooled power analysis (forward_pooled_power_kernel)
   bool filterbank = false;                // filterbank analysis (forward_filterbank_kernel) on the grid of power_every
+  bool cross_sum = false;                 // pooled cross-spectrum analysis (forward_cross_sum_kernel) of ...
+  size_t cross_items = 0;                 // ... this many work items (logic::cross_items), which take the channels' place in the launch
   bool row_pointers = false;              // rows go to a table of row pointers
   uintptr_t out = 0; size_t out_stride = 0;
   bool analysis_batch = false;            // CallPattern: analyses come call after call
@@ -775,7 +828,7 @@ struct ForwardQuery
        chain_L = 0, relay_flow = 1, segments = 0, xcd_map = 1, rows_f32 = 1, pipeline = 1;
   long prefix_cells = 1;                  // test hook: 0 = never the prefix-cell route, 1 = calls beyond kSelfMax, 2 = whatever the length
 };
-enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6, FK_FILTERBANK = 7 };     // = get_option "last_kernel"
+enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6, FK_FILTERBANK = 7, FK_CROSS_SUM = 8 };     // = get_option "last_kernel"
 // carries: the single chunk's are the stream state (delta_kernel copies it); pre-pass partial sums + scan (carries from the
 // closed-form table); the serial exact pass (carry_exact_kernel); the relay form of the exact pass (carry_relay_kernel)
 enum CarryForm : int { CARRY_STATE = 0, CARRY_SUMS = 1, CARRY_SERIAL = 2, CARRY_RELAY = 3 };
@@ -823,8 +876,10 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   ForwardRoute r;
   const size_t nb = q.nbins, span = 2 * nb, n = q.n, ch = std::max<size_t>(q.channels, 1);
   const bool pow2 = (span & (span - 1)) == 0;
-  // the decimated, the power-spectrogram, the pooled power and the filterbank analysis have the tile form only
-  const bool grid = q.every || q.power || q.power_sum || q.filterbank;
+  // the decimated, the power-spectrogram, the pooled power, the filterbank and the cross-spectrum analysis have the tile form only
+  const bool grid = q.every || q.power || q.power_sum || q.filterbank || q.cross_sum;
+  // (channel, chunk) groups of a tile launch per chunk: the cross-spectrum call's are its work items
+  const size_t lanes = q.cross_sum ? std::max<size_t>(q.cross_items, 1) : ch;
   const bool rows = !grid && rows_kernel_ok(nb, q.fdx_bytes, q.row_pointers, q.rows_kernel != 0, q.row_slots_max);
   const bool folded = q.fuse && !q.reference_order && !q.fuse_store && q.fold && q.coeff_ready;
   // pipelined calls (forward_self): decided first because they take the self-carried form at any length and cut time differently
@@ -849,13 +904,13 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   if (grid)
   {
     EveryQuery e;
-    e.n = n; e.channels = ch; e.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); e.exact = q.exact; e.forced_chunk = q.chunk; e.compute_units = q.compute_units;
-    c = q.power_sum ? choose_power_sum_chunks(e) : (q.power || q.filterbank) ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
+    e.n = n; e.channels = lanes; e.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); e.exact = q.exact; e.forced_chunk = q.chunk; e.compute_units = q.compute_units;
+    c = (q.power_sum || q.cross_sum) ? choose_power_sum_chunks(e) : (q.power || q.filterbank) ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
   }
   else c = choose_chunks(chunk_query(q, rows, r.pipelined));
   r.chunks = c.chunks; r.len = c.len;
   r.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); r.interior = interior_lanes(q.window, q.fdx_bytes, q.interior);
-  r.kernel = q.filterbank ? FK_FILTERBANK : q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
+  r.kernel = q.cross_sum ? FK_CROSS_SUM : q.filterbank ? FK_FILTERBANK : q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
   if (r.chunks == 1 && q.hop_kernel && nb >= 2 && !q.fuse && !grid) { r.kernel = FK_HOP; return r; }
 
   // self-carried chunks: every workgroup derives its carry-in from the raw samples (fold + one FFT in LDS) and forms
@@ -909,7 +964,7 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   {
     // time segments: the serial pass of segment s+1 (few waves, latency-bound) runs on the side stream while the forward kernel
     // of segment s streams the matrix; up to 8 segments, each forward launch still filling the chip (>= 256 workgroups)
-    const long launch_blocks = rows ? (long)ch * r.chunks : (long)ch * r.chunks * r.tiles / kWavesPerBlock;
+    const long launch_blocks = rows ? (long)ch * r.chunks : (long)lanes * r.chunks * r.tiles / kWavesPerBlock;
     r.segments = q.segments > 0 ? q.segments : std::max(1L, std::min(8L, launch_blocks / 256));
     // Relay form, flow mode: ONE relay launch for the whole call on the side stream and ONE forward launch whose workgroups wait
     // for their chunk's carries themselves (ForwardArgs::ready).  With segments and events the two passes barely overlap:

@@ -45,6 +45,7 @@ class SDFT:
         self.api = Api(combo, hooks=hooks)
         self._options = []                                   # (key, value) set so far, and the caller's stream: replayed when the plan moves
         self._stream = None
+        self._pairs = None                                   # the pair list of set_pairs, likewise
         self.combo = combo
         self.td = _NP_REAL[combo[:3]]
         self.fd = _NP_REAL[combo[3:]]
@@ -115,6 +116,8 @@ class SDFT:
                     self.set_state(acc, fid, hist, cursor)
                 if self._stream is not None:
                     self.set_stream(self._stream)
+                if self._pairs is not None:                      # (the installed pair list moves with the plan)
+                    self.set_pairs(*self._pairs)
                 self._options.append((key, int(value)))
                 return
             if q:
@@ -346,6 +349,73 @@ class SDFT:
         if got < 0:
             self.api.check()
             raise SdftHipError("sdft_hip_sdft_filterbank_n failed")
+        self.api.check()
+        assert got == rows, (got, rows)
+        return out
+
+    def set_pairs(self, a, b):
+        """Installs a list of channel pairs in the plan (``sdft_hip_set_pairs``; the arrays are copied): pair p is the channels
+        ``(a[p], b[p])``.  Pairs may repeat, come in any order and have ``a == b`` (the auto-spectrum).  No pairs removes the list."""
+        self.api.clear()
+        try:
+            pa = np.ascontiguousarray(a, dtype=np.uint64).ravel()
+            pb = np.ascontiguousarray(b, dtype=np.uint64).ravel()
+        except OverflowError as e:
+            raise ValueError(f"channel indices must not be negative: {e}") from None
+        if pa.size != pb.size:
+            raise ValueError(f"a and b must have one entry per pair, got {pa.size} and {pb.size}")
+        rc = self.api.set_pairs(self._p, pa.size, C.c_void_p(pa.ctypes.data), C.c_void_p(pb.ctypes.data))
+        if rc != 0:
+            self.api.check()
+            raise SdftHipError("sdft_hip_set_pairs failed")
+        self.api.check()
+        self._pairs = (pa, pb) if pa.size else None
+
+    @property
+    def pairs(self) -> int:
+        """Pairs of the installed list (``sdft_hip_pairs``), 0 for none."""
+        return int(self.api.pairs(self._p))
+
+    def cross_sum(self, x, every: int = 1, first: int = 0, bins=None, out=None):
+        """Pooled cross-spectrum analysis (``sdft_hip_sdft_cross_sum_n``): per pair ``(a, b)`` of the installed list
+        (:meth:`set_pairs`) the sum of ``X_a * conj(X_b)`` over the windows :meth:`power_sum` cuts the n samples into, for the bins
+        ``bins = (bin0, nbins)`` (``None``: all) -> complex array of shape (npairs, rows, nbins), ``rows = power_sum_rows(n, every,
+        first)``, numpy for numpy input, a device tensor for a device tensor.  ``x`` is (channels, n) [(n,) for a single-channel
+        plan].  Head row, streaming and sums-not-means as with :meth:`power_sum`.  The state of every channel of the plan advances
+        over all n samples and all bins, as with :meth:`sdft`."""
+        self.api.clear()
+        every, first = int(every), int(first)
+        bin0, nb = (0, self.dftsize) if bins is None else (int(bins[0]), int(bins[1]))
+        if every < 1 or first < 0:
+            raise ValueError(f"every must be >= 1 and first >= 0, got every={every}, first={first}")
+        if bin0 < 0 or nb < 1 or bin0 + nb > self.dftsize:
+            raise ValueError(f"bins = (bin0, nbins) must select at least one of the {self.dftsize} bins, got {(bin0, nb)}")
+        npairs = self.pairs
+        if npairs == 0:
+            raise ValueError("no pairs are installed: call set_pairs first")
+        cdtype = np.dtype(np.complex64 if np.dtype(self.fd) == np.float32 else np.complex128)
+        if _is_tensor(x):
+            torch = _torch()
+            n = self._shape_x(x.shape)
+            self._check_tensor(x, "samples", self.td)
+            rows = power_sum_rows(n, every, first)
+            shape = (npairs, rows, nb)
+            if out is None:
+                out = torch.empty(shape, dtype=getattr(torch, cdtype.name), device=x.device)
+            self._check_tensor(out, "out", cdtype, shape)
+            got = self.api.sdft_cross_sum_n(self._p, n, C.c_void_p(x.data_ptr()), every, first, bin0, nb, C.c_void_p(out.data_ptr() if rows else None))
+        else:
+            x = np.ascontiguousarray(x, dtype=self.td)
+            n = self._shape_x(x.shape)
+            rows = power_sum_rows(n, every, first)
+            shape = (npairs, rows, nb)
+            if out is None:
+                out = np.empty(shape, dtype=cdtype)
+            assert out.flags.c_contiguous and out.shape == shape and out.dtype == cdtype
+            got = self.api.sdft_cross_sum_n(self._p, n, C.c_void_p(x.ctypes.data), every, first, bin0, nb, C.c_void_p(out.ctypes.data if rows else None))
+        if got < 0:
+            self.api.check()
+            raise SdftHipError("sdft_hip_sdft_cross_sum_n failed")
         self.api.check()
         assert got == rows, (got, rows)
         return out
