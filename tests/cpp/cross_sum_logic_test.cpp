@@ -178,12 +178,95 @@ static void test_route()
   CHECK(FK_CROSS_SUM == 8, "get_option(\"last_kernel\") answers 8");
 }
 
+// The carry forms of the shapes tests/test_gpu_cross_sum_routes.py runs on the GPU (4 channels, the 6 pairs of PAIRS and one
+// advance-only item, n = 6000): what its assertions on last_chain, last_segments and last_chunk_len rest on.
+static ForwardQuery gpu_test_query(size_t nbins, bool f32, size_t n, size_t cursor)
+{
+  ForwardQuery q;
+  q.n = n; q.nbins = nbins; q.channels = 4; q.fd_bytes = f32 ? 4 : 8; q.fdx_bytes = f32 ? 8 : 16;
+  q.window = kWindowHann; q.cursor = cursor; q.exact = true; q.fid_canonical = true;
+  q.cross_sum = true; q.cross_items = 7;
+  return q;
+}
+static ForwardRoute route_of(const ForwardQuery& q)
+{
+  bool asked = false;
+  const ForwardRoute r = forward_route(q, [&] { asked = true; return true; });
+  CHECK(r.kernel == FK_CROSS_SUM && !r.flow && !asked, "N %zu: never the flow form", q.nbins);
+  return r;
+}
+static void test_carry_forms()
+{
+  for (int f32 = 0; f32 < 2; ++f32)
+  {
+    // N = 125: no block length (8 ... 128) divides 2N = 250, so the exact carries are the serial pass whatever option chain says
+    for (long chain : {0L, 1L, 2L})
+      for (long chunk : {0L, 128L})
+      {
+        ForwardQuery q = gpu_test_query(125, f32, 6000, 0); q.chain = chain; q.chunk = chunk;
+        const ForwardRoute r = route_of(q);
+        CHECK(r.chunks > 1 && r.carry == CARRY_SERIAL && r.relay_L == 0 && r.shift == 0 && r.use_seed, "N 125, chain %ld, chunk %ld: carry %d, L %u", chain, chunk, r.carry, r.relay_L);
+      }
+    // N = 1000: the relay form by default, with chain = 2, with forced chunks and in forced segments; chunks begin on block boundaries
+    for (long chain : {1L, 2L})
+      for (long chunk : {0L, 128L, 1000L})
+        for (long segments : {0L, 3L})
+          for (size_t cursor : {(size_t)0, (size_t)700, (size_t)1500})
+          {
+            const size_t n = 6000 - cursor;
+            ForwardQuery q = gpu_test_query(1000, f32, n, cursor); q.chain = chain; q.chunk = chunk; q.segments = segments;
+            const ForwardRoute r = route_of(q);
+            CHECK(r.carry == CARRY_RELAY && r.relay_L >= 8 && r.use_seed, "N 1000, chain %ld, chunk %ld, cursor %zu: carry %d", chain, chunk, cursor, r.carry);
+            if (r.carry != CARRY_RELAY) continue;
+            CHECK(2000 % r.relay_L == 0 && r.len % (long)r.relay_L == 0, "block %u, chunks of %ld", r.relay_L, r.len);
+            CHECK(r.shift == cursor % r.relay_L && (cursor == 0) == (r.shift == 0), "cursor %zu, block %u: shift %u", cursor, r.relay_L, r.shift);
+            CHECK(r.chunks > 1 && (size_t)r.chunks * (size_t)r.len >= n + r.shift && (size_t)(r.chunks - 1) * (size_t)r.len < n + r.shift, "%ld chunks of %ld for %zu + %u", r.chunks, r.len, n, r.shift);
+            if (chunk) CHECK(r.len == chunk, "forced chunk %ld: %ld", chunk, r.len);
+            if (segments) CHECK(r.segments == segments, "forced segments %ld: %ld", segments, r.segments);
+          }
+    // ... and the serial pass with chain = 0, and after sdft_hip_set_state (the fid is the host's: not the canonical rotation)
+    for (int installed = 0; installed < 2; ++installed)
+      for (size_t cursor : {(size_t)0, (size_t)1500})
+      {
+        ForwardQuery q = gpu_test_query(1000, f32, 6000 - cursor, cursor); q.chain = installed ? 1 : 0; q.fid_canonical = !installed;
+        const ForwardRoute r = route_of(q);
+        CHECK(r.chunks > 1 && r.carry == CARRY_SERIAL && r.relay_L == 0 && r.shift == 0 && r.use_seed, "N 1000, installed %d: carry %d", installed, r.carry);
+      }
+  }
+  // FD double with its default carries: partial sums + scan, the fid from the closed-form table
+  ForwardQuery q = gpu_test_query(125, false, 6000, 0); q.exact = false;
+  const ForwardRoute r = route_of(q);
+  CHECK(r.chunks > 1 && r.carry == CARRY_SUMS && !r.use_seed && r.segments == 1, "FD double, default carries: carry %d", r.carry);
+  // the 70-pair list of 5 channels (70 items: every channel is named), N = 64, n = 3000, and the lists of two and three pairs
+  for (size_t items : {(size_t)4, (size_t)3, (size_t)5, (size_t)70})
+    for (int f32 = 0; f32 < 2; ++f32)
+    {
+      ForwardQuery w = gpu_test_query(64, f32, 3000, 0); w.channels = 5; w.cross_items = items; w.exact = f32;
+      CHECK(route_of(w).chunks > 1, "%zu items, N 64, n 3000: one chunk", items);
+    }
+}
+
+// how stage_bytes bounds the segments of the staging tests (band of 100 bins, 6 pairs, 4 channels of float samples)
+static void test_stage_rows()
+{
+  for (size_t fd : {(size_t)4, (size_t)8})
+  {
+    const size_t row = 6 * 2 * 100 * fd;
+    CHECK(stage_rows(6000, row, 7 * row) == 7 && stage_rows(6000, row, 2 * row) == 2, "7 and 2 rows of sums");
+    CHECK(stage_rows(6000, row, 700 * 4 * 4) == (fd == 4 ? 2u : 1u), "700 samples' bytes hold %zu rows of sums", stage_rows(6000, row, 700 * 4 * 4));
+  }
+  CHECK(stage_rows(6000, 4 * 4, 700 * 4 * 4) == 700 && 700 > (size_t)kHopSamples, "700 samples of 4 channels: a segment bound by the samples' bytes");
+  CHECK(stage_rows(6000, 4 * 4, 1) == 1 && stage_rows(5, 16, 1 << 30) == 5 && stage_rows(0, 16, 64) == 1, "at least one row, at most the call's");
+}
+
 int main()
 {
   test_items();
   test_refusals();
   test_workspace();
   test_route();
+  test_carry_forms();
+  test_stage_rows();
   if (failures) { fprintf(stderr, "%d failures\n", failures); return 1; }
   printf("cross-sum-logic: all properties hold\n");
   return 0;

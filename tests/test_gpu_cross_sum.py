@@ -41,12 +41,12 @@ ALL_PAIRS = [(a, b) for a in range(CH) for b in range(CH)]
 assert np.finfo(np.longdouble).eps <= 2.0 ** -63, "the FD double reference needs an extended long double"
 
 
-def signals(td, n, seed):
-    x = np.empty((CH, n), dtype=td)
+def signals(td, n, seed, channels=CH):
+    """channel 1 is half of channel 0; every other channel c has a seed of its own, seed + 1000 (c - 1)"""
+    x = np.empty((channels, n), dtype=td)
     x[0] = signal(n, td, seed)
-    x[1] = x[0] * td(0.5)
-    x[2] = signal(n, td, seed + 1000)
-    x[3] = signal(n, td, seed + 2000)
+    for c in range(1, channels):
+        x[c] = x[0] * td(0.5) if c == 1 else signal(n, td, seed + 1000 * (c - 1))
     return x
 
 
@@ -58,19 +58,19 @@ def plan(m, window, combo, pairs=PAIRS, channels=CH, **opts):
 
 
 @functools.lru_cache(maxsize=2)
-def rows_of(combo, window, m, n, cols=None):
-    """(samples (4, n), the oracle's rows of every channel (4, n, columns)) of one shape; cols = (lo, hi) keeps those bins only.
-    Computed once, shared, never written"""
+def rows_of(combo, window, m, n, cols=None, channels=CH):
+    """(samples (channels, n), the oracle's rows of every channel (channels, n, columns)) of one shape; cols = (lo, hi) keeps those
+    bins only.  Computed once, shared, never written"""
     td, fd, _ = O.combo_types(combo)
-    x = signals(td, n, m)
+    x = signals(td, n, m, channels)
     lo, hi = cols if cols else (0, m)
     X = None
-    for c in range(CH):
+    for c in range(channels):
         ref = O.best(m, window, 1.0, combo)
         for t in range(0, n, 2048):
             d = ref.sdft(x[c, t:t + 2048])
             if X is None:
-                X = np.empty((CH, n, hi - lo), dtype=d.dtype)
+                X = np.empty((channels, n, hi - lo), dtype=d.dtype)
             X[c, t:t + 2048] = d[:, lo:hi]
     x.setflags(write=False)
     X.setflags(write=False)

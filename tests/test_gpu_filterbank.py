@@ -733,8 +733,100 @@ def test_filterbank_is_cut_again_when_the_tiles_change(combo, opts):
 
 
 # ---------------------------------------------------------------------------------------------
-# the five analysis entry points interleaved on one plan
+# the analysis entry points interleaved on one plan
 # ---------------------------------------------------------------------------------------------
+PAIR_LISTS = ([(3, 3)], [(2, 0), (1, 3)])                    # (what a batched run draws its pair list from, beside PAIRS)
+
+
+def run_interleaved(combo, opts, m, seed, channels=1):
+    """The body of test_analysis_entry_points_interleaved_on_one_plan; channels > 1 (tests/test_gpu_cross_sum_routes.py): a batched
+    plan, the samples signals(td, n, seed), cross_sum a sixth kind, every expectation per channel.  p and pool carry a pair list,
+    drawn again before some calls and installed in both (installing a list does not touch the state); the cross-spectrum call is
+    checked as the pooled power call is -- pool's own call with the same memory, bit for bit, the same time chunks -- and against
+    the twin's rows: at every == 1, first == 0 the bits of numpy's unfused expression, elsewhere check_pairs' bar for an exact
+    route.  The state compared after every call is that of all channels, the ones no pair names included."""
+    from sdft_amd.sdft import every_rows
+    from test_gpu_cross_sum import PAIRS, check_pairs, signals, terms
+    td, fd, _ = O.combo_types(combo)
+    batched = channels > 1
+    rng = np.random.default_rng(100 * m + seed)
+    n = 12000
+    special = [1, 2, 99, 100, 511, 512, 513, 2 * m - 1, 2 * m, 2 * m + 1]
+    calls = int(rng.integers(25, 41))
+    cuts = np.sort(rng.choice(np.arange(1, n - sum(special)), calls - len(special) - 1, replace=False))
+    drawn = np.diff(np.concatenate([[0], cuts, [n - sum(special)]]))
+    lengths = rng.permutation(np.concatenate([special, drawn]).astype(np.int64))
+    assert lengths.size == calls and lengths.sum() == n and (lengths >= 1).all()
+    x = signals(td, n, seed, channels) if batched else signal(n, td, 50 + seed)
+    bank = in_fd(random_bands(m), fd)
+    names = ("sdft", "every", "power", "power_sum", "filterbank") + (("cross_sum",) if batched else ())
+    lists = (PAIRS,) + PAIR_LISTS
+    seen, installed = set(), set()
+
+    def install(pairs, *plans):
+        for q in plans:
+            q.set_pairs([a for a, _ in pairs], [b for _, b in pairs])
+            assert q.pairs == len(pairs)
+        installed.add(tuple(pairs))
+        return pairs
+
+    with make(m, "hann", combo, channels, **opts) as p, make(m, "hann", combo, channels, **opts) as twin, \
+            make(m, "hann", combo, channels, **opts) as lone, make(m, "hann", combo, channels, **opts) as pool:
+        p.set_filterbank(*bank); lone.set_filterbank(*bank)
+        pairs = install(PAIRS, p, pool) if batched else None
+        t = 0
+        for i, k in enumerate(lengths.tolist()):
+            kind = names[int(rng.integers(0, len(names)))]
+            every = int(rng.choice([1, 2, 3, 7, 100, int(rng.integers(1, 600))]))
+            first = int(rng.integers(0, every + 2))
+            b0 = int(rng.integers(0, m))
+            band = (b0, int(rng.integers(1, m - b0 + 1)))
+            cols = slice(band[0], band[0] + band[1])
+            xs = np.ascontiguousarray(x[..., t:t + k])
+            xin = to_dev(xs) if i % 2 else xs
+            what = (combo, m, seed, i, kind, k, every, first, band)
+            before = twin.state()
+            rows = twin.sdft(xs)
+            if batched and int(rng.integers(0, 3)) == 0:     # a list installed mid-stream: the state stays
+                was = p.state()
+                pairs = install(lists[int(rng.integers(0, len(lists)))], p, pool)
+                now = p.state()
+                assert all(same_bits(u, v) for u, v in zip(was[:3], now[:3])) and was[3] == now[3], what
+            if kind == "sdft":
+                got, want = p.sdft(xin), rows
+            elif kind == "every":
+                got, want = p.sdft_every(xin, every, first), rows[..., first::every, :]
+            elif kind == "power":
+                got, want = p.power(xin, every, first, bins=band), power_of(rows)[..., first::every, cols]
+            elif kind == "power_sum":
+                got, want = p.power_sum(xin, every, first, bins=band), pool.power_sum(xin, every, first, bins=band)
+                assert (p.get_option("last_chunks"), p.get_option("last_chunk_len")) == (pool.get_option("last_chunks"), pool.get_option("last_chunk_len")), what
+                if every == 1 and first == 0:
+                    assert same_bits(got, np.ascontiguousarray(power_of(rows)[..., cols])), what
+            elif kind == "cross_sum":
+                got, want = p.cross_sum(xin, every, first, bins=band), pool.cross_sum(xin, every, first, bins=band)
+                assert p.get_option("last_kernel") == 8 and pool.get_option("last_kernel") == 8, what
+                assert (p.get_option("last_chunks"), p.get_option("last_chunk_len")) == (pool.get_option("last_chunks"), pool.get_option("last_chunk_len")), what
+                host = got.cpu().numpy() if hasattr(got, "cpu") else got
+                if every == 1 and first == 0:
+                    for j, (a, b) in enumerate(pairs):
+                        re, im = terms(rows[a][:, cols], rows[b][:, cols])
+                        assert same_bits(host[j].real, re) and same_bits(host[j].imag, im), (what, (a, b))
+                check_pairs(host, rows, pairs, k, every, first, band, True, what)
+            else:
+                lone.set_state(*before)
+                got, want = p.filterbank(xin, every, first), lone.filterbank(xs, every, first)
+                assert got.shape == ((channels,) if batched else ()) + (every_rows(k, every, first), bank[0].size), what
+            if kind not in ("power_sum", "cross_sum"):
+                pool.sdft(xs)
+            assert same_bits(got, want if hasattr(want, "cpu") else np.ascontiguousarray(want)), what
+            assert same_state(p, twin) and same_state(pool, twin), what
+            seen.add(kind)
+            t += k
+    assert len(seen) == len(names), seen
+    assert not batched or len(installed) == len(lists), installed
+
+
 @pytest.mark.parametrize("seed", [0, 1, 2])
 @pytest.mark.parametrize("m", [125, 1000])
 @pytest.mark.parametrize("combo,opts", BOUNDED)
@@ -748,57 +840,7 @@ def test_analysis_entry_points_interleaved_on_one_plan(combo, opts, m, seed):
     installed state moves the chunks (its fid does not count as canonical, so the relay form, whose chunks begin on its block
     boundaries, is not taken): there the other plan follows the stream through sdft and makes only the pooled calls itself, with
     the same kind of memory; every == 1, first == 0 is numpy's powers as well.  After every call the plan's state is the twin's."""
-    from sdft_amd.sdft import every_rows
-    td, fd, _ = O.combo_types(combo)
-    rng = np.random.default_rng(100 * m + seed)
-    n = 12000
-    special = [1, 2, 99, 100, 511, 512, 513, 2 * m - 1, 2 * m, 2 * m + 1]
-    calls = int(rng.integers(25, 41))
-    cuts = np.sort(rng.choice(np.arange(1, n - sum(special)), calls - len(special) - 1, replace=False))
-    drawn = np.diff(np.concatenate([[0], cuts, [n - sum(special)]]))
-    lengths = rng.permutation(np.concatenate([special, drawn]).astype(np.int64))
-    assert lengths.size == calls and lengths.sum() == n and (lengths >= 1).all()
-    x = signal(n, td, 50 + seed)
-    bank = in_fd(random_bands(m), fd)
-    names = ("sdft", "every", "power", "power_sum", "filterbank")
-    seen = set()
-    with make(m, "hann", combo, **opts) as p, make(m, "hann", combo, **opts) as twin, make(m, "hann", combo, **opts) as lone, \
-            make(m, "hann", combo, **opts) as pool:
-        p.set_filterbank(*bank); lone.set_filterbank(*bank)
-        t = 0
-        for i, k in enumerate(lengths.tolist()):
-            kind = names[int(rng.integers(0, len(names)))]
-            every = int(rng.choice([1, 2, 3, 7, 100, int(rng.integers(1, 600))]))
-            first = int(rng.integers(0, every + 2))
-            b0 = int(rng.integers(0, m))
-            band = (b0, int(rng.integers(1, m - b0 + 1)))
-            xs = x[t:t + k]
-            xin = to_dev(xs) if i % 2 else xs
-            what = (combo, m, seed, i, kind, k, every, first, band)
-            before = twin.state()
-            rows = twin.sdft(xs)
-            if kind == "sdft":
-                got, want = p.sdft(xin), rows
-            elif kind == "every":
-                got, want = p.sdft_every(xin, every, first), rows[first::every]
-            elif kind == "power":
-                got, want = p.power(xin, every, first, bins=band), power_of(rows)[first::every, band[0]:band[0] + band[1]]
-            elif kind == "power_sum":
-                got, want = p.power_sum(xin, every, first, bins=band), pool.power_sum(xin, every, first, bins=band)
-                assert (p.get_option("last_chunks"), p.get_option("last_chunk_len")) == (pool.get_option("last_chunks"), pool.get_option("last_chunk_len")), what
-                if every == 1 and first == 0:
-                    assert same_bits(got, np.ascontiguousarray(power_of(rows)[:, band[0]:band[0] + band[1]])), what
-            else:
-                lone.set_state(*before)
-                got, want = p.filterbank(xin, every, first), lone.filterbank(xs, every, first)
-                assert got.shape == (every_rows(k, every, first), bank[0].size), what
-            if kind != "power_sum":
-                pool.sdft(xs)
-            assert same_bits(got, want if hasattr(want, "cpu") else np.ascontiguousarray(want)), what
-            assert same_state(p, twin) and same_state(pool, twin), what
-            seen.add(kind)
-            t += k
-    assert len(seen) == len(names), seen
+    run_interleaved(combo, opts, m, seed)
 
 
 # ---------------------------------------------------------------------------------------------
