@@ -44,7 +44,11 @@ const char* sdft_hip_last_error(void);
   int sdft_hip_set_pairs_##SUF(void* plan, std::size_t npairs, const std::size_t* pair_a, const std::size_t* pair_b);    \
   std::size_t sdft_hip_pairs_##SUF(const void* plan);                                                                  \
   long sdft_hip_sdft_cross_sum_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, \
-                                       std::size_t bin0, std::size_t nbins, void* sums);
+                                       std::size_t bin0, std::size_t nbins, void* sums);                               \
+  int sdft_hip_set_array_##SUF(void* plan, std::size_t nch, const std::size_t* chan);                                  \
+  std::size_t sdft_hip_array_channels_##SUF(const void* plan);                                                         \
+  long sdft_hip_sdft_covariance_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, \
+                                        std::size_t bin0, std::size_t nbins, void* cov);
 SDFT_HPP_DECLARE(f32f64, float)
 SDFT_HPP_DECLARE(f32f32, float)
 SDFT_HPP_DECLARE(f64f64, double)
@@ -87,6 +91,9 @@ namespace sdft
       static int set_pairs(void* p, std::size_t np, const std::size_t* a, const std::size_t* b) { return sdft_hip_set_pairs_##SUF(p, np, a, b); } \
       static std::size_t pairs(const void* p) { return sdft_hip_pairs_##SUF(p); } \
       static long sdft_cross_sum_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_cross_sum_n_##SUF(p, n, x, e, f, b, k, d); } \
+      static int set_array(void* p, std::size_t nc, const std::size_t* c) { return sdft_hip_set_array_##SUF(p, nc, c); } \
+      static std::size_t array_channels(const void* p) { return sdft_hip_array_channels_##SUF(p); } \
+      static long sdft_covariance_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_covariance_n_##SUF(p, n, x, e, f, b, k, d); } \
     };
     SDFT_HPP_ABI(f32f64, float, double)
     SDFT_HPP_ABI(f32f32, float, float)
@@ -271,6 +278,38 @@ namespace sdft
       {
         const char* e = sdft_hip_last_error();
         throw std::runtime_error(std::string("sdft_hip_sdft_cross_sum_n: ") + (e ? e : "failed"));
+      }
+      return static_cast<std::size_t>(rows);
+    }
+
+    /**
+     * Installs (copies) an array in the plan (sdft_hip_set_array; a host list): an ordered list of nch distinct channels,
+     * chan == nullptr for the channels 0 ... nch - 1.  nch == 0 removes the list.  Independent of set_pairs().
+     **/
+    void set_array(const std::size_t nch, const std::size_t* chan = nullptr)
+    {
+      if (api::set_array(plan_, nch, chan) != 0)
+      {
+        const char* e = sdft_hip_last_error();
+        throw std::runtime_error(std::string("sdft_hip_set_array: ") + (e ? e : "failed"));
+      }
+    }
+    /** Channels of the installed array, 0 for none. */
+    std::size_t array_channels() const { return api::array_channels(plan_); }
+
+    /**
+     * Array covariance analysis (sdft_hip_sdft_covariance_n): cross_sum() for all pairs (i <= j) of the installed array; out is
+     * dense (nch (nch + 1) / 2, rows, nbins), the upper triangle in row-major order, element i nch - i (i - 1) / 2 + (j - i)
+     * the sums of X_chan[i] conj(X_chan[j]).  Every element has cross_sum()'s bits.  Returns the number of rows written.
+     **/
+    std::size_t covariance(const std::size_t nsamples, const T* samples, const std::size_t every, const std::size_t first,
+                           const std::size_t bin0, const std::size_t nbins, std::complex<F>* const out)
+    {
+      const long rows = api::sdft_covariance_n(plan_, nsamples, samples, every, first, bin0, nbins, out);
+      if (rows < 0)
+      {
+        const char* e = sdft_hip_last_error();
+        throw std::runtime_error(std::string("sdft_hip_sdft_covariance_n: ") + (e ? e : "failed"));
       }
       return static_cast<std::size_t>(rows);
     }

@@ -275,7 +275,7 @@ long sdft_hip_sdft_filterbank_n(sdft_t* sdft, const sdft_size_t nsamples, const 
    sdft_hip_pairs: the installed list's length, 0 for none or a NULL plan.
    Cost: every pair steps the recurrences of its two channels (one for a == b), so P pairs cost up to 2 P channels of
    sdft_hip_sdft_power_sum_n; a channel in no pair is stepped once more to keep its state.  The call is built for a few pairs per
-   channel, not for an all-pairs covariance of many channels. */
+   channel, not for an all-pairs covariance of many channels: that is sdft_hip_sdft_covariance_n below. */
 int         sdft_hip_set_pairs(sdft_t* sdft, const sdft_size_t npairs,
                                const sdft_size_t* pair_a, const sdft_size_t* pair_b) SDFT_HIP_SYMBOL(set_pairs);
 sdft_size_t sdft_hip_pairs(const sdft_t* sdft) SDFT_HIP_SYMBOL(pairs);
@@ -312,6 +312,44 @@ long sdft_hip_sdft_cross_sum_n(sdft_t* sdft, const sdft_size_t nsamples, const s
                                const sdft_size_t every, const sdft_size_t first,
                                const sdft_size_t bin0, const sdft_size_t nbins,
                                sdft_fdx_t* sums) SDFT_HIP_SYMBOL(sdft_cross_sum_n);
+
+/* ---- array covariance analysis -----------------------------------------------------------------------
+   The spatial covariance matrix per bin of an ARRAY of channels -- what MVDR / GEV beamformers, MUSIC and multichannel Wiener
+   filters start from: the pooled cross-spectrum of ALL pairs of the array's channels.  As a pair list that costs two recurrences
+   per pair; this call steps groups of channels instead (a wave takes a block of two groups, windows each channel once and forms
+   every term between them in registers), so the recurrences grow with the number of blocks, not of pairs.
+   An array belongs to the plan: an ordered list of nch DISTINCT channels of a batched plan, its elements.  sdft_hip_set_array
+   installs (copies) one; chan is HOST memory, chan == NULL with nch > 0 means the channels 0 ... nch - 1, nch == 0 removes the
+   list.  Returns 0, or -1 with sdft_hip_last_error() set and the previous list untouched: a NULL plan, an index >= channels, a
+   repeated index, nch > channels.  The array is independent of the pair list of sdft_hip_set_pairs: both may be installed.
+   sdft_hip_array_channels: the installed array's length, 0 for none or a NULL plan. */
+int         sdft_hip_set_array(sdft_t* sdft, const sdft_size_t nch, const sdft_size_t* chan) SDFT_HIP_SYMBOL(set_array);
+sdft_size_t sdft_hip_array_channels(const sdft_t* sdft) SDFT_HIP_SYMBOL(array_channels);
+/* sdft_hip_sdft_covariance_n takes its grid, windows, head row, row count, streaming rule, the next call's first, the band
+   arguments and the host / device pointer rules from sdft_hip_sdft_cross_sum_n, unchanged.
+   cov is [T][rows][nbins] complex numbers (re, im), T = nch (nch + 1) / 2, dense, aligned to sizeof(sdft_fd_t) only: the upper
+   triangle of the matrix in row-major order.  Element p(i, j) = i nch - i (i - 1) / 2 + (j - i), 0 <= i <= j < nch, holds the sum
+   over each window of X_chan[i] * conj(X_chan[j]); the lower triangle is its conjugate, which the host mirrors.
+   Three things are promised.
+   (1) The same plan, options and input give the same bits on every run.
+   (2) Element p(i, j) is, bit for bit, what sdft_hip_sdft_cross_sum_n returns for the pair (chan[i], chan[j]) from the same
+       samples, wherever the two calls start from the same carries: on the bit-identical routes (FD float, FD double with option
+       "carry" = 1, calls shorter than 512 samples) always, elsewhere when both cut time into chunks of the same length
+       ("last_chunk_len"; option "chunk" sets it).  The call uses that call's term expression with the lower array index on
+       side A (four rounded products, no fused multiply-add, -0 start), its additions in ascending time order, its workspace of
+       cut windows and its ordered adder.  Hence p(i, i) has im == +0 and is the pooled power call's value, and promise (5) of
+       sdft_hip_sdft_cross_sum_n (accuracy) holds for every element verbatim.
+   (3) The stream state of every channel of the plan, in the array or not, is afterwards what sdft_sdft_n of the same samples
+       leaves: every channel has exactly one writer.  Any other entry point may follow.
+   Workspace (kept by the plan, grown on demand): where a call is cut into C > 1 time chunks, T * C * 2 * nbins complex numbers
+   -- sdft_hip_sdft_cross_sum_n's, with T pairs.
+   The call is never resident, pipelined or fused and always runs its own kernel ("last_kernel" = 9).  Returns the number of rows
+   written (0 for nsamples == 0), or -1 with sdft_hip_last_error() set and the stream state untouched: a NULL plan, no array
+   installed, every == 0, nbins == 0, bin0 + nbins > dftsize, cov == NULL with rows > 0, or a workspace that cannot be reserved. */
+long sdft_hip_sdft_covariance_n(sdft_t* sdft, const sdft_size_t nsamples, const sdft_td_t* samples,
+                                const sdft_size_t every, const sdft_size_t first,
+                                const sdft_size_t bin0, const sdft_size_t nbins,
+                                sdft_fdx_t* cov) SDFT_HIP_SYMBOL(sdft_covariance_n);
 
 /* ---- streams ---------------------------------------------------------------------------------
    Every plan owns a HIP stream.  Calls with host pointers always return with the output
@@ -424,13 +462,14 @@ double sdft_hip_time_hops(sdft_t* sdft, size_t hops, size_t hop, const sdft_td_t
    -DSDFT_HIP_TEST_HOOKS (libsdft_hip_hooks.so, built beside the product by `python -m sdft_amd.build`; no host links it) accept the keys that force
    those forks, so that the tests can run every route against the reference and the probes under scripts/ can measure them:
    "rows_kernel", "row_slots_max", "interior", "fused", "fft_carry", "fold", "rows_f32", "hop_parts", "xcd_map", "chain_block", "relay_waves", "inverse_verify",
-   "relay_flow", "relay_groups", "chain_debug", "inverse_nt", "inverse_nt_skip_mb", "inverse_step", "inverse_ordered", "host_direct", "copy_streams", "prefix_cells" (sdft_capi.inc names what each selects);
+   "relay_flow", "relay_groups", "chain_debug", "inverse_nt", "inverse_nt_skip_mb", "inverse_step", "inverse_ordered", "host_direct", "copy_streams", "prefix_cells", "array_group" (sdft_capi.inc names what each selects);
    get_option "test_hooks" = 1 in that build.
    get_option additionally answers "tiles", "bins_per_lane", "row_slots", "last_chunks",
-   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis, 6 pooled power analysis, 7 filterbank analysis, 8 pooled cross-spectrum analysis), "last_segments", "last_fused",
+   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis, 6 pooled power analysis, 7 filterbank analysis, 8 pooled cross-spectrum analysis, 9 array covariance analysis), "last_segments", "last_fused",
    "last_filterbank_launches" (forward_filterbank_kernel launches of the last filterbank call, over all of its host segments: more than its carry segments once its pieces exceed the workspace bound),
    "last_chain", "last_fused_exact", "last_fused_fold", "last_process_path" (1 fused kernel, 2 hop pair, 3 two-pass),
    "last_self" (no pre-pass launch), "last_prefix" (long calls: one pre-pass launch, prefix_cells_kernel), "last_inverse_nt" / "last_inverse_skip" (what the last synthesis launch used: non-temporal loads, rows read with ordinary loads),
+   "array_group" (channels per group of a register block of sdft_hip_sdft_covariance_n),
    "cursor", "device", "ring_recoveries" (calls re-run with the serial carry pass after a poll loop of
    the exact-carry kernels timed out: results stay valid, sdft_hip_last_warning() reports it), "flag_fallbacks". */
 int  sdft_hip_set_option(sdft_t* sdft, const char* key, long value) SDFT_HIP_SYMBOL(set_option);

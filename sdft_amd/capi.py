@@ -62,6 +62,9 @@ def typed_signatures(combo: str):
         "set_pairs": (C.c_int, [vp, sz, vp, vp]),
         "pairs": (sz, [vp]),
         "sdft_cross_sum_n": (C.c_long, [vp, sz, vp, sz, sz, sz, sz, vp]),
+        "set_array": (C.c_int, [vp, sz, vp]),
+        "array_channels": (sz, [vp]),
+        "sdft_covariance_n": (C.c_long, [vp, sz, vp, sz, sz, sz, sz, vp]),
     }
 
 

@@ -488,6 +488,127 @@
     });
   }
 
+  // ---- array covariance analysis ------------------------------------------------------------------------------------------------
+  // sdft_hip_set_array: the list is host memory and is copied (nullptr: the channels 0 ... nch - 1); a refused list leaves the
+  // installed one as it is.  The work items (logic::covariance_items) and the list go to the device here, and again when a test
+  // hook changes the group size (upload_array).
+  bool upload_array(Array& f)
+  {
+    f.group = array_group();
+    f.items = logic::covariance_items(channels, f.chan.size(), f.chan.data(), f.group);
+    std::vector<unsigned> chan32(f.chan.begin(), f.chan.end());
+    // (fresh tables: whatever still reads the installed ones has drained before they are replaced, and a failure leaves them alone)
+    DevBuf<CovItem> table;
+    DevBuf<unsigned> list;
+    SDFT_TRY(hipStreamSynchronize(stream));
+    if (!table.reserve(f.items.size()) || !list.reserve(chan32.size())) { table.release(); list.release(); return false; }
+    if (!to_device(table.p, f.items.data(), f.items.size() * sizeof(CovItem)) || !to_device(list.p, chan32.data(), chan32.size() * sizeof(unsigned)) ||
+        hipStreamSynchronize(stream) != hipSuccess) { table.release(); list.release(); return false; }
+    d_cov_items.release(); d_cov_chan.release();
+    d_cov_items = table; d_cov_chan = list;
+    return true;
+  }
+  bool set_array(size_t nch, const size_t* chan)
+  {
+    static const char* fn = "sdft_hip_set_array";
+    switch (logic::array_check(channels, nch, chan))
+    {
+      case logic::AR_OK: break;
+      case logic::AR_CHANNEL: set_error(fn, "the list names a channel the plan does not have (index >= channels)"); return false;
+      case logic::AR_REPEAT: set_error(fn, "the list names a channel twice"); return false;
+      default: set_error(fn, "the list is too long: more channels than the plan has (or than 65535)"); return false;
+    }
+    if (!bind()) return false;
+    if (!pipe_join()) return false;
+    Array f;
+    if (nch)
+    {
+      f.chan.resize(nch);
+      for (size_t i = 0; i < nch; ++i) f.chan[i] = chan ? chan[i] : i;
+      if (!upload_array(f)) return false;
+    }
+    else SDFT_TRY(hipStreamSynchronize(stream));
+    array = std::move(f);
+    return true;
+  }
+  size_t array_channels() const { return array.chan.size(); }
+
+  // array covariance analysis (sdft_hip_sdft_covariance_n): sdft_cross_sum_n for all pairs (i <= j) of the installed array, dense
+  // [nch (nch + 1) / 2][rows][nbins_out] complex numbers in the order of logic::covariance_pair_index.  Grid, state, pointers,
+  // segments of host memory, head rows and launches are sdft_cross_sum_n's with the output indices for pairs (d_cov_head,
+  // d_cov_stage); forward_covariance_kernel forms the sums by blocks of groups of channels.
+  bool sdft_covariance_n(size_t n, const TD* x, size_t every, size_t first, size_t bin0, size_t nbins_out, FD* sums, size_t& rows)
+  {
+    static const char* fn = "sdft_hip_sdft_covariance_n";
+    rows = 0;
+    const size_t nch = array_channels(), npairs = logic::covariance_pairs(nch);
+    if (nch == 0) { set_error(fn, "no array is installed (sdft_hip_set_array)"); return false; }
+    if (every == 0) { set_error(fn, "every must be at least 1"); return false; }
+    if (nbins_out == 0) { set_error(fn, "nbins must be at least 1"); return false; }
+    if (!logic::power_band_ok(nbins, bin0, nbins_out)) { set_error(fn, "the band bin0 ... bin0 + nbins - 1 does not lie within the plan's bins"); return false; }
+    rows = logic::power_sum_rows(n, every, first);
+    if (rows > 0 && !sums) { set_error(fn, "cov is NULL but the call writes rows"); return false; }
+    if (n == 0) return true;
+    if (!bind()) return false;
+    if (!pipe_join()) return false;
+    if (array.group != array_group() && !upload_array(array)) return false;       // (a test hook changed the group size)
+    if (every > n) every = n;                                // (the same windows; keeps first + k * every in range)
+    const bool xd = on_device(x);
+    const bool od = on_device(sums);
+    const size_t nb2 = 2 * nbins_out;                        // numbers of a row of one pair
+    const size_t row_bytes = npairs * nb2 * sizeof(FD);
+    auto band = [&](FD* row0, size_t row0_stride, FD* rest, size_t rest_stride, size_t f) {
+      return CovarianceArgs<FD>{row0, row0_stride, rest, rest_stride, nullptr, d_cov_items.p, d_cov_chan.p, (unsigned)array.items.size(), (unsigned)nch,
+                                (unsigned)npairs, (unsigned long long)every, (unsigned long long)f, (unsigned)bin0, (unsigned)nbins_out};
+    };
+    const size_t stride = logic::cross_pair_stride(rows, nbins_out);
+    if (xd && od)
+    {
+      const CovarianceArgs<FD> g = band(sums, stride, sums + nb2, stride, first);
+      return forward_device(n, x, n, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &g) && finish(rows * row_bytes);
+    }
+    // host memory: segments of at most seg samples (rows written and samples within stage_bytes); where the grid allows it, of
+    // whole windows, so that no row is made of two segments
+    size_t seg = n;
+    if (!od) seg = std::min(seg, logic::stage_rows(n, row_bytes, stage_bytes) * every);
+    if (!xd) seg = std::min(seg, std::max<size_t>((size_t)logic::kHopSamples, logic::stage_rows(n, channels * sizeof(TD), stage_bytes)));
+    if (seg < n && seg > every && first % every == 0) seg -= seg % every;
+    const size_t seg_rows_max = (seg + every - 1) / every + 1;
+    if (!od && !d_cov_stage.reserve(npairs * seg_rows_max * nb2)) return false;
+    std::vector<FD> head;                                    // host buffers: a segment's head rows on their way to the rows they complete
+    return staged_segments(n, seg, StagedCall{true, const_cast<TD*>(x), !xd, nullptr, false, rows, seg_rows_max, nb2 * sizeof(FD)}, [&](Segment& s) {
+      const size_t f = logic::every_first_from(s.t, every, first);
+      const logic::PowerSumWindow w0 = logic::power_sum_window(s.t, n, every, first);      // of the segment's row 0 in the call
+      const bool joins = w0.begin < s.t;                     // row 0 is a head: it completes row w0.row of the call
+      const size_t seg_rows = logic::power_sum_rows(s.m, every, f), kept = seg_rows - (joins ? 1 : 0);
+      if (joins && !d_cov_head.reserve(npairs * nb2)) return false;
+      const size_t r0 = w0.row + (joins ? 1 : 0);            // the segment's first row of its own
+      s.rows = 0;                                            // (nothing for staged_segments to copy)
+      FD* const at = od ? sums + r0 * nb2 : d_cov_stage.p;   // scratch: [npairs][kept][nbins_out] complex
+      const size_t at_stride = od ? stride : kept * nb2;
+      const CovarianceArgs<FD> g = joins ? band(d_cov_head.p, nb2, at, at_stride, f) : band(at, at_stride, at + nb2, at_stride, f);
+      if (!forward_device(s.m, s.td, s.td_stride, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &g)) return false;
+      if (od)
+      {
+        if (!joins) return true;
+        const unsigned long long threads = (unsigned long long)npairs * nb2;
+        hipLaunchKernelGGL((pooled_power_add_kernel<FD>), dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
+                           sums + w0.row * nb2, stride, d_cov_head.p, (unsigned)nb2, (unsigned)npairs);
+        SDFT_TRY(hipGetLastError());
+        return true;
+      }
+      for (size_t p = 0; p < npairs && kept; ++p)
+        if (!to_host(sums + p * stride + r0 * nb2, d_cov_stage.p + p * kept * nb2, kept * nb2 * sizeof(FD))) return false;
+      if (!joins) return true;
+      head.resize(npairs * nb2);
+      if (!to_host(head.data(), d_cov_head.p, head.size() * sizeof(FD))) return false;
+      SDFT_TRY(hipStreamSynchronize(stream));
+      for (size_t p = 0; p < npairs; ++p)
+        for (size_t k = 0; k < nb2; ++k) sums[p * stride + w0.row * nb2 + k] += head[p * nb2 + k];
+      return true;
+    });
+  }
+
   // a host table of device rows goes to the device; nullptr: failed
   fdx* const* device_table(fdx* const* dfts, size_t n, bool table_on_device)
   {

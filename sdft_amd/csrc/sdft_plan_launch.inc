@@ -366,8 +366,44 @@
       default:           hipLaunchKernelGGL((forward_cross_sum_kernel<FD, BPL, WIN_BOXCAR>), gr, b, 0, stream, fa, g); break;
     }
   }
+  // channels per group of a covariance call: the build's choice per FD type, or (test hook) a candidate of scripts/covariance_rates.py
+  int array_group() const
+  {
+#ifdef SDFT_HIP_TEST_HOOKS
+    if (opt_array_group == 1 || opt_array_group == 2 || opt_array_group == 4) return (int)opt_array_group;
+#endif
+    return cov_group<FD>::value;
+  }
+  template <int G> void launch_forward_covariance_g(const ForwardArgs<FD>& fa, const CovarianceArgs<FD>& g, unsigned blocks)
+  {
+    constexpr int BPL = sizeof(fdx) == 16 ? 1 : 2;
+    const dim3 gr(blocks), b(kBlock);
+    switch (window)
+    {
+      case WIN_HANN:     hipLaunchKernelGGL((forward_covariance_kernel<FD, BPL, WIN_HANN, G>), gr, b, 0, stream, fa, g); break;
+      case WIN_HAMMING:  hipLaunchKernelGGL((forward_covariance_kernel<FD, BPL, WIN_HAMMING, G>), gr, b, 0, stream, fa, g); break;
+      case WIN_BLACKMAN: hipLaunchKernelGGL((forward_covariance_kernel<FD, BPL, WIN_BLACKMAN, G>), gr, b, 0, stream, fa, g); break;
+      default:           hipLaunchKernelGGL((forward_covariance_kernel<FD, BPL, WIN_BOXCAR, G>), gr, b, 0, stream, fa, g); break;
+    }
+  }
+  // (the items of g were built for array.group channels per group: the kernel's G must be that)
+  bool launch_forward_covariance(const ForwardArgs<FD>& fa, const CovarianceArgs<FD>& g, unsigned blocks)
+  {
+    if (array.group == cov_group<FD>::value) { launch_forward_covariance_g<cov_group<FD>::value>(fa, g, blocks); return true; }
+#ifdef SDFT_HIP_TEST_HOOKS
+    switch (array.group)
+    {
+      case 1: launch_forward_covariance_g<1>(fa, g, blocks); return true;
+      case 2: launch_forward_covariance_g<2>(fa, g, blocks); return true;
+      case 4: launch_forward_covariance_g<4>(fa, g, blocks); return true;
+      default: break;
+    }
+#endif
+    set_error("sdft_hip_sdft_covariance_n", "no kernel for the array's group size");
+    return false;
+  }
   // the rows of the windows a chunk boundary cuts, from their pieces in the workspace (chunks > 1); nch: the plan's channels, or the
-  // pairs of a cross-spectrum call
+  // pairs of a cross-spectrum or covariance call
   bool launch_power_sum_rows(const PowerSumArgs<FD>& g, size_t n, long chunks, long len, long shift, size_t nch)
   {
     const unsigned long long threads = (unsigned long long)nch * (unsigned long long)(chunks - 1) * g.nbins_out;

@@ -348,6 +348,67 @@ inline size_t cross_sum_slot(size_t item, size_t chunks, size_t chunk, int slot,
 // numbers (not complex numbers) from one pair's first sum to the next pair's
 inline size_t cross_pair_stride(size_t rows, size_t nbins_out) { return power_channel_stride(rows, 2 * nbins_out); }
 
+// ---- array covariance analysis (sdft_hip_sdft_covariance_n) ------------------------------------------------------------------------
+// The array is an ordered list of nch distinct channels of the plan (sdft_hip_set_array); the call returns the cross-spectrum
+// call's sums for ALL pairs of its elements: the upper triangle in row-major order, element (i <= j) -- the pair of the channels
+// (chan[i], chan[j]) -- at the output index covariance_pair_index.  As a pair list that steps two recurrences per pair; here the
+// array is cut into groups of G consecutive elements (the last one may be shorter) and a wave of forward_covariance_kernel takes a
+// BLOCK: group u on side A and group v >= u on side B, 2 G recurrences for G x G pairs.  A diagonal block (u == v) steps its one
+// group once and forms the pairs (sa <= sb) of it; it is also the one item that writes the state of its channels back, so every
+// array channel has exactly one writer.  After the blocks comes one advance-only item per plan channel that is not in the array.
+enum ArrayCheck : int { AR_OK = 0, AR_CHANNEL = 1, AR_REPEAT = 2, AR_TOO_MANY = 3 };
+constexpr size_t kArrayMaxChannels = 65535;                   // the pairs are counted in 32 bits
+// a list sdft_hip_set_array may install (nch == 0 removes the list; chan == nullptr: the channels 0 ... nch - 1)
+inline int array_check(size_t channels, size_t nch, const size_t* chan)
+{
+  const size_t ch = std::max<size_t>(channels, 1);
+  if (nch > ch || nch > kArrayMaxChannels) return AR_TOO_MANY;
+  if (!chan) return AR_OK;
+  std::vector<char> seen(ch, 0);
+  for (size_t i = 0; i < nch; ++i)
+  {
+    if (chan[i] >= ch) return AR_CHANNEL;
+    if (seen[chan[i]]) return AR_REPEAT;
+    seen[chan[i]] = 1;
+  }
+  return AR_OK;
+}
+inline size_t covariance_pairs(size_t nch) { return nch * (nch + 1) / 2; }
+// i <= j < nch: i * nch - i (i - 1) / 2 + (j - i)
+inline size_t covariance_pair_index(size_t nch, size_t i, size_t j) { return (i * (2 * nch - i + 1)) / 2 + (j - i); }
+struct CovItem
+{
+  unsigned a0, b0;                        // a block: the first array element of side A and of side B (a0 <= b0; a0 == b0: diagonal);
+                                          // an advance-only item: the PLAN channel, twice
+  unsigned short na, nb;                  // elements on each side (1 ... G; advance-only: 1 and 0)
+  unsigned short block, writes;           // block: forms pairs; writes: stores the state of side A's channels on the last chunk
+};
+// (of a list array_check has passed)
+inline std::vector<CovItem> covariance_items(size_t channels, size_t nch, const size_t* chan, int G)
+{
+  const size_t ch = std::max<size_t>(channels, 1), g = (size_t)std::max(G, 1), groups = (nch + g - 1) / g;
+  std::vector<CovItem> items;
+  std::vector<char> in_array(ch, 0);
+  for (size_t i = 0; i < nch; ++i) in_array[chan ? chan[i] : i] = 1;
+  items.reserve(groups * (groups + 1) / 2 + ch);
+  for (size_t u = 0; u < groups; ++u)
+    for (size_t v = u; v < groups; ++v)
+      items.push_back(CovItem{(unsigned)(u * g), (unsigned)(v * g), (unsigned short)std::min(g, nch - u * g), (unsigned short)std::min(g, nch - v * g),
+                              1, (unsigned short)(u == v ? 1 : 0)});
+  for (size_t c = 0; c < ch; ++c)
+    if (!in_array[c]) items.push_back(CovItem{(unsigned)c, (unsigned)c, 1, 0, 0, 1});
+  return items;
+}
+// the output index of the slots (sa, sb) of an item, or -1: the slot pair forms nothing (the kernel makes the same test)
+inline long covariance_item_out(size_t nch, const CovItem& it, size_t sa, size_t sb)
+{
+  if (!it.block || sa >= it.na || sb >= it.nb || (it.a0 == it.b0 && sa > sb)) return -1;
+  return (long)covariance_pair_index(nch, it.a0 + sa, it.b0 + sb);
+}
+// The workspace of the windows a chunk boundary cuts is the cross-spectrum call's with the nch (nch + 1) / 2 output indices for
+// pairs: [pairs][chunks][2][nbins_out] complex, slot cross_sum_slot(p, ...)
+inline size_t covariance_workspace(size_t nch, size_t chunks, size_t nbins_out) { return cross_sum_workspace(covariance_pairs(nch), chunks, nbins_out); }
+
 // ---- filterbank analysis (sdft_hip_sdft_filterbank_n) --------------------------------------------------------------------------
 // Band b of a filterbank covers the bins [band_bin0[b], band_bin0[b] + band_nbins[b]) with one weight per bin; row r of the output
 // holds, per band, the sum of fl(weight * power) over the band's bins, the powers those sdft_hip_sdft_power_n stores for the row.
@@ -818,6 +879,7 @@ struct ForwardQuery
   bool filterbank = false;                // filterbank analysis (forward_filterbank_kernel) on the grid of power_every
   bool cross_sum = false;                 // pooled cross-spectrum analysis (forward_cross_sum_kernel) of ...
   size_t cross_items = 0;                 // ... this many work items (logic::cross_items), which take the channels' place in the launch
+  bool covariance = false;                // array covariance analysis (forward_covariance_kernel): cross_items counts its block items (logic::covariance_items)
   bool row_pointers = false;              // rows go to a table of row pointers
   uintptr_t out = 0; size_t out_stride = 0;
   bool analysis_batch = false;            // CallPattern: analyses come call after call
@@ -828,7 +890,7 @@ struct ForwardQuery
        chain_L = 0, relay_flow = 1, segments = 0, xcd_map = 1, rows_f32 = 1, pipeline = 1;
   long prefix_cells = 1;                  // test hook: 0 = never the prefix-cell route, 1 = calls beyond kSelfMax, 2 = whatever the length
 };
-enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6, FK_FILTERBANK = 7, FK_CROSS_SUM = 8 };     // = get_option "last_kernel"
+enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6, FK_FILTERBANK = 7, FK_CROSS_SUM = 8, FK_COVARIANCE = 9 };     // = get_option "last_kernel"
 // carries: the single chunk's are the stream state (delta_kernel copies it); pre-pass partial sums + scan (carries from the
 // closed-form table); the serial exact pass (carry_exact_kernel); the relay form of the exact pass (carry_relay_kernel)
 enum CarryForm : int { CARRY_STATE = 0, CARRY_SUMS = 1, CARRY_SERIAL = 2, CARRY_RELAY = 3 };
@@ -876,10 +938,10 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   ForwardRoute r;
   const size_t nb = q.nbins, span = 2 * nb, n = q.n, ch = std::max<size_t>(q.channels, 1);
   const bool pow2 = (span & (span - 1)) == 0;
-  // the decimated, the power-spectrogram, the pooled power, the filterbank and the cross-spectrum analysis have the tile form only
-  const bool grid = q.every || q.power || q.power_sum || q.filterbank || q.cross_sum;
-  // (channel, chunk) groups of a tile launch per chunk: the cross-spectrum call's are its work items
-  const size_t lanes = q.cross_sum ? std::max<size_t>(q.cross_items, 1) : ch;
+  // the decimated, the power-spectrogram, the pooled power, the filterbank, the cross-spectrum and the covariance analysis have the tile form only
+  const bool grid = q.every || q.power || q.power_sum || q.filterbank || q.cross_sum || q.covariance;
+  // (channel, chunk) groups of a tile launch per chunk: the cross-spectrum and the covariance call's are their work items
+  const size_t lanes = (q.cross_sum || q.covariance) ? std::max<size_t>(q.cross_items, 1) : ch;
   const bool rows = !grid && rows_kernel_ok(nb, q.fdx_bytes, q.row_pointers, q.rows_kernel != 0, q.row_slots_max);
   const bool folded = q.fuse && !q.reference_order && !q.fuse_store && q.fold && q.coeff_ready;
   // pipelined calls (forward_self): decided first because they take the self-carried form at any length and cut time differently
@@ -905,12 +967,12 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   {
     EveryQuery e;
     e.n = n; e.channels = lanes; e.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); e.exact = q.exact; e.forced_chunk = q.chunk; e.compute_units = q.compute_units;
-    c = (q.power_sum || q.cross_sum) ? choose_power_sum_chunks(e) : (q.power || q.filterbank) ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
+    c = (q.power_sum || q.cross_sum || q.covariance) ? choose_power_sum_chunks(e) : (q.power || q.filterbank) ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
   }
   else c = choose_chunks(chunk_query(q, rows, r.pipelined));
   r.chunks = c.chunks; r.len = c.len;
   r.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); r.interior = interior_lanes(q.window, q.fdx_bytes, q.interior);
-  r.kernel = q.cross_sum ? FK_CROSS_SUM : q.filterbank ? FK_FILTERBANK : q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
+  r.kernel = q.covariance ? FK_COVARIANCE : q.cross_sum ? FK_CROSS_SUM : q.filterbank ? FK_FILTERBANK : q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
   if (r.chunks == 1 && q.hop_kernel && nb >= 2 && !q.fuse && !grid) { r.kernel = FK_HOP; return r; }
 
   // self-carried chunks: every workgroup derives its carry-in from the raw samples (fold + one FFT in LDS) and forms

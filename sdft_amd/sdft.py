@@ -46,6 +46,7 @@ class SDFT:
         self._options = []                                   # (key, value) set so far, and the caller's stream: replayed when the plan moves
         self._stream = None
         self._pairs = None                                   # the pair list of set_pairs, likewise
+        self._array = None                                   # the array of set_array, likewise
         self.combo = combo
         self.td = _NP_REAL[combo[:3]]
         self.fd = _NP_REAL[combo[3:]]
@@ -118,6 +119,8 @@ class SDFT:
                     self.set_stream(self._stream)
                 if self._pairs is not None:                      # (the installed pair list moves with the plan)
                     self.set_pairs(*self._pairs)
+                if self._array is not None:                      # (and the installed array)
+                    self.set_array(self._array)
                 self._options.append((key, int(value)))
                 return
             if q:
@@ -420,6 +423,72 @@ class SDFT:
         assert got == rows, (got, rows)
         return out
 
+    def set_array(self, chan):
+        """Installs an array in the plan (``sdft_hip_set_array``; the list is copied): an ordered list of distinct channels, the
+        elements of the array whose covariance :meth:`covariance` forms.  An int n means the channels ``0 ... n - 1``; an empty list
+        (or 0) removes the array.  Independent of :meth:`set_pairs`: both may be installed."""
+        self.api.clear()
+        try:
+            ch = np.arange(int(chan), dtype=np.uint64) if np.isscalar(chan) else np.ascontiguousarray(chan, dtype=np.uint64).ravel()
+        except OverflowError as e:
+            raise ValueError(f"channel indices must not be negative: {e}") from None
+        rc = self.api.set_array(self._p, ch.size, C.c_void_p(ch.ctypes.data if ch.size else None))
+        if rc != 0:
+            self.api.check()
+            raise SdftHipError("sdft_hip_set_array failed")
+        self.api.check()
+        self._array = ch if ch.size else None
+
+    @property
+    def array_channels(self) -> int:
+        """Channels of the installed array (``sdft_hip_array_channels``), 0 for none."""
+        return int(self.api.array_channels(self._p))
+
+    def covariance(self, x, every: int = 1, first: int = 0, bins=None, out=None):
+        """Array covariance analysis (``sdft_hip_sdft_covariance_n``): :meth:`cross_sum` for ALL pairs ``(i <= j)`` of the installed
+        array (:meth:`set_array`), formed by register blocks of groups of channels -> complex array of shape (T, rows, nbins),
+        ``T = nch (nch + 1) / 2``: the upper triangle in row-major order, the order of :func:`covariance_pairs`; element
+        ``i * nch - i * (i - 1) / 2 + (j - i)`` holds the sums of ``X_chan[i] * conj(X_chan[j])`` and has :meth:`cross_sum`'s bits.
+        Arguments, grid, head row, streaming and state as with :meth:`cross_sum`; :func:`covariance_matrix` expands the result to
+        Hermitian matrices on the host."""
+        self.api.clear()
+        every, first = int(every), int(first)
+        bin0, nb = (0, self.dftsize) if bins is None else (int(bins[0]), int(bins[1]))
+        if every < 1 or first < 0:
+            raise ValueError(f"every must be >= 1 and first >= 0, got every={every}, first={first}")
+        if bin0 < 0 or nb < 1 or bin0 + nb > self.dftsize:
+            raise ValueError(f"bins = (bin0, nbins) must select at least one of the {self.dftsize} bins, got {(bin0, nb)}")
+        nch = self.array_channels
+        if nch == 0:
+            raise ValueError("no array is installed: call set_array first")
+        npairs = nch * (nch + 1) // 2
+        cdtype = np.dtype(np.complex64 if np.dtype(self.fd) == np.float32 else np.complex128)
+        if _is_tensor(x):
+            torch = _torch()
+            n = self._shape_x(x.shape)
+            self._check_tensor(x, "samples", self.td)
+            rows = power_sum_rows(n, every, first)
+            shape = (npairs, rows, nb)
+            if out is None:
+                out = torch.empty(shape, dtype=getattr(torch, cdtype.name), device=x.device)
+            self._check_tensor(out, "out", cdtype, shape)
+            got = self.api.sdft_covariance_n(self._p, n, C.c_void_p(x.data_ptr()), every, first, bin0, nb, C.c_void_p(out.data_ptr() if rows else None))
+        else:
+            x = np.ascontiguousarray(x, dtype=self.td)
+            n = self._shape_x(x.shape)
+            rows = power_sum_rows(n, every, first)
+            shape = (npairs, rows, nb)
+            if out is None:
+                out = np.empty(shape, dtype=cdtype)
+            assert out.flags.c_contiguous and out.shape == shape and out.dtype == cdtype
+            got = self.api.sdft_covariance_n(self._p, n, C.c_void_p(x.ctypes.data), every, first, bin0, nb, C.c_void_p(out.ctypes.data if rows else None))
+        if got < 0:
+            self.api.check()
+            raise SdftHipError("sdft_hip_sdft_covariance_n failed")
+        self.api.check()
+        assert got == rows, (got, rows)
+        return out
+
     def power_sum(self, x, every: int = 1, first: int = 0, bins=None, out=None):
         """Pooled power analysis (``sdft_hip_sdft_power_sum_n``): the grid points ``first``, ``first + every``, ... cut the n samples
         into windows, and row r is the sum of :meth:`power`'s ``every = 1`` values over the r-th window, for the bins
@@ -579,6 +648,32 @@ def power_sum_rows(n: int, every: int, first: int) -> int:
     """Rows a pooled power analysis call of n samples writes (sdft_hip_sdft_power_sum_n): the head window, if any, and one row per
     grid point."""
     return (1 if first > 0 and n > 0 else 0) + every_rows(n, every, first)
+
+
+def covariance_pairs(nch: int):
+    """The upper triangle of an array of ``nch`` elements as a pair list ``(a, b)`` of array INDICES in the order of
+    :meth:`SDFT.covariance`'s output: ``(0, 0), (0, 1), ... (0, nch - 1), (1, 1), ...``.  With the array's channel list ``chan``,
+    ``set_pairs(chan[a], chan[b])`` makes :meth:`SDFT.cross_sum` return the same elements."""
+    nch = int(nch)
+    a = np.array([i for i in range(nch) for _ in range(i, nch)], dtype=np.uint64)
+    b = np.array([j for i in range(nch) for j in range(i, nch)], dtype=np.uint64)
+    return a, b
+
+
+def covariance_matrix(cov, nch: int):
+    """Expands :meth:`SDFT.covariance`'s (T, rows, nbins) upper triangle to Hermitian matrices of shape (rows, nbins, nch, nch) on the
+    host (numpy; a device tensor is copied): ``[r, k, i, j]`` is the sum of ``X_chan[i] * conj(X_chan[j])``, the lower triangle the
+    conjugate of the upper.  Plumbing only."""
+    nch = int(nch)
+    c = cov.detach().cpu().numpy() if _is_tensor(cov) else np.asarray(cov)
+    if c.ndim != 3 or c.shape[0] != nch * (nch + 1) // 2:
+        raise ValueError(f"cov must be (nch (nch + 1) / 2, rows, nbins) for nch = {nch}, got {c.shape}")
+    a, b = covariance_pairs(nch)
+    a, b = a.astype(np.intp), b.astype(np.intp)
+    m = np.empty(c.shape[1:] + (nch, nch), dtype=c.dtype)
+    m[:, :, b, a] = np.conj(np.moveaxis(c, 0, -1))
+    m[:, :, a, b] = np.moveaxis(c, 0, -1)                        # (the diagonal last: as returned, im == +0)
+    return m
 
 
 def every_next_first(n: int, every: int, first: int) -> int:
