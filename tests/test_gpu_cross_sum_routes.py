@@ -41,11 +41,11 @@ def numpy_of(a):
     return a.cpu().numpy() if hasattr(a, "cpu") else a
 
 
-def assert_route(p, opts, exact, m, what):
-    """the route a long call took: forward_cross_sum_kernel on several chunks, never the flow form; the forced chunk and segment
-    count; the relay form (last_chain == 3) wherever the carries are exact, the form is not turned off and a block exists, else the
-    serial pass or the partial sums (0)"""
-    assert p.get_option("last_kernel") == 8 and p.get_option("last_chunks") > 1 and p.get_option("last_flow") == 0, what
+def assert_route(p, opts, exact, m, what, kernel=8):
+    """the route a long call took: forward_cross_sum_kernel (kernel = 9: forward_covariance_kernel) on several chunks, never the
+    flow form; the forced chunk and segment count; the relay form (last_chain == 3) wherever the carries are exact, the form is not
+    turned off and a block exists, else the serial pass or the partial sums (0)"""
+    assert p.get_option("last_kernel") == kernel and p.get_option("last_chunks") > 1 and p.get_option("last_flow") == 0, what
     if "chunk" in opts:
         assert p.get_option("last_chunk_len") == opts["chunk"], what
     if "segments" in opts:
@@ -286,13 +286,13 @@ def raw_cross_sum(p, x, n, every, first, band, sums):
     assert p.get_option("last_kernel") == 8
 
 
-def sentinel_sums(fd, rows, nb, device):
+def sentinel_sums(fd, rows, nb, device, npairs=len(PAIRS)):
     """sums no call has written: NaN in every number (a head row added to an unwritten row stays NaN, too)"""
     import torch
     cd = np.complex64 if fd == np.float32 else np.complex128
     if device:
-        return torch.full((len(PAIRS), rows, nb), complex(float("nan"), float("nan")), dtype=getattr(torch, np.dtype(cd).name), device="cuda")
-    return np.full((len(PAIRS), rows, nb), complex(np.nan, np.nan), dtype=cd)
+        return torch.full((npairs, rows, nb), complex(float("nan"), float("nan")), dtype=getattr(torch, np.dtype(cd).name), device="cuda")
+    return np.full((npairs, rows, nb), complex(np.nan, np.nan), dtype=cd)
 
 
 @pytest.mark.parametrize("combo", ["f32f64", "f32f32"])

@@ -736,16 +736,24 @@ def test_filterbank_is_cut_again_when_the_tiles_change(combo, opts):
 # the analysis entry points interleaved on one plan
 # ---------------------------------------------------------------------------------------------
 PAIR_LISTS = ([(3, 3)], [(2, 0), (1, 3)])                    # (what a batched run draws its pair list from, beside PAIRS)
+# what a run with the covariance call draws its array from: a full group permuted, a padded group with two channels left to
+# advance-only items, one channel with three
+ARRAY_LISTS = ([3, 1, 0, 2], [2, 0], [1])
 
 
-def run_interleaved(combo, opts, m, seed, channels=1):
+def run_interleaved(combo, opts, m, seed, channels=1, covariance=False):
     """The body of test_analysis_entry_points_interleaved_on_one_plan; channels > 1 (tests/test_gpu_cross_sum_routes.py): a batched
     plan, the samples signals(td, n, seed), cross_sum a sixth kind, every expectation per channel.  p and pool carry a pair list,
     drawn again before some calls and installed in both (installing a list does not touch the state); the cross-spectrum call is
     checked as the pooled power call is -- pool's own call with the same memory, bit for bit, the same time chunks -- and against
     the twin's rows: at every == 1, first == 0 the bits of numpy's unfused expression, elsewhere check_pairs' bar for an exact
-    route.  The state compared after every call is that of all channels, the ones no pair names included."""
-    from sdft_amd.sdft import every_rows
+    route.  The state compared after every call is that of all channels, the ones no pair names included.
+    covariance = True (tests/test_gpu_covariance_routes.py; channels > 1): covariance is a seventh kind; p and pool carry an array
+    as well, drawn again from ARRAY_LISTS before some calls and before every covariance call (the state stays), and the call is
+    checked as the cross-spectrum call is, its pairs being the array's upper triangle.  The kinds are then a drawn order of equal
+    shares, not independent draws, and a list no call has run on yet is drawn before the others: every kind has run, and the
+    covariance call on every array, whatever the seed."""
+    from sdft_amd.sdft import covariance_pairs, every_rows
     from test_gpu_cross_sum import PAIRS, check_pairs, signals, terms
     td, fd, _ = O.combo_types(combo)
     batched = channels > 1
@@ -759,9 +767,11 @@ def run_interleaved(combo, opts, m, seed, channels=1):
     assert lengths.size == calls and lengths.sum() == n and (lengths >= 1).all()
     x = signals(td, n, seed, channels) if batched else signal(n, td, 50 + seed)
     bank = in_fd(random_bands(m), fd)
-    names = ("sdft", "every", "power", "power_sum", "filterbank") + (("cross_sum",) if batched else ())
+    covariance = covariance and batched
+    names = ("sdft", "every", "power", "power_sum", "filterbank") + (("cross_sum",) if batched else ()) + (("covariance",) if covariance else ())
     lists = (PAIRS,) + PAIR_LISTS
-    seen, installed = set(), set()
+    seen, installed, arrays = set(), set(), set()
+    order = rng.permutation(np.resize(np.arange(len(names)), calls)) if covariance else None
 
     def install(pairs, *plans):
         for q in plans:
@@ -770,13 +780,26 @@ def run_interleaved(combo, opts, m, seed, channels=1):
         installed.add(tuple(pairs))
         return pairs
 
+    def install_array(chan, *plans):
+        for q in plans:
+            q.set_array(chan)
+            assert q.array_channels == len(chan)
+        a, b = covariance_pairs(len(chan))
+        return [(chan[i], chan[j]) for i, j in zip(a.tolist(), b.tolist())]
+
+    def draw(seq, done=None):
+        left = [s for s in seq if tuple(s) not in done] if covariance and done is not None else []
+        return (left or seq)[int(rng.integers(0, len(left or seq)))]
+
     with make(m, "hann", combo, channels, **opts) as p, make(m, "hann", combo, channels, **opts) as twin, \
             make(m, "hann", combo, channels, **opts) as lone, make(m, "hann", combo, channels, **opts) as pool:
         p.set_filterbank(*bank); lone.set_filterbank(*bank)
         pairs = install(PAIRS, p, pool) if batched else None
+        chan = ARRAY_LISTS[0]
+        elements = install_array(chan, p, pool) if covariance else None
         t = 0
         for i, k in enumerate(lengths.tolist()):
-            kind = names[int(rng.integers(0, len(names)))]
+            kind = names[int(order[i])] if covariance else names[int(rng.integers(0, len(names)))]
             every = int(rng.choice([1, 2, 3, 7, 100, int(rng.integers(1, 600))]))
             first = int(rng.integers(0, every + 2))
             b0 = int(rng.integers(0, m))
@@ -789,7 +812,13 @@ def run_interleaved(combo, opts, m, seed, channels=1):
             rows = twin.sdft(xs)
             if batched and int(rng.integers(0, 3)) == 0:     # a list installed mid-stream: the state stays
                 was = p.state()
-                pairs = install(lists[int(rng.integers(0, len(lists)))], p, pool)
+                pairs = install(draw(lists, installed), p, pool)
+                now = p.state()
+                assert all(same_bits(u, v) for u, v in zip(was[:3], now[:3])) and was[3] == now[3], what
+            if covariance and (kind == "covariance" or int(rng.integers(0, 3)) == 0):    # an array installed mid-stream: the state stays
+                was = p.state()
+                chan = draw(ARRAY_LISTS, arrays if kind == "covariance" else None)
+                elements = install_array(chan, p, pool)
                 now = p.state()
                 assert all(same_bits(u, v) for u, v in zip(was[:3], now[:3])) and was[3] == now[3], what
             if kind == "sdft":
@@ -813,11 +842,22 @@ def run_interleaved(combo, opts, m, seed, channels=1):
                         re, im = terms(rows[a][:, cols], rows[b][:, cols])
                         assert same_bits(host[j].real, re) and same_bits(host[j].imag, im), (what, (a, b))
                 check_pairs(host, rows, pairs, k, every, first, band, True, what)
+            elif kind == "covariance":
+                got, want = p.covariance(xin, every, first, bins=band), pool.covariance(xin, every, first, bins=band)
+                assert p.get_option("last_kernel") == 9 and pool.get_option("last_kernel") == 9, what
+                assert (p.get_option("last_chunks"), p.get_option("last_chunk_len")) == (pool.get_option("last_chunks"), pool.get_option("last_chunk_len")), what
+                host = got.cpu().numpy() if hasattr(got, "cpu") else got
+                if every == 1 and first == 0:
+                    for j, (a, b) in enumerate(elements):
+                        re, im = terms(rows[a][:, cols], rows[b][:, cols])
+                        assert same_bits(host[j].real, re) and same_bits(host[j].imag, im), (what, (a, b))
+                check_pairs(host, rows, elements, k, every, first, band, True, what)
+                arrays.add(tuple(chan))
             else:
                 lone.set_state(*before)
                 got, want = p.filterbank(xin, every, first), lone.filterbank(xs, every, first)
                 assert got.shape == ((channels,) if batched else ()) + (every_rows(k, every, first), bank[0].size), what
-            if kind not in ("power_sum", "cross_sum"):
+            if kind not in ("power_sum", "cross_sum", "covariance"):
                 pool.sdft(xs)
             assert same_bits(got, want if hasattr(want, "cpu") else np.ascontiguousarray(want)), what
             assert same_state(p, twin) and same_state(pool, twin), what
@@ -825,6 +865,7 @@ def run_interleaved(combo, opts, m, seed, channels=1):
             t += k
     assert len(seen) == len(names), seen
     assert not batched or len(installed) == len(lists), installed
+    assert not covariance or len(arrays) == len(ARRAY_LISTS), arrays
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2])
