@@ -118,11 +118,14 @@ def window_sums(P, w, t):
 
 def reference(X, a, b, s, cache):
     """the terms of pair (a, b) over the band's columns s, their prefix sums and |terms|, once per (pair, band); the pair (b, a)
-    of one that is there is its conjugate, exactly (numpy's products commute and x - y = -(y - x))"""
+    of one that is there is its conjugate in value (numpy's products commute and x - y = -(y - x)), so re, the prefix sums and
+    |terms| are taken from it.  The im terms are formed again all the same: where the difference is zero its SIGN is not that of
+    -(y - x) -- (-0) - (+0) is -0 and (+0) - (-0) is +0 -- and at one bin every product of an im term is a zero of either sign
+    (the rows are real), so the negated terms of (b, a) are not the expression's bits there"""
     if (a, b) not in cache:
         if (b, a) in cache:
-            (re, pre, are), (im, (H, E), aim) = cache[(b, a)]
-            cache[(a, b)] = [(re, pre, are), (-im + im.dtype.type(0), (-H, -E), aim)]     # (+ 0: a difference of equals is +0)
+            (re, pre, are), (_, (H, E), aim) = cache[(b, a)]
+            cache[(a, b)] = [(re, pre, are), (terms(X[a][:, s], X[b][:, s])[1], (-H, -E), aim)]
         else:
             cache[(a, b)] = [(t, prefix_sums(t), np.abs(t).astype(np.float64)) for t in terms(X[a][:, s], X[b][:, s])]
     return cache[(a, b)]
@@ -309,6 +312,27 @@ def test_cross_sum_all_ordered_pairs(combo):
         assert np.count_nonzero(s[0 * CH + 2].imag) > 0
         q.sdft(x)
         check_state(p, q, exact, (combo, "all pairs"))
+
+
+@pytest.mark.parametrize("combo,opts", [("f32f32", {}), ("f32f64", {"carry": 1})])
+def test_cross_sum_one_bin_both_orders_of_independent_channels(combo, opts):
+    """A plan of one bin: the rows are real, so every product of an im term is a zero whose sign follows the signs of the two real
+    parts, and so is the term.  With two independent channels named in both orders the im term of (0, 2) is -0 where that of (2, 0)
+    is +0 and +0 where it is +0: not its negation.  The call forms each pair's expression on its own, as numpy does, bit for bit
+    (every = 1, first = 0, exact carries, several chunks) -- what the sweep of tests/test_gpu_fuzz_grid.py found the reference of
+    this file to get wrong (SDFT_FUZZ_OFFSET=1000, seed 33: it negated the cached terms of the other order)."""
+    m, n, pairs = 1, 3000, [(2, 0), (0, 2), (2, 1), (1, 2)]
+    x, X = rows_of(combo, "boxcar", m, n)
+    im20, im02 = terms(X[2], X[0])[1], terms(X[0], X[2])[1]
+    assert not np.any(im20) and not np.any(im02) and 0 < np.count_nonzero(np.signbit(im02)) < n         # zeros of both signs
+    assert not same_bits(im02, -im20 + im20.dtype.type(0)) and not same_bits(im02, -im20)
+    with plan(m, "boxcar", combo, pairs=pairs, **opts) as p:
+        for i in range(2):
+            p.reset()
+            got = p.cross_sum(to_dev(x) if i else x, 1, 0)
+            got = got.cpu().numpy() if i else got
+            assert p.get_option("last_kernel") == 8 and p.get_option("last_chunks") > 1
+            check_pairs(got, X, pairs, n, 1, 0, (0, 1), True, (combo, opts, "one bin, both orders", i))
 
 
 @pytest.mark.parametrize("combo", ["f32f64", "f64f32"])

@@ -105,7 +105,11 @@ def bands_of(m, p):
     bands = [(0, m), (0, 1), (m - 1, 1)]
     if m >= 3:
         bands.append((1, m - 2))            # the odd start puts the float pairs off 8-byte alignment
-    bands += [b for b in ((61, 3), (123, 3), (50, 100)) if b[0] + b[1] <= m]   # across the first boundaries of 62-lane tiles
+    # (61, 3) and (123, 3) lie across the first boundaries of tiles of 62 bins, the geometry of the test hook interior = 62 at FD
+    # double; no default tile (56 or 64 lanes: 56 / 64 bins at FD double, 112 / 128 at FD float) ends inside them.  Of the default
+    # tiles' boundaries (50, 100) crosses the first, and the two narrow bands from the plan's own per sit on it: the last bin of
+    # tile 0 with the first of tile 1, and the first bin of tile 1 alone
+    bands += [b for b in ((61, 3), (123, 3), (50, 100), (per - 1, 2), (per, 1)) if b[0] + b[1] <= m]
     bands.append(inside)
     return list(dict.fromkeys(bands))
 
