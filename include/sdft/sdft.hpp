@@ -48,7 +48,11 @@ const char* sdft_hip_last_error(void);
   int sdft_hip_set_array_##SUF(void* plan, std::size_t nch, const std::size_t* chan);                                  \
   std::size_t sdft_hip_array_channels_##SUF(const void* plan);                                                         \
   long sdft_hip_sdft_covariance_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, \
-                                        std::size_t bin0, std::size_t nbins, void* cov);
+                                        std::size_t bin0, std::size_t nbins, void* cov);                                \
+  int sdft_hip_set_mix_##SUF(void* plan, std::size_t nout, std::size_t nch, const std::size_t* chan, const void* weights); \
+  std::size_t sdft_hip_mix_outputs_##SUF(const void* plan);                                                            \
+  long sdft_hip_sdft_mix_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first,   \
+                                 std::size_t bin0, std::size_t nbins, void* out);
 SDFT_HPP_DECLARE(f32f64, float)
 SDFT_HPP_DECLARE(f32f32, float)
 SDFT_HPP_DECLARE(f64f64, double)
@@ -94,6 +98,9 @@ namespace sdft
       static int set_array(void* p, std::size_t nc, const std::size_t* c) { return sdft_hip_set_array_##SUF(p, nc, c); } \
       static std::size_t array_channels(const void* p) { return sdft_hip_array_channels_##SUF(p); } \
       static long sdft_covariance_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_covariance_n_##SUF(p, n, x, e, f, b, k, d); } \
+      static int set_mix(void* p, std::size_t no, std::size_t nc, const std::size_t* c, const void* w) { return sdft_hip_set_mix_##SUF(p, no, nc, c, w); } \
+      static std::size_t mix_outputs(const void* p) { return sdft_hip_mix_outputs_##SUF(p); } \
+      static long sdft_mix_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_mix_n_##SUF(p, n, x, e, f, b, k, d); } \
     };
     SDFT_HPP_ABI(f32f64, float, double)
     SDFT_HPP_ABI(f32f32, float, float)
@@ -310,6 +317,38 @@ namespace sdft
       {
         const char* e = sdft_hip_last_error();
         throw std::runtime_error(std::string("sdft_hip_sdft_covariance_n: ") + (e ? e : "failed"));
+      }
+      return static_cast<std::size_t>(rows);
+    }
+
+    /**
+     * Installs (copies) a mix in the plan (sdft_hip_set_mix; host memory): nout weight tables [nch][dftsize] for an ordered list
+     * of nch distinct channels, chan == nullptr for the channels 0 ... nch - 1.  The weights are applied as written.  nout == 0
+     * removes the mix.  Independent of set_pairs(), set_array() and the filterbank.
+     **/
+    void set_mix(const std::size_t nout, const std::size_t nch, const std::complex<F>* weights, const std::size_t* chan = nullptr)
+    {
+      if (api::set_mix(plan_, nout, nch, chan, weights) != 0)
+      {
+        const char* e = sdft_hip_last_error();
+        throw std::runtime_error(std::string("sdft_hip_set_mix: ") + (e ? e : "failed"));
+      }
+    }
+    /** Outputs of the installed mix, 0 for none. */
+    std::size_t mix_outputs() const { return api::mix_outputs(plan_); }
+
+    /**
+     * Channel-mix analysis (sdft_hip_sdft_mix_n): the per-bin weighted sums of the installed mix at the rows of every()'s grid,
+     * for the bins bin0 ... bin0 + nbins - 1; out is dense (nout, rows, nbins).  Returns the number of rows written.
+     **/
+    std::size_t mix(const std::size_t nsamples, const T* samples, const std::size_t every, const std::size_t first,
+                    const std::size_t bin0, const std::size_t nbins, std::complex<F>* const out)
+    {
+      const long rows = api::sdft_mix_n(plan_, nsamples, samples, every, first, bin0, nbins, out);
+      if (rows < 0)
+      {
+        const char* e = sdft_hip_last_error();
+        throw std::runtime_error(std::string("sdft_hip_sdft_mix_n: ") + (e ? e : "failed"));
       }
       return static_cast<std::size_t>(rows);
     }

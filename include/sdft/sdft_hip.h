@@ -351,6 +351,53 @@ long sdft_hip_sdft_covariance_n(sdft_t* sdft, const sdft_size_t nsamples, const 
                                 const sdft_size_t bin0, const sdft_size_t nbins,
                                 sdft_fdx_t* cov) SDFT_HIP_SYMBOL(sdft_covariance_n);
 
+/* ---- channel-mix analysis ------------------------------------------------------------------------------
+   The step every consumer of the covariance call ends with -- an MVDR / GEV beamformer, a multichannel Wiener filter, a per-bin
+   demixing matrix: a per-bin linear combination of the channels' spectra,
+     Y_o[t][k] = sum over the elements i of W[o][i][k] * X_chan[i][t][k],
+   formed in registers from the windowed bins, so that no channel's spectrum ever reaches memory.
+   A mix belongs to the plan: an ordered list of nch DISTINCT channels of a batched plan (its elements; the rule is
+   sdft_hip_set_array's: chan is HOST memory, chan == NULL means the channels 0 ... nch - 1) and nout weight tables.  weights is
+   [nout][nch][dftsize] complex numbers in HOST memory and is applied as written: a host that wants w^H x passes conjugates.
+   sdft_hip_set_mix installs (copies) one; nout == 0 removes the mix, whatever the other arguments.  Returns 0, or -1 with
+   sdft_hip_last_error() set and the previous mix untouched: a NULL plan, weights == NULL with nout > 0, nch == 0 with nout > 0,
+   nch > channels, an index >= channels, a repeated index, more than 65535 outputs, or a table that cannot be reserved.  The mix is
+   independent of the pair list, the array and the filterbank: all may be installed.
+   sdft_hip_mix_outputs: the installed mix's nout, 0 for none or a NULL plan. */
+int         sdft_hip_set_mix(sdft_t* sdft, const sdft_size_t nout, const sdft_size_t nch, const sdft_size_t* chan,
+                             const sdft_fdx_t* weights) SDFT_HIP_SYMBOL(set_mix);
+sdft_size_t sdft_hip_mix_outputs(const sdft_t* sdft) SDFT_HIP_SYMBOL(mix_outputs);
+/* sdft_hip_sdft_mix_n takes its grid, row count, streaming rule and the next call's first from sdft_hip_sdft_every_n (sampled
+   rows, not pooled windows), and the band arguments and the host / device pointer rules from sdft_hip_sdft_power_n.  samples is
+   [channels][nsamples]; out is [nout][rows][nbins] complex numbers (re, im), dense, aligned to sizeof(sdft_fd_t) only; it may be
+   NULL when the call keeps no row.
+   The value, exactly.  Let y_i = (yr, yi) be the windowed, weighted bin of element i as sdft_sdft_n stores it at the grid sample,
+   and w_i = (wr, wi) its weight for this output and bin.  The term is formed in sdft_fd_t with no fused multiply-add,
+     re = fl(fl(wr * yr) - fl(wi * yi))        im = fl(fl(wr * yi) + fl(wi * yr)),
+   and the output is the sequential sum of the terms: the accumulator starts at -0, the terms are added in ascending element order
+   i = 0 ... nch - 1, each component by itself, in sdft_fd_t.  The bits do not depend on how the kernel groups channels or outputs.
+   (1) The same plan, options and input give the same bits on every run (no atomics).
+   (2) The value is exactly that expression on the channels' sdft_sdft_n rows wherever that call is bit-identical to the
+       reference: FD float, FD double with option "carry" = 1, calls shorter than 512 samples -- for any every, first, band, cut of
+       time into chunks, or cut of a stream into calls.  A row's bits depend only on the plan, the mix and that row's bins.
+   (3) A one-hot mix (weight 1 for one element, 0 for the others) returns sdft_hip_sdft_every_n's row of that channel as numbers,
+       for finite bins; zeros may differ in sign.
+   (4) On the other routes the row deviation sdft_hip_sdft_every_n documents comes on top: with E_i = 1e-11 times the largest
+       |bin| of channel chan[i] over the call, each component moves by at most sum over i of (|wr_i| + |wi_i|) E_i  (from
+       |d re| <= |wr| |d yr| + |wi| |d yi|), plus what the 3 nch roundings of a component make of it: gamma_(nch + 1) times
+       sum over i of (|wr_i| + |wi_i|) (|yr_i| + |yi_i|), gamma_n = n u / (1 - n u), u = 2^-53.
+   (5) The stream state of EVERY channel of the plan, in the mix or not, is afterwards what sdft_sdft_n of the same samples
+       leaves: every channel has exactly one writer.  Any other entry point may follow.
+   No workspace: the running sum of a row lives in the row itself between the groups of channels a wave takes.  Rows on their way
+   to HOST memory are formed in device scratch, segment by segment, and copied out.
+   The call is never resident, pipelined or fused and always runs its own kernel ("last_kernel" = 10).  Returns the number of rows
+   written (0 for nsamples == 0), or -1 with sdft_hip_last_error() set and the stream state untouched: a NULL plan, no mix
+   installed, every == 0, nbins == 0, bin0 + nbins > dftsize, out == NULL with rows > 0. */
+long sdft_hip_sdft_mix_n(sdft_t* sdft, const sdft_size_t nsamples, const sdft_td_t* samples,
+                         const sdft_size_t every, const sdft_size_t first,
+                         const sdft_size_t bin0, const sdft_size_t nbins,
+                         sdft_fdx_t* out) SDFT_HIP_SYMBOL(sdft_mix_n);
+
 /* ---- streams ---------------------------------------------------------------------------------
    Every plan owns a HIP stream.  Calls with host pointers always return with the output
    complete.  Calls with device pointers do too unless option "async" is 1; then they return after
@@ -462,14 +509,15 @@ double sdft_hip_time_hops(sdft_t* sdft, size_t hops, size_t hop, const sdft_td_t
    -DSDFT_HIP_TEST_HOOKS (libsdft_hip_hooks.so, built beside the product by `python -m sdft_amd.build`; no host links it) accept the keys that force
    those forks, so that the tests can run every route against the reference and the probes under scripts/ can measure them:
    "rows_kernel", "row_slots_max", "interior", "fused", "fft_carry", "fold", "rows_f32", "hop_parts", "xcd_map", "chain_block", "relay_waves", "inverse_verify",
-   "relay_flow", "relay_groups", "chain_debug", "inverse_nt", "inverse_nt_skip_mb", "inverse_step", "inverse_ordered", "host_direct", "copy_streams", "prefix_cells", "array_group" (sdft_capi.inc names what each selects);
+   "relay_flow", "relay_groups", "chain_debug", "inverse_nt", "inverse_nt_skip_mb", "inverse_step", "inverse_ordered", "host_direct", "copy_streams", "prefix_cells", "array_group", "mix_group", "mix_block" (sdft_capi.inc names what each selects);
    get_option "test_hooks" = 1 in that build.
    get_option additionally answers "tiles", "bins_per_lane", "row_slots", "last_chunks",
-   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis, 6 pooled power analysis, 7 filterbank analysis, 8 pooled cross-spectrum analysis, 9 array covariance analysis), "last_segments", "last_fused",
+   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis, 6 pooled power analysis, 7 filterbank analysis, 8 pooled cross-spectrum analysis, 9 array covariance analysis, 10 channel-mix analysis), "last_segments", "last_fused",
    "last_filterbank_launches" (forward_filterbank_kernel launches of the last filterbank call, over all of its host segments: more than its carry segments once its pieces exceed the workspace bound),
    "last_chain", "last_fused_exact", "last_fused_fold", "last_process_path" (1 fused kernel, 2 hop pair, 3 two-pass),
    "last_self" (no pre-pass launch), "last_prefix" (long calls: one pre-pass launch, prefix_cells_kernel), "last_inverse_nt" / "last_inverse_skip" (what the last synthesis launch used: non-temporal loads, rows read with ordinary loads),
    "array_group" (channels per group of a register block of sdft_hip_sdft_covariance_n),
+   "mix_group" / "mix_block" (channels per group and outputs per block of a wave of sdft_hip_sdft_mix_n),
    "cursor", "device", "ring_recoveries" (calls re-run with the serial carry pass after a poll loop of
    the exact-carry kernels timed out: results stay valid, sdft_hip_last_warning() reports it), "flag_fallbacks". */
 int  sdft_hip_set_option(sdft_t* sdft, const char* key, long value) SDFT_HIP_SYMBOL(set_option);

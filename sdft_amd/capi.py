@@ -65,6 +65,9 @@ def typed_signatures(combo: str):
         "set_array": (C.c_int, [vp, sz, vp]),
         "array_channels": (sz, [vp]),
         "sdft_covariance_n": (C.c_long, [vp, sz, vp, sz, sz, sz, sz, vp]),
+        "set_mix": (C.c_int, [vp, sz, sz, vp, vp]),
+        "mix_outputs": (sz, [vp]),
+        "sdft_mix_n": (C.c_long, [vp, sz, vp, sz, sz, sz, sz, vp]),
     }
 
 

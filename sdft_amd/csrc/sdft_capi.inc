@@ -153,6 +153,21 @@ long SDFT_FN(sdft_covariance_n)(void* p, size_t n, const SDFT_TD* x, size_t ever
   if (rows > (size_t)LONG_MAX) { sdfthip::set_error("sdft_hip_sdft_covariance_n", "more rows than a long can count"); return -1; }
   return (long)rows;
 }
+// channel-mix analysis: per-bin weighted sums of the windowed bins of the channels of a mix on a row grid; see sdft_hip.h
+int SDFT_FN(set_mix)(void* p, size_t nout, size_t nch, const size_t* chan, const SDFT_FD* weights)
+{
+  if (!p) { sdfthip::set_error("sdft_hip_set_mix", "NULL plan"); return -1; }
+  return P(p)->set_mix(nout, nch, chan, reinterpret_cast<const sdfthip::cx<SDFT_FD>*>(weights)) ? 0 : -1;
+}
+size_t SDFT_FN(mix_outputs)(const void* p) { return p ? P(p)->mix_outputs() : 0; }
+long SDFT_FN(sdft_mix_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, size_t bin0, size_t nbins, SDFT_FD* out)
+{
+  if (!p) { sdfthip::set_error("sdft_hip_sdft_mix_n", "NULL plan"); return -1; }
+  size_t rows = 0;
+  if (!P(p)->sdft_mix_n(n, x, every, first, bin0, nbins, out, rows)) return -1;
+  if (rows > (size_t)LONG_MAX) { sdfthip::set_error("sdft_hip_sdft_mix_n", "more rows than a long can count"); return -1; }
+  return (long)rows;
+}
 int SDFT_FN(set_stream)(void* p, void* hip_stream) { return p && P(p)->set_stream(static_cast<hipStream_t>(hip_stream)) ? 0 : -1; }
 // (a host that asks for the stream may queue work of its own behind a call: from here on every kernel of the plan is on it)
 void* SDFT_FN(get_stream)(void* p)
@@ -237,6 +252,8 @@ int SDFT_FN(set_option)(void* p, const char* key, long value)
   else if (!strcmp(key, "host_direct")) q->io.opt_host_direct = value;         // 0: a hop-sized host matrix by DMA between staging matrix and pinned pieces
   else if (!strcmp(key, "copy_streams")) q->io.opt_copy_streams = value;       // 1: the DMAs of long host copies on one stream
   else if (!strcmp(key, "array_group")) q->opt_array_group = value;            // covariance call: channels per group (1, 2, 4), 0: the build's choice
+  else if (!strcmp(key, "mix_group")) q->opt_mix_group = value;                // mix call: channels per group (2, 4, 8), 0: the build's choice
+  else if (!strcmp(key, "mix_block")) q->opt_mix_block = value;                // mix call: outputs per block (1, 2, 4), 0: the build's choice
   else if (!strcmp(key, "prefix_cells")) q->opt_prefix_cells = value;          // prefix-cell route of long calls: 0 never, 1 beyond 2^19 samples, 2 whatever the length
 #ifdef SDFT_SELF_STAMPS
   else if (!strcmp(key, "self_stamps")) q->opt_self_stamps = value;
@@ -303,6 +320,8 @@ long SDFT_FN(get_option)(const void* p, const char* key)
   if (!strcmp(key, "prefix_cells")) return q->opt_prefix_cells;
 #endif
   if (!strcmp(key, "array_group")) return q->array_group();
+  if (!strcmp(key, "mix_group")) return q->mix_group_size();
+  if (!strcmp(key, "mix_block")) return q->mix_block_size();
   if (!strcmp(key, "host_register")) return q->io.opt_host_register;
   if (!strcmp(key, "host_register_hits")) return q->io.host_reg_hits;
   if (!strcmp(key, "host_copy")) return q->io.opt_host_copy;

@@ -20,6 +20,8 @@
 //                          bins of two channels of a plan, summed in registers over the windows of the grid (sdft_hip_sdft_cross_sum_n)
 //   sdft_forward_covariance.hpp K1v forward_covariance_kernel: the cross-spectrum kernel with groups of channels in place of channels --
 //                          all pairs of an array by register blocks of G x G pairs (sdft_hip_sdft_covariance_n)
+//   sdft_forward_mix.hpp   K1m   forward_mix_kernel: forward_power_kernel's grid with the covariance kernel's groups of channels -- per-bin
+//                          weighted sums of the windowed bins of the channels of a mix, for blocks of outputs (sdft_hip_sdft_mix_n)
 //   sdft_forward_filterbank.hpp K1f forward_filterbank_kernel: the powers of a kept row go to a wave-private strip of LDS and the lanes
 //                          form the weighted sums of the pieces of the plan's bands that lie in the tile; filterbank_rows_kernel adds
 //                          the pieces of the bands a tile boundary cuts (sdft_hip_sdft_filterbank_n)
@@ -57,6 +59,7 @@
 #include "sdft_forward_power_sum.hpp"
 #include "sdft_forward_cross_sum.hpp"
 #include "sdft_forward_covariance.hpp"
+#include "sdft_forward_mix.hpp"
 #include "sdft_forward_filterbank.hpp"
 #include "sdft_forward_hop.hpp"
 #include "sdft_ops.hpp"

@@ -101,6 +101,8 @@ static_assert(sizeof(logic::CrossItem) == sizeof(CrossItem) && offsetof(logic::C
               offsetof(logic::CrossItem, writes_b) == offsetof(CrossItem, writes_b), "cross-spectrum items");
 static_assert(sizeof(logic::CovItem) == sizeof(CovItem) && offsetof(logic::CovItem, b0) == offsetof(CovItem, b0) && offsetof(logic::CovItem, nb) == offsetof(CovItem, nb) &&
               offsetof(logic::CovItem, writes) == offsetof(CovItem, writes), "covariance items");
+static_assert(sizeof(logic::MixItem) == sizeof(MixItem) && offsetof(logic::MixItem, no) == offsetof(MixItem, no) &&
+              offsetof(logic::MixItem, writes) == offsetof(MixItem, writes), "mix items");
 
 enum CarryMode : int { CARRY_FAST = 0, CARRY_EXACT = 1 };
 
@@ -203,7 +205,7 @@ class Plan
   long opt_prefix_cells = 1;     // test hook: the prefix-cell route of long calls (logic::ForwardQuery::prefix_cells)
   long last_prefix = 0;          // the last analysis call took it (one pre-pass launch: prefix_cells_kernel)
 
-  long last_kernel = 0;          // 1 = forward_kernel (independent tiles), 2 = forward_rows_kernel, 3 = hop, 4 = forward_every_kernel, 5 = forward_power_kernel, 6 = forward_pooled_power_kernel, 7 = forward_filterbank_kernel, 8 = forward_cross_sum_kernel, 9 = forward_covariance_kernel
+  long last_kernel = 0;          // 1 = forward_kernel (independent tiles), 2 = forward_rows_kernel, 3 = hop, 4 = forward_every_kernel, 5 = forward_power_kernel, 6 = forward_pooled_power_kernel, 7 = forward_filterbank_kernel, 8 = forward_cross_sum_kernel, 9 = forward_covariance_kernel, 10 = forward_mix_kernel
 
   // device-resident stream state
   DevBuf<fdx> d_tw, d_syn, d_wtab;
@@ -284,6 +286,21 @@ class Plan
   DevBuf<unsigned> d_cov_chan;
   DevBuf<FD> d_cov_ws, d_cov_head, d_cov_stage;
   long opt_array_group = 0;                                // test hook: channels per group (1, 2, 4), 0: the build's choice
+  // channel-mix analysis: the installed mix (sdft_hip_set_mix) -- its channels, its work items (logic::mix_items) for blocks of
+  // `block` outputs and their device copy, the channels and the weight table [nout][nch][N] on the device -- and the stage of a
+  // segment's rows on their way to a host buffer
+  struct Mix
+  {
+    std::vector<size_t> chan;
+    std::vector<logic::MixItem> items;
+    size_t nout = 0;
+    int block = 0;
+  } mix;
+  DevBuf<MixItem> d_mix_items;
+  DevBuf<unsigned> d_mix_chan;
+  DevBuf<fdx> d_mix_weights;
+  DevBuf<FD> d_mix_stage;
+  long opt_mix_group = 0, opt_mix_block = 0;               // test hooks: channels per group (2, 4, 8), outputs per block (1, 2, 4), 0: the build's choice
 
   // profile: HIP events on the plan's stream, one pair per stage launch, collected lazily so
   // that back-to-back asynchronous calls are never serialised by the measurement
@@ -338,6 +355,7 @@ class Plan
     d_fb_pieces.release(); d_fb_tile0.release(); d_fb_splits.release(); d_fb_weights.release(); d_fb_ws.release();
     d_cross_items.release(); d_cross_ws.release(); d_cross_head.release(); d_cross_stage.release();
     d_cov_items.release(); d_cov_chan.release(); d_cov_ws.release(); d_cov_head.release(); d_cov_stage.release();
+    d_mix_items.release(); d_mix_chan.release(); d_mix_weights.release(); d_mix_stage.release();
     d_gain.release(); d_stage_y.release(); d_chain_stats.release();
     d_alpha.release(); d_beta.release(); d_partial.release(); d_tickets.release();
     if (h_done_flag) { (void)hipHostFree(h_done_flag); h_done_flag = nullptr; }
@@ -579,14 +597,15 @@ class Plan
   // fbk: filterbank analysis (sdft_filterbank_n) -- forward_filterbank_kernel stores the band sums of the plan's filterbank (out is unused)
   // cross: cross-spectrum analysis (sdft_cross_sum_n) -- forward_cross_sum_kernel sums A conj(B) of the plan's pairs over the grid's windows (out is unused)
   // cov: covariance analysis (sdft_covariance_n) -- forward_covariance_kernel does that for all pairs of the plan's array, by blocks (out is unused)
+  // mixa: channel-mix analysis (sdft_mix_n) -- forward_mix_kernel stores the weighted sums of the plan's mix on the grid (out is unused)
   bool forward_device(size_t n, const TD* x, size_t x_stride, fdx* out, size_t out_stride, fdx* const* rows,
                       const FuseArgs<TD, FD>* fuse = nullptr, const EveryGrid* every = nullptr, const PowerArgs<FD>* power = nullptr,
                       const PowerSumArgs<FD>* psum = nullptr, const FilterbankArgs<FD>* fbk = nullptr,
-                      const CrossSumArgs<FD>* cross = nullptr, const CovarianceArgs<FD>* cov = nullptr)
+                      const CrossSumArgs<FD>* cross = nullptr, const CovarianceArgs<FD>* cov = nullptr, const MixArgs<FD>* mixa = nullptr)
   {
     const struct { size_t cursor; int st_cur, hist_cur; bool fid_canonical; } was{cursor, st_cur, hist_cur, fid_canonical};
     auto restore = [&] { cursor = was.cursor; st_cur = was.st_cur; hist_cur = was.hist_cur; fid_canonical = was.fid_canonical; };
-    if (!forward_launch(n, x, x_stride, out, out_stride, rows, fuse, every, power, psum, fbk, cross, cov))
+    if (!forward_launch(n, x, x_stride, out, out_stride, rows, fuse, every, power, psum, fbk, cross, cov, mixa))
     {
       // a launch that failed half-way (a host expression that does not compile, a grid that does not fit, an allocation)
       // must not leave the stream half-advanced: what was queued wrote the OTHER buffer set and the workspace only
@@ -600,7 +619,7 @@ class Plan
     restore();
     const long saved = opt_chain;
     opt_chain = 0;
-    const bool ok = forward_launch(n, x, x_stride, out, out_stride, rows, fuse, every, power, psum, fbk, cross, cov) && (hipStreamSynchronize(stream) == hipSuccess);
+    const bool ok = forward_launch(n, x, x_stride, out, out_stride, rows, fuse, every, power, psum, fbk, cross, cov, mixa) && (hipStreamSynchronize(stream) == hipSuccess);
     opt_chain = saved;
     ++ring_recoveries;
     // a recovered call is a valid call: it goes to the warning channel (and the counter), not to the error channel, so a
@@ -616,13 +635,13 @@ class Plan
 
   logic::ForwardQuery forward_query(size_t n, const fdx* out, size_t out_stride, fdx* const* rows, const FuseArgs<TD, FD>* fuse, const EveryGrid* every,
                                    const PowerArgs<FD>* power, const PowerSumArgs<FD>* psum, const FilterbankArgs<FD>* fbk, const CrossSumArgs<FD>* cross,
-                                   const CovarianceArgs<FD>* cov) const
+                                   const CovarianceArgs<FD>* cov, const MixArgs<FD>* mixa) const
   {
     logic::ForwardQuery q;
     q.n = n; q.nbins = nbins; q.channels = channels; q.fd_bytes = sizeof(FD); q.fdx_bytes = sizeof(fdx);
     q.window = window; q.compute_units = compute_units; q.cursor = cursor; q.exact = carry_mode == CARRY_EXACT; q.fid_canonical = fid_canonical;
     q.fuse = fuse != nullptr; q.fuse_store = fuse && fuse->store; q.reference_order = fuse && wants_reference_order(); q.coeff_ready = coeff_ready;
-    q.every = every != nullptr; q.power = power != nullptr; q.power_every = power ? (size_t)power->every : fbk ? (size_t)fbk->every : 1; q.power_sum = psum != nullptr; q.filterbank = fbk != nullptr; q.cross_sum = cross != nullptr; q.cross_items = cross ? cross->nitems : cov ? cov->nitems : 0; q.covariance = cov != nullptr; q.row_pointers = rows != nullptr; q.out = reinterpret_cast<uintptr_t>(out); q.out_stride = out_stride;
+    q.every = every != nullptr; q.power = power != nullptr; q.power_every = power ? (size_t)power->every : fbk ? (size_t)fbk->every : mixa ? (size_t)mixa->every : 1; q.power_sum = psum != nullptr; q.filterbank = fbk != nullptr; q.cross_sum = cross != nullptr; q.cross_items = cross ? cross->nitems : cov ? cov->nitems : mixa ? mixa->nitems : 0; q.covariance = cov != nullptr; q.mix = mixa != nullptr; q.row_pointers = rows != nullptr; q.out = reinterpret_cast<uintptr_t>(out); q.out_stride = out_stride;
     q.analysis_batch = calls.analysis_batch; q.pipe_wanted = pipe_wanted(nullptr); q.prev_out = prev_out;
     q.rows_kernel = opt_rows_kernel; q.row_slots_max = opt_row_slots_max; q.interior = opt_interior; q.chunk = opt_chunk; q.self = opt_self;
     q.fused = opt_fused; q.fold = opt_fold; q.fft_carry = opt_fft_carry; q.hop_kernel = opt_hop_kernel; q.chain = opt_chain; q.chain_L = opt_chain_L;
@@ -636,13 +655,13 @@ class Plan
   bool forward_launch(size_t n, const TD* x, size_t x_stride, fdx* out, size_t out_stride, fdx* const* rows,
                       const FuseArgs<TD, FD>* fuse = nullptr, const EveryGrid* every = nullptr, const PowerArgs<FD>* power = nullptr,
                       const PowerSumArgs<FD>* psum = nullptr, const FilterbankArgs<FD>* fbk = nullptr,
-                      const CrossSumArgs<FD>* cross = nullptr, const CovarianceArgs<FD>* cov = nullptr)
+                      const CrossSumArgs<FD>* cross = nullptr, const CovarianceArgs<FD>* cov = nullptr, const MixArgs<FD>* mixa = nullptr)
   {
     if (n == 0 || nbins == 0) return true;
     SDFT_TRY(hipSetDevice(device));
     flag_pending = false;                                    // only the hop kernel signals its completion
     calls.on_analysis(fuse != nullptr);                      // (which kind of host is calling: logic::CallPattern)
-    const logic::ForwardRoute r = logic::forward_route(forward_query(n, out, out_stride, rows, fuse, every, power, psum, fbk, cross, cov), [this] { return gate_ok(); });
+    const logic::ForwardRoute r = logic::forward_route(forward_query(n, out, out_stride, rows, fuse, every, power, psum, fbk, cross, cov, mixa), [this] { return gate_ok(); });
     pipe_this = r.pipelined;
     if (r.out.hi) prev_out = r.out;
     last_kernel = r.kernel; last_chunks = r.chunks; last_chunk_len = r.len; last_tiles = r.tiles; last_interior = r.interior;
@@ -671,7 +690,7 @@ class Plan
     }
 
     DeltaIn<TD, FD> din;
-    if (!forward_delta(r, n, x, x_stride, din) || !forward_carries(r, n, din) || !forward_rows_stage(r, n, out, out_stride, rows, fuse, every, power, psum, fbk, cross, cov)) return false;
+    if (!forward_delta(r, n, x, x_stride, din) || !forward_carries(r, n, din) || !forward_rows_stage(r, n, out, out_stride, rows, fuse, every, power, psum, fbk, cross, cov, mixa)) return false;
 
     // fid stays on the canonical rotation sequence unless this call seeded chunks from the closed-form
     // table; a call that crosses the roll-over with serial fid arithmetic puts it back
@@ -828,7 +847,7 @@ class Plan
   // it, see forward_device)
   bool forward_rows_stage(const logic::ForwardRoute& r, size_t n, fdx* out, size_t out_stride, fdx* const* rows,
                           const FuseArgs<TD, FD>* fuse, const EveryGrid* every, const PowerArgs<FD>* power, const PowerSumArgs<FD>* psum,
-                          const FilterbankArgs<FD>* fbk, const CrossSumArgs<FD>* cross, const CovarianceArgs<FD>* cov)
+                          const FilterbankArgs<FD>* fbk, const CrossSumArgs<FD>* cross, const CovarianceArgs<FD>* cov, const MixArgs<FD>* mixa)
   {
     const size_t nb = nbins;
     const long chunks = r.chunks, segments = r.segments;
@@ -849,7 +868,7 @@ class Plan
       if (!d_cov_ws.reserve(logic::covariance_workspace(cv.nch, (size_t)chunks, cv.nbins_out))) return false;
       cv.ws = chunks > 1 ? d_cov_ws.p : nullptr;
     }
-    const size_t launch_channels = cross ? cs.nitems : cov ? cv.nitems : channels;
+    const size_t launch_channels = cross ? cs.nitems : cov ? cv.nitems : mixa ? mixa->nitems : channels;
     // pooled power analysis: the workspace of the windows a chunk boundary cuts (grown on demand, kept by the plan)
     PowerSumArgs<FD> ps{};
     if (psum)
@@ -939,6 +958,7 @@ class Plan
       }
       else if (cross) { if (!grid_fits(blocks)) return false; launch_forward_cross_sum(fa, cs, (unsigned)blocks); }
       else if (cov) { if (!grid_fits(blocks)) return false; if (!launch_forward_covariance(fa, cv, (unsigned)blocks)) return false; }
+      else if (mixa) { if (!grid_fits(blocks)) return false; if (!launch_forward_mix(fa, *mixa, (unsigned)blocks)) return false; }
       else if (psum) { if (!grid_fits(blocks)) return false; launch_forward_power_sum(fa, ps, (unsigned)blocks); }
       else if (power) { if (!grid_fits(blocks)) return false; launch_forward_power(fa, *power, (unsigned)blocks); }
       else if (every) { if (!grid_fits(blocks)) return false; launch_forward_every(fa, *every, (unsigned)blocks); }

@@ -609,6 +609,121 @@
     });
   }
 
+  // ---- channel-mix analysis ---------------------------------------------------------------------------------------------------------
+  // sdft_hip_set_mix: list and weights are host memory and are copied (chan == nullptr: the channels 0 ... nch - 1); a refused mix
+  // leaves the installed one as it is.  The work items (logic::mix_items) go to the device here, and again when a test hook changes
+  // the block size (upload_mix_items); the weight table [nout][nch][N] does not depend on it.
+  bool upload_mix_items(Mix& f, DevBuf<MixItem>& into)
+  {
+    f.block = mix_block_size();
+    f.items = logic::mix_items(channels, f.chan.size(), f.chan.data(), f.nout, f.block);
+    DevBuf<MixItem> table;
+    SDFT_TRY(hipStreamSynchronize(stream));
+    if (!table.reserve(f.items.size())) return false;
+    if (!to_device(table.p, f.items.data(), f.items.size() * sizeof(MixItem)) || hipStreamSynchronize(stream) != hipSuccess) { table.release(); return false; }
+    into.release();
+    into = table;
+    return true;
+  }
+  bool set_mix(size_t nout, size_t nch, const size_t* chan, const fdx* weights)
+  {
+    static const char* fn = "sdft_hip_set_mix";
+    switch (logic::mix_check(channels, nout, nch, chan, weights != nullptr))
+    {
+      case logic::MX_OK: break;
+      case logic::MX_NO_WEIGHTS: set_error(fn, "weights is NULL"); return false;
+      case logic::MX_NO_CHANNELS: set_error(fn, "a mix needs at least one channel (nch == 0)"); return false;
+      case logic::MX_CHANNEL: set_error(fn, "the list names a channel the plan does not have (index >= channels)"); return false;
+      case logic::MX_REPEAT: set_error(fn, "the list names a channel twice"); return false;
+      case logic::MX_TOO_MANY_OUTPUTS: set_error(fn, "too many outputs (more than 65535)"); return false;
+      default: set_error(fn, "the list is too long: more channels than the plan has (or than 65535)"); return false;
+    }
+    if (!bind()) return false;
+    if (!pipe_join()) return false;
+    Mix f;
+    if (nout)
+    {
+      f.nout = nout;
+      f.chan.resize(nch);
+      for (size_t i = 0; i < nch; ++i) f.chan[i] = chan ? chan[i] : i;
+      std::vector<unsigned> chan32(f.chan.begin(), f.chan.end());
+      // (fresh tables: whatever still reads the installed ones has drained before they are replaced, and a failure leaves them alone)
+      const size_t count = nout * nch * nbins;
+      if (nbins && count / nbins / nch != nout) { set_error(fn, "the weight table cannot be reserved"); return false; }
+      DevBuf<MixItem> table;
+      DevBuf<unsigned> list;
+      DevBuf<fdx> wtable;
+      auto drop = [&] { table.release(); list.release(); wtable.release(); return false; };
+      if (!list.reserve(chan32.size()) || !wtable.reserve(std::max<size_t>(count, 1))) return drop();
+      if (!upload_mix_items(f, table)) return drop();
+      if (!to_device(list.p, chan32.data(), chan32.size() * sizeof(unsigned)) || !to_device(wtable.p, weights, count * sizeof(fdx)) ||
+          hipStreamSynchronize(stream) != hipSuccess) return drop();
+      d_mix_items.release(); d_mix_chan.release(); d_mix_weights.release();
+      d_mix_items = table; d_mix_chan = list; d_mix_weights = wtable;
+    }
+    else
+    {
+      SDFT_TRY(hipStreamSynchronize(stream));
+      d_mix_items.release(); d_mix_chan.release(); d_mix_weights.release();
+    }
+    mix = std::move(f);
+    return true;
+  }
+  size_t mix_outputs() const { return mix.nout; }
+
+  // channel-mix analysis (sdft_hip_sdft_mix_n): the weighted sums of the installed mix at the rows of sdft_every_n's grid, for the
+  // bins of sdft_power_n's band, dense [nout][rows][nbins_out] complex numbers; the stream state afterwards is the one sdft_n
+  // leaves.  Never resident, pipelined or fused: one forward launch on the plan's stream (forward_mix_kernel), host memory in time
+  // segments as in sdft_power_n -- but rows on their way to a host buffer are formed in device scratch (d_mix_stage), so that the
+  // kernel never re-reads a running sum from host memory, and copied out output by output.
+  bool sdft_mix_n(size_t n, const TD* x, size_t every, size_t first, size_t bin0, size_t nbins_out, FD* out, size_t& rows)
+  {
+    static const char* fn = "sdft_hip_sdft_mix_n";
+    rows = 0;
+    const size_t nout = mix.nout, nch = mix.chan.size();
+    if (nout == 0) { set_error(fn, "no mix is installed (sdft_hip_set_mix)"); return false; }
+    if (every == 0) { set_error(fn, "every must be at least 1"); return false; }
+    if (nbins_out == 0) { set_error(fn, "nbins must be at least 1"); return false; }
+    if (!logic::power_band_ok(nbins, bin0, nbins_out)) { set_error(fn, "the band bin0 ... bin0 + nbins - 1 does not lie within the plan's bins"); return false; }
+    rows = logic::every_rows(n, every, first);
+    if (rows > 0 && !out) { set_error(fn, "out is NULL but the call keeps rows"); return false; }
+    if (n == 0) return true;
+    if (!bind()) return false;
+    if (!pipe_join()) return false;
+    if (mix.block != mix_block_size() && !upload_mix_items(mix, d_mix_items)) return false;      // (a test hook changed the block size)
+    if (every > n) every = n;                                // (the same grid: at most one row; keeps first + k * every in range)
+    const bool xd = on_device(x);
+    const bool od = rows == 0 || on_device(out);
+    const size_t nb2 = 2 * nbins_out;                        // numbers of a row of one output
+    const size_t row_bytes = nout * nb2 * sizeof(FD);
+    auto band = [&](FD* at, size_t at_rows, size_t f) {
+      return MixArgs<FD>{at, logic::mix_output_stride(at_rows, nbins_out), d_mix_weights.p, d_mix_items.p, d_mix_chan.p, (unsigned)mix.items.size(), (unsigned)nch,
+                         (unsigned)nout, (unsigned long long)every, (unsigned long long)f, (unsigned)bin0, (unsigned)nbins_out};
+    };
+    if (xd && od)
+    {
+      const MixArgs<FD> g = band(out, rows, first);
+      return forward_device(n, x, n, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &g) && finish(rows * row_bytes);
+    }
+    // host memory: segments of at most seg samples (rows kept and samples within stage_bytes), each one forward launch
+    size_t seg = n;
+    if (!od) seg = std::min(seg, logic::stage_rows(n, row_bytes, stage_bytes) * every);
+    if (!xd) seg = std::min(seg, std::max<size_t>((size_t)logic::kHopSamples, logic::stage_rows(n, channels * sizeof(TD), stage_bytes)));
+    const size_t seg_rows_max = (seg + every - 1) / every;
+    if (!od && !d_mix_stage.reserve(nout * seg_rows_max * nb2)) return false;
+    return staged_segments(n, seg, StagedCall{true, const_cast<TD*>(x), !xd, nullptr, false, rows, seg_rows_max, nb2 * sizeof(FD)}, [&](Segment& s) {
+      const size_t f = logic::every_first_from(s.t, every, first);
+      const size_t kept = logic::every_rows(s.m, every, f);
+      const size_t r0 = kept ? (s.t + f - first) / every : 0; // the segment's first row in the call's grid
+      s.rows = 0;                                            // (nothing for staged_segments to copy)
+      const MixArgs<FD> g = od ? band(kept ? out + r0 * nb2 : nullptr, rows, f) : band(d_mix_stage.p, kept, f);
+      if (!forward_device(s.m, s.td, s.td_stride, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &g)) return false;
+      for (size_t o = 0; o < nout && kept && !od; ++o)
+        if (!to_host(out + o * rows * nb2 + r0 * nb2, d_mix_stage.p + o * kept * nb2, kept * nb2 * sizeof(FD))) return false;
+      return true;
+    });
+  }
+
   // a host table of device rows goes to the device; nullptr: failed
   fdx* const* device_table(fdx* const* dfts, size_t n, bool table_on_device)
   {

@@ -402,6 +402,67 @@
     set_error("sdft_hip_sdft_covariance_n", "no kernel for the array's group size");
     return false;
   }
+  // channels per group and outputs per block of a mix call: the build's choice per FD type, or (test hooks) a candidate of
+  // scripts/mix_rates.py
+  int mix_group_size() const
+  {
+#ifdef SDFT_HIP_TEST_HOOKS
+    if (opt_mix_group == 2 || opt_mix_group == 4 || opt_mix_group == 8) return (int)opt_mix_group;
+#endif
+    return mix_group<FD>::value;
+  }
+  int mix_block_size() const
+  {
+#ifdef SDFT_HIP_TEST_HOOKS
+    if (opt_mix_block == 1 || opt_mix_block == 2 || opt_mix_block == 4) return (int)opt_mix_block;
+#endif
+    return mix_block<FD>::value;
+  }
+  template <int G, int O> void launch_forward_mix_go(const ForwardArgs<FD>& fa, const MixArgs<FD>& g, unsigned blocks)
+  {
+    constexpr int BPL = sizeof(fdx) == 16 ? 1 : 2;
+    const dim3 gr(blocks), b(kBlock);
+    switch (window)
+    {
+      case WIN_HANN:     hipLaunchKernelGGL((forward_mix_kernel<FD, BPL, WIN_HANN, G, O>), gr, b, 0, stream, fa, g); break;
+      case WIN_HAMMING:  hipLaunchKernelGGL((forward_mix_kernel<FD, BPL, WIN_HAMMING, G, O>), gr, b, 0, stream, fa, g); break;
+      case WIN_BLACKMAN: hipLaunchKernelGGL((forward_mix_kernel<FD, BPL, WIN_BLACKMAN, G, O>), gr, b, 0, stream, fa, g); break;
+      default:           hipLaunchKernelGGL((forward_mix_kernel<FD, BPL, WIN_BOXCAR, G, O>), gr, b, 0, stream, fa, g); break;
+    }
+  }
+#ifdef SDFT_HIP_TEST_HOOKS
+  template <int G> bool launch_forward_mix_g(const ForwardArgs<FD>& fa, const MixArgs<FD>& g, unsigned blocks)
+  {
+    switch (mix.block)
+    {
+      case 1: launch_forward_mix_go<G, 1>(fa, g, blocks); return true;
+      case 2: launch_forward_mix_go<G, 2>(fa, g, blocks); return true;
+      case 4: launch_forward_mix_go<G, 4>(fa, g, blocks); return true;
+      default: return false;
+    }
+  }
+#endif
+  // (the items of g were built for mix.block outputs per block: the kernel's O must be that; G is the kernel's alone)
+  bool launch_forward_mix(const ForwardArgs<FD>& fa, const MixArgs<FD>& g, unsigned blocks)
+  {
+    const int group = mix_group_size();
+    if (group == mix_group<FD>::value && mix.block == mix_block<FD>::value)
+    {
+      launch_forward_mix_go<mix_group<FD>::value, mix_block<FD>::value>(fa, g, blocks);
+      return true;
+    }
+#ifdef SDFT_HIP_TEST_HOOKS
+    switch (group)
+    {
+      case 2: if (launch_forward_mix_g<2>(fa, g, blocks)) return true; break;
+      case 4: if (launch_forward_mix_g<4>(fa, g, blocks)) return true; break;
+      case 8: if (launch_forward_mix_g<8>(fa, g, blocks)) return true; break;
+      default: break;
+    }
+#endif
+    set_error("sdft_hip_sdft_mix_n", "no kernel for the mix's group and block size");
+    return false;
+  }
   // the rows of the windows a chunk boundary cuts, from their pieces in the workspace (chunks > 1); nch: the plan's channels, or the
   // pairs of a cross-spectrum or covariance call
   bool launch_power_sum_rows(const PowerSumArgs<FD>& g, size_t n, long chunks, long len, long shift, size_t nch)

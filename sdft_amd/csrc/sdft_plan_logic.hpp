@@ -409,6 +409,52 @@ inline long covariance_item_out(size_t nch, const CovItem& it, size_t sa, size_t
 // pairs: [pairs][chunks][2][nbins_out] complex, slot cross_sum_slot(p, ...)
 inline size_t covariance_workspace(size_t nch, size_t chunks, size_t nbins_out) { return cross_sum_workspace(covariance_pairs(nch), chunks, nbins_out); }
 
+// ---- channel-mix analysis (sdft_hip_sdft_mix_n) --------------------------------------------------------------------------------------
+// A mix is an ordered list of nch distinct channels of the plan, as an array is, and nout weight tables [nch][dftsize] (sdft_hip_set_mix);
+// output o of the call is, per row of an every-grid and per bin, the sum over the elements i of W[o][i][k] * X_chan[i][k].  A wave of
+// forward_mix_kernel takes a BLOCK of up to O consecutive outputs and all the elements of the mix, group by group, so the items are
+// the ceil(nout / O) blocks and, after them, one advance-only item per plan channel that is not in the mix.  The block of output 0
+// is the one item that writes the state of the mix's channels back: every channel of the plan has exactly one writer.
+enum MixCheck : int { MX_OK = 0, MX_CHANNEL = 1, MX_REPEAT = 2, MX_TOO_MANY = 3, MX_NO_WEIGHTS = 4, MX_NO_CHANNELS = 5, MX_TOO_MANY_OUTPUTS = 6 };
+constexpr size_t kMixMaxOutputs = 65535;                      // an item counts its outputs in 16 bits
+// a mix sdft_hip_set_mix may install (nout == 0 removes the mix, whatever the other arguments; chan == nullptr: the channels 0 ... nch - 1)
+inline int mix_check(size_t channels, size_t nout, size_t nch, const size_t* chan, bool has_weights)
+{
+  if (nout == 0) return MX_OK;
+  if (nout > kMixMaxOutputs) return MX_TOO_MANY_OUTPUTS;
+  if (!has_weights) return MX_NO_WEIGHTS;
+  if (nch == 0) return MX_NO_CHANNELS;
+  switch (array_check(channels, nch, chan))
+  {
+    case AR_OK: return MX_OK;
+    case AR_CHANNEL: return MX_CHANNEL;
+    case AR_REPEAT: return MX_REPEAT;
+    default: return MX_TOO_MANY;
+  }
+}
+struct MixItem
+{
+  unsigned o0;                            // a block: its first output; an advance-only item: the PLAN channel
+  unsigned short no, writes;              // no: outputs of the block (1 ... O; advance-only: 0); writes: stores state on the last chunk
+};
+// (of a mix mix_check has passed, nout > 0)
+inline std::vector<MixItem> mix_items(size_t channels, size_t nch, const size_t* chan, size_t nout, int O)
+{
+  const size_t ch = std::max<size_t>(channels, 1), o = (size_t)std::max(O, 1), blocks = (nout + o - 1) / o;
+  std::vector<MixItem> items;
+  std::vector<char> in_mix(ch, 0);
+  for (size_t i = 0; i < nch; ++i) in_mix[chan ? chan[i] : i] = 1;
+  items.reserve(blocks + ch);
+  for (size_t b = 0; b < blocks; ++b)
+    items.push_back(MixItem{(unsigned)(b * o), (unsigned short)std::min(o, nout - b * o), (unsigned short)(b == 0 ? 1 : 0)});
+  for (size_t c = 0; c < ch; ++c)
+    if (!in_mix[c]) items.push_back(MixItem{(unsigned)c, 0, 1});
+  return items;
+}
+// numbers (not complex numbers) from one output's first bin to the next output's, and the weight of (output, element, bin)
+inline size_t mix_output_stride(size_t rows, size_t nbins_out) { return power_channel_stride(rows, 2 * nbins_out); }
+inline size_t mix_weight_index(size_t nch, size_t nbins, size_t o, size_t i, size_t k) { return (o * nch + i) * nbins + k; }
+
 // ---- filterbank analysis (sdft_hip_sdft_filterbank_n) --------------------------------------------------------------------------
 // Band b of a filterbank covers the bins [band_bin0[b], band_bin0[b] + band_nbins[b]) with one weight per bin; row r of the output
 // holds, per band, the sum of fl(weight * power) over the band's bins, the powers those sdft_hip_sdft_power_n stores for the row.
@@ -880,6 +926,7 @@ struct ForwardQuery
   bool cross_sum = false;                 // pooled cross-spectrum analysis (forward_cross_sum_kernel) of ...
   size_t cross_items = 0;                 // ... this many work items (logic::cross_items), which take the channels' place in the launch
   bool covariance = false;                // array covariance analysis (forward_covariance_kernel): cross_items counts its block items (logic::covariance_items)
+  bool mix = false;                       // channel-mix analysis (forward_mix_kernel) on the grid of power_every: cross_items counts its items (logic::mix_items)
   bool row_pointers = false;              // rows go to a table of row pointers
   uintptr_t out = 0; size_t out_stride = 0;
   bool analysis_batch = false;            // CallPattern: analyses come call after call
@@ -890,7 +937,7 @@ struct ForwardQuery
        chain_L = 0, relay_flow = 1, segments = 0, xcd_map = 1, rows_f32 = 1, pipeline = 1;
   long prefix_cells = 1;                  // test hook: 0 = never the prefix-cell route, 1 = calls beyond kSelfMax, 2 = whatever the length
 };
-enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6, FK_FILTERBANK = 7, FK_CROSS_SUM = 8, FK_COVARIANCE = 9 };     // = get_option "last_kernel"
+enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6, FK_FILTERBANK = 7, FK_CROSS_SUM = 8, FK_COVARIANCE = 9, FK_MIX = 10 };     // = get_option "last_kernel"
 // carries: the single chunk's are the stream state (delta_kernel copies it); pre-pass partial sums + scan (carries from the
 // closed-form table); the serial exact pass (carry_exact_kernel); the relay form of the exact pass (carry_relay_kernel)
 enum CarryForm : int { CARRY_STATE = 0, CARRY_SUMS = 1, CARRY_SERIAL = 2, CARRY_RELAY = 3 };
@@ -938,10 +985,10 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   ForwardRoute r;
   const size_t nb = q.nbins, span = 2 * nb, n = q.n, ch = std::max<size_t>(q.channels, 1);
   const bool pow2 = (span & (span - 1)) == 0;
-  // the decimated, the power-spectrogram, the pooled power, the filterbank, the cross-spectrum and the covariance analysis have the tile form only
-  const bool grid = q.every || q.power || q.power_sum || q.filterbank || q.cross_sum || q.covariance;
-  // (channel, chunk) groups of a tile launch per chunk: the cross-spectrum and the covariance call's are their work items
-  const size_t lanes = (q.cross_sum || q.covariance) ? std::max<size_t>(q.cross_items, 1) : ch;
+  // the decimated, the power-spectrogram, the pooled power, the filterbank, the cross-spectrum, the covariance and the mix analysis have the tile form only
+  const bool grid = q.every || q.power || q.power_sum || q.filterbank || q.cross_sum || q.covariance || q.mix;
+  // (channel, chunk) groups of a tile launch per chunk: the cross-spectrum, the covariance and the mix call's are their work items
+  const size_t lanes = (q.cross_sum || q.covariance || q.mix) ? std::max<size_t>(q.cross_items, 1) : ch;
   const bool rows = !grid && rows_kernel_ok(nb, q.fdx_bytes, q.row_pointers, q.rows_kernel != 0, q.row_slots_max);
   const bool folded = q.fuse && !q.reference_order && !q.fuse_store && q.fold && q.coeff_ready;
   // pipelined calls (forward_self): decided first because they take the self-carried form at any length and cut time differently
@@ -967,12 +1014,12 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   {
     EveryQuery e;
     e.n = n; e.channels = lanes; e.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); e.exact = q.exact; e.forced_chunk = q.chunk; e.compute_units = q.compute_units;
-    c = (q.power_sum || q.cross_sum || q.covariance) ? choose_power_sum_chunks(e) : (q.power || q.filterbank) ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
+    c = (q.power_sum || q.cross_sum || q.covariance) ? choose_power_sum_chunks(e) : (q.power || q.filterbank || q.mix) ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
   }
   else c = choose_chunks(chunk_query(q, rows, r.pipelined));
   r.chunks = c.chunks; r.len = c.len;
   r.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); r.interior = interior_lanes(q.window, q.fdx_bytes, q.interior);
-  r.kernel = q.covariance ? FK_COVARIANCE : q.cross_sum ? FK_CROSS_SUM : q.filterbank ? FK_FILTERBANK : q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
+  r.kernel = q.mix ? FK_MIX : q.covariance ? FK_COVARIANCE : q.cross_sum ? FK_CROSS_SUM : q.filterbank ? FK_FILTERBANK : q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
   if (r.chunks == 1 && q.hop_kernel && nb >= 2 && !q.fuse && !grid) { r.kernel = FK_HOP; return r; }
 
   // self-carried chunks: every workgroup derives its carry-in from the raw samples (fold + one FFT in LDS) and forms

@@ -47,6 +47,7 @@ class SDFT:
         self._stream = None
         self._pairs = None                                   # the pair list of set_pairs, likewise
         self._array = None                                   # the array of set_array, likewise
+        self._mix = None                                     # the (weights, chan) of set_mix, likewise
         self.combo = combo
         self.td = _NP_REAL[combo[:3]]
         self.fd = _NP_REAL[combo[3:]]
@@ -121,6 +122,8 @@ class SDFT:
                     self.set_pairs(*self._pairs)
                 if self._array is not None:                      # (and the installed array)
                     self.set_array(self._array)
+                if self._mix is not None:                        # (and the installed mix)
+                    self.set_mix(*self._mix)
                 self._options.append((key, int(value)))
                 return
             if q:
@@ -489,6 +492,91 @@ class SDFT:
         assert got == rows, (got, rows)
         return out
 
+    def set_mix(self, weights, chan=None):
+        """Installs a mix in the plan (``sdft_hip_set_mix``; list and weights are copied).  ``weights`` is a complex array of shape
+        (nout, nch, dftsize) (or (nch, dftsize) for one output), applied as written: ``out[o] = sum_i weights[o, i] * X_chan[i]`` per
+        bin, so a host that wants ``w^H x`` passes conjugates (:func:`mvdr_weights` does).  ``chan`` is an ordered list of ``nch``
+        distinct channels, None for the channels ``0 ... nch - 1``.  ``weights=None`` removes the mix.  Independent of
+        :meth:`set_pairs`, :meth:`set_array` and the filterbank."""
+        self.api.clear()
+        if weights is None:
+            rc = self.api.set_mix(self._p, 0, 0, C.c_void_p(None), C.c_void_p(None))
+            if rc != 0:
+                self.api.check()
+                raise SdftHipError("sdft_hip_set_mix failed")
+            self.api.check()
+            self._mix = None
+            return
+        w = weights.detach().cpu().numpy() if _is_tensor(weights) else np.asarray(weights)
+        if w.ndim == 2:
+            w = w[None]
+        if w.ndim != 3 or w.shape[2] != self.dftsize or w.shape[0] == 0:
+            raise ValueError(f"weights must be (nout, nch, {self.dftsize}) with nout >= 1, got {w.shape}")
+        w = np.ascontiguousarray(w, dtype=self.fdx)
+        nout, nch = int(w.shape[0]), int(w.shape[1])
+        ch = None
+        if chan is not None:
+            try:
+                ch = np.ascontiguousarray(chan, dtype=np.uint64).ravel()
+            except OverflowError as e:
+                raise ValueError(f"channel indices must not be negative: {e}") from None
+            if ch.size != nch:
+                raise ValueError(f"chan names {ch.size} channels but weights has {nch}")
+        rc = self.api.set_mix(self._p, nout, nch, C.c_void_p(ch.ctypes.data if ch is not None and ch.size else None), C.c_void_p(w.ctypes.data if w.size else None))
+        if rc != 0:
+            self.api.check()
+            raise SdftHipError("sdft_hip_set_mix failed")
+        self.api.check()
+        self._mix = (w, ch)
+
+    @property
+    def mix_outputs(self) -> int:
+        """Outputs of the installed mix (``sdft_hip_mix_outputs``), 0 for none."""
+        return int(self.api.mix_outputs(self._p))
+
+    def mix(self, x, every: int = 1, first: int = 0, bins=None, out=None):
+        """Channel-mix analysis (``sdft_hip_sdft_mix_n``): the per-bin weighted sums of the installed mix (:meth:`set_mix`) at the rows
+        of :meth:`sdft_every`'s grid, for the bins ``bins = (bin0, nbins)`` (default: all) -> complex array of shape (nout, rows, nbins).
+        Each value is the sequential sum over the mix's elements of ``w * X`` formed from four rounded products, in the FD type.  The
+        stream state of every channel afterwards is the one :meth:`sdft` leaves; ``every_next_first`` gives the next call's
+        ``first``."""
+        self.api.clear()
+        every, first = int(every), int(first)
+        bin0, nb = (0, self.dftsize) if bins is None else (int(bins[0]), int(bins[1]))
+        if every < 1 or first < 0:
+            raise ValueError(f"every must be >= 1 and first >= 0, got every={every}, first={first}")
+        if bin0 < 0 or nb < 1 or bin0 + nb > self.dftsize:
+            raise ValueError(f"bins = (bin0, nbins) must select at least one of the {self.dftsize} bins, got {(bin0, nb)}")
+        nout = self.mix_outputs
+        if nout == 0:
+            raise ValueError("no mix is installed: call set_mix first")
+        cdtype = np.dtype(self.fdx)
+        if _is_tensor(x):
+            torch = _torch()
+            n = self._shape_x(x.shape)
+            self._check_tensor(x, "samples", self.td)
+            rows = every_rows(n, every, first)
+            shape = (nout, rows, nb)
+            if out is None:
+                out = torch.empty(shape, dtype=getattr(torch, cdtype.name), device=x.device)
+            self._check_tensor(out, "out", cdtype, shape)
+            got = self.api.sdft_mix_n(self._p, n, C.c_void_p(x.data_ptr()), every, first, bin0, nb, C.c_void_p(out.data_ptr() if rows else None))
+        else:
+            x = np.ascontiguousarray(x, dtype=self.td)
+            n = self._shape_x(x.shape)
+            rows = every_rows(n, every, first)
+            shape = (nout, rows, nb)
+            if out is None:
+                out = np.empty(shape, dtype=cdtype)
+            assert out.flags.c_contiguous and out.shape == shape and out.dtype == cdtype
+            got = self.api.sdft_mix_n(self._p, n, C.c_void_p(x.ctypes.data), every, first, bin0, nb, C.c_void_p(out.ctypes.data if rows else None))
+        if got < 0:
+            self.api.check()
+            raise SdftHipError("sdft_hip_sdft_mix_n failed")
+        self.api.check()
+        assert got == rows, (got, rows)
+        return out
+
     def power_sum(self, x, every: int = 1, first: int = 0, bins=None, out=None):
         """Pooled power analysis (``sdft_hip_sdft_power_sum_n``): the grid points ``first``, ``first + every``, ... cut the n samples
         into windows, and row r is the sum of :meth:`power`'s ``every = 1`` values over the r-th window, for the bins
@@ -674,6 +762,33 @@ def covariance_matrix(cov, nch: int):
     m[:, :, b, a] = np.conj(np.moveaxis(c, 0, -1))
     m[:, :, a, b] = np.moveaxis(c, 0, -1)                        # (the diagonal last: as returned, im == +0)
     return m
+
+
+def mvdr_weights(mat, steering, loading: float = 0.0):
+    """MVDR weights per bin from :func:`covariance_matrix`'s output, shaped for :meth:`SDFT.set_mix` (numpy, on the host).
+    ``mat`` is (rows, nbins, nch, nch), or one row of it (nbins, nch, nch); a stack of rows is summed first.  ``steering`` is the
+    steering vector d per bin, (nbins, nch) or (nch,) for all bins.  ``loading`` adds ``loading * trace(R) / nch`` to R's diagonal.
+    Returns ``conj(R^-1 d / (d^H R^-1 d))`` of shape (1, nch, nbins), so that :meth:`SDFT.mix` yields ``w^H x`` with ``w^H d = 1``."""
+    r = np.asarray(mat)
+    if r.ndim == 4:
+        r = r.sum(axis=0)
+    if r.ndim != 3 or r.shape[1] != r.shape[2]:
+        raise ValueError(f"mat must be (rows, nbins, nch, nch) or (nbins, nch, nch), got {np.asarray(mat).shape}")
+    nbins, nch = r.shape[0], r.shape[1]
+    d = np.asarray(steering)
+    if d.ndim == 1:
+        d = np.broadcast_to(d, (nbins, d.shape[0]))
+    if d.shape != (nbins, nch):
+        raise ValueError(f"steering must be ({nbins}, {nch}) or ({nch},), got {np.asarray(steering).shape}")
+    cdtype = np.result_type(r.dtype, np.complex64)
+    r = r.astype(cdtype)
+    d = d.astype(cdtype)
+    if loading:
+        r = r + (float(loading) * np.trace(r, axis1=1, axis2=2).real / nch)[:, None, None] * np.eye(nch, dtype=cdtype)
+    rid = np.linalg.solve(r, d[:, :, None])[:, :, 0]                     # R^-1 d per bin
+    den = np.einsum("kc,kc->k", np.conj(d), rid)                          # d^H R^-1 d
+    w = rid / den[:, None]
+    return np.ascontiguousarray(np.conj(w).T[None])
 
 
 def every_next_first(n: int, every: int, first: int) -> int:
