@@ -37,6 +37,8 @@ const char* sdft_hip_last_error(void);
                                    std::size_t bin0, std::size_t nbins, void* power);                                    \
   long sdft_hip_sdft_power_sum_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, \
                                        std::size_t bin0, std::size_t nbins, void* sums);                               \
+  long sdft_hip_sdft_power_peak_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, \
+                                        std::size_t bin0, std::size_t nbins, int hold, void* peaks);                   \
   int sdft_hip_set_filterbank_##SUF(void* plan, std::size_t nbands, const std::size_t* band_bin0, const std::size_t* band_nbins, \
                                     const void* weights);                                                               \
   std::size_t sdft_hip_filterbank_bands_##SUF(const void* plan);                                                       \
@@ -71,6 +73,13 @@ namespace sdft
     Blackman
   };
 
+  /** The statistic of SDFT::power_peak(): the largest or the smallest power of a window (enum sdft_hip_hold). */
+  enum class Hold
+  {
+    Max = 0,
+    Min = 1
+  };
+
   namespace detail
   {
     template <typename T, typename F> struct abi;   // undefined for unsupported type pairs
@@ -89,6 +98,7 @@ namespace sdft
       static long sdft_every_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, void* d) { return sdft_hip_sdft_every_n_##SUF(p, n, x, e, f, d); } \
       static long sdft_power_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_power_n_##SUF(p, n, x, e, f, b, k, d); } \
       static long sdft_power_sum_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_power_sum_n_##SUF(p, n, x, e, f, b, k, d); } \
+      static long sdft_power_peak_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, int h, void* d) { return sdft_hip_sdft_power_peak_n_##SUF(p, n, x, e, f, b, k, h, d); } \
       static int set_filterbank(void* p, std::size_t nb, const std::size_t* b0, const std::size_t* bn, const void* w) { return sdft_hip_set_filterbank_##SUF(p, nb, b0, bn, w); } \
       static std::size_t filterbank_bands(const void* p) { return sdft_hip_filterbank_bands_##SUF(p); } \
       static long sdft_filterbank_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, void* d) { return sdft_hip_sdft_filterbank_n_##SUF(p, n, x, e, f, d); } \
@@ -219,6 +229,25 @@ namespace sdft
       {
         const char* e = sdft_hip_last_error();
         throw std::runtime_error(std::string("sdft_hip_sdft_power_sum_n: ") + (e ? e : "failed"));
+      }
+      return static_cast<std::size_t>(rows);
+    }
+
+    /**
+     * Peak-hold analysis (sdft_hip_sdft_power_peak_n): power_sum()'s grid, windows, head row and layout; row r of out, dense
+     * (rows, nbins), is the largest (Hold::Max) or the smallest (Hold::Min) of power()'s every == 1 values over the r-th window
+     * for the bins bin0 <= k < bin0 + nbins, bit for bit one of them (NaN if the window holds a NaN).  first > 0 makes row 0 the
+     * head window [0, first), which completes the previous call's last row (take the larger / smaller of the two); the next
+     * call's first is sdft_every()'s.  The plan's state advances over all samples and all bins.  Returns the number of rows written.
+     **/
+    std::size_t power_peak(const std::size_t nsamples, const T* samples, const std::size_t every, const std::size_t first,
+                           const std::size_t bin0, const std::size_t nbins, const Hold hold, F* const out)
+    {
+      const long rows = api::sdft_power_peak_n(plan_, nsamples, samples, every, first, bin0, nbins, static_cast<int>(hold), out);
+      if (rows < 0)
+      {
+        const char* e = sdft_hip_last_error();
+        throw std::runtime_error(std::string("sdft_hip_sdft_power_peak_n: ") + (e ? e : "failed"));
       }
       return static_cast<std::size_t>(rows);
     }

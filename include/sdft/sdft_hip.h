@@ -221,6 +221,40 @@ long sdft_hip_sdft_power_sum_n(sdft_t* sdft, const sdft_size_t nsamples, const s
                                const sdft_size_t bin0, const sdft_size_t nbins,
                                sdft_fd_t* sums) SDFT_HIP_SYMBOL(sdft_power_sum_n);
 
+/* ---- peak-hold analysis ----------------------------------------------------------------------------
+   sdft_hip_sdft_power_peak_n holds the largest (hold = sdft_hip_hold_max: the peak spectrum of a spectrum analyser, crest factor
+   against the mean) or the smallest (hold = sdft_hip_hold_min: the noise-floor tracker of minimum statistics) |X|^2 over windows
+   of rows.  Grid, windows, head row, rows = (first > 0 && nsamples > 0 ? 1 : 0) + (rows of sdft_hip_sdft_every_n), the next
+   call's first, the band, every > nsamples, host or device pointers (option "async" applies to device pointers) and the layout
+   -- peaks is [rows][nbins], dense, aligned to sizeof(sdft_fd_t) only; batched plans: samples [channels][nsamples], peaks
+   [channels][rows][nbins] -- are sdft_hip_sdft_power_sum_n's, unchanged.  Row r holds, for bin0 <= k < bin0 + nbins, the extreme
+   over the r-th window of p[t][k], the value sdft_hip_sdft_power_n stores at every == 1, first == 0 (in sdft_fd_t: two rounded
+   products, one rounded sum, no fused multiply-add).  One rule combines a held value m with a term p, in the kernels and for
+   the host:
+     max:  m = (p > m || p != p) ? p : m          min:  m = (p < m || p != p) ? p : m
+   A window that holds a NaN term gives NaN (payload unspecified); otherwise the result is exactly one of the window's terms.
+   Powers are +0 or larger, so signed zeros do not occur.  Every window has a sample, so the accumulators' start (-inf for max,
+   +inf for min) never reaches the output.  With first > 0, row 0 completes the previous call's last row: the host combines the
+   two by the same rule (fmax / fmin of finite values).
+   Promised: (1) The same plan, options and input give the same bits on every run.  (2) every == 1 with first == 0 gives
+   sdft_hip_sdft_power_n's values bit for bit, for either hold.  (3) Wherever sdft_sdft_n is bit-identical to the reference (FD
+   float, FD double with option "carry" = 1, calls shorter than 512 samples) the value is the largest / smallest of the
+   reference's powers over the window, bit for bit, for any every, first, band, cut of time into chunks, host staging and cut of a
+   stream into calls: max and min are associative and commutative, so no order of combination shows.  (4) On the other routes
+   the value is bit for bit the extreme of what sdft_hip_sdft_power_n stores at every == 1 when both calls cut time into chunks
+   of the same length ("last_chunk_len"), and within 2.1e-11 of the call's largest power of the reference's extreme
+   (sdft_hip_sdft_power_n's term deviation, with no factor for the window's length: |max a - max b| <= max |a - b|).  (5) The
+   stream state afterwards is the one sdft_sdft_n of the same samples leaves -- bins outside the band step every sample too --
+   so any other entry point may follow.
+   The call is never resident, pipelined or fused and always runs its own kernel ("last_kernel" = 11).  Returns the number of
+   rows written (0 only for nsamples == 0), or -1 with sdft_hip_last_error() set and the stream state untouched: a NULL plan,
+   every == 0, nbins == 0, bin0 + nbins > dftsize, hold neither 0 nor 1, or peaks == NULL with rows > 0. */
+enum sdft_hip_hold { sdft_hip_hold_max = 0, sdft_hip_hold_min = 1 };
+long sdft_hip_sdft_power_peak_n(sdft_t* sdft, const sdft_size_t nsamples, const sdft_td_t* samples,
+                                const sdft_size_t every, const sdft_size_t first,
+                                const sdft_size_t bin0, const sdft_size_t nbins,
+                                const int hold, sdft_fd_t* peaks) SDFT_HIP_SYMBOL(sdft_power_peak_n);
+
 /* ---- filterbank analysis ---------------------------------------------------------------------------
    Pooling of |X|^2 over frequency: mel, Bark and fractional-octave band energies, or the total power of a row, without storing
    and re-reading the powers.  A filterbank belongs to the plan.  sdft_hip_set_filterbank installs (copies) one; all four pointers
@@ -512,7 +546,7 @@ double sdft_hip_time_hops(sdft_t* sdft, size_t hops, size_t hop, const sdft_td_t
    "relay_flow", "relay_groups", "chain_debug", "inverse_nt", "inverse_nt_skip_mb", "inverse_step", "inverse_ordered", "host_direct", "copy_streams", "prefix_cells", "array_group", "mix_group", "mix_block" (sdft_capi.inc names what each selects);
    get_option "test_hooks" = 1 in that build.
    get_option additionally answers "tiles", "bins_per_lane", "row_slots", "last_chunks",
-   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis, 6 pooled power analysis, 7 filterbank analysis, 8 pooled cross-spectrum analysis, 9 array covariance analysis, 10 channel-mix analysis), "last_segments", "last_fused",
+   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis, 6 pooled power analysis, 7 filterbank analysis, 8 pooled cross-spectrum analysis, 9 array covariance analysis, 10 channel-mix analysis, 11 peak-hold analysis), "last_segments", "last_fused",
    "last_filterbank_launches" (forward_filterbank_kernel launches of the last filterbank call, over all of its host segments: more than its carry segments once its pieces exceed the workspace bound),
    "last_chain", "last_fused_exact", "last_fused_fold", "last_process_path" (1 fused kernel, 2 hop pair, 3 two-pass),
    "last_self" (no pre-pass launch), "last_prefix" (long calls: one pre-pass launch, prefix_cells_kernel), "last_inverse_nt" / "last_inverse_skip" (what the last synthesis launch used: non-temporal loads, rows read with ordinary loads),

@@ -108,6 +108,15 @@ long SDFT_FN(sdft_power_sum_n)(void* p, size_t n, const SDFT_TD* x, size_t every
   if (rows > (size_t)LONG_MAX) { sdfthip::set_error("sdft_hip_sdft_power_sum_n", "more rows than a long can count"); return -1; }
   return (long)rows;
 }
+// peak-hold analysis: the largest or the smallest of those powers over the windows of the grid; see sdft_hip.h
+long SDFT_FN(sdft_power_peak_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, size_t bin0, size_t nbins, int hold, SDFT_FD* peaks)
+{
+  if (!p) { sdfthip::set_error("sdft_hip_sdft_power_peak_n", "NULL plan"); return -1; }
+  size_t rows = 0;
+  if (!P(p)->sdft_power_peak_n(n, x, every, first, bin0, nbins, hold, peaks, rows)) return -1;
+  if (rows > (size_t)LONG_MAX) { sdfthip::set_error("sdft_hip_sdft_power_peak_n", "more rows than a long can count"); return -1; }
+  return (long)rows;
+}
 // filterbank analysis: weighted band sums of those powers on the grid; see sdft_hip.h
 int SDFT_FN(set_filterbank)(void* p, size_t nbands, const size_t* band_bin0, const size_t* band_nbins, const SDFT_FD* weights)
 {

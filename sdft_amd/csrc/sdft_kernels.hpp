@@ -16,6 +16,9 @@
 //   sdft_forward_power_sum.hpp K1s forward_pooled_power_kernel: that power at every sample, summed in registers over the windows of the
 //                          grid, one store per window; pooled_power_rows_kernel adds the pieces of the windows a chunk boundary cuts
 //                          (sdft_hip_sdft_power_sum_n)
+//   sdft_forward_power_peak.hpp K1k forward_power_peak_kernel: the pooled power kernel with the other statistic -- the largest or the
+//                          smallest of those powers over each window, kept in registers by one rule (peak_hold); peak_rows_kernel
+//                          combines the pieces of the windows a chunk boundary cuts (sdft_hip_sdft_power_peak_n)
 //   sdft_forward_cross_sum.hpp K1x forward_cross_sum_kernel: the pooled power kernel with a second channel -- A conj(B) of the windowed
 //                          bins of two channels of a plan, summed in registers over the windows of the grid (sdft_hip_sdft_cross_sum_n)
 //   sdft_forward_covariance.hpp K1v forward_covariance_kernel: the cross-spectrum kernel with groups of channels in place of channels --
@@ -57,6 +60,7 @@
 #include "sdft_forward_every.hpp"
 #include "sdft_forward_power.hpp"
 #include "sdft_forward_power_sum.hpp"
+#include "sdft_forward_power_peak.hpp"
 #include "sdft_forward_cross_sum.hpp"
 #include "sdft_forward_covariance.hpp"
 #include "sdft_forward_mix.hpp"

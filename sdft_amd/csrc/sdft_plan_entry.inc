@@ -373,6 +373,86 @@
       return true;
     });
   }
+  // peak-hold analysis (sdft_hip_sdft_power_peak_n): the largest (hold 0) or the smallest (hold 1) of sdft_power_n's every == 1 powers
+  // over the windows of sdft_power_sum_n's grid; rows, head row, output, state, pointers, launches and host segments are that
+  // call's, with forward_power_peak_kernel, peak_rows_kernel and peak_join_kernel in its kernels' places.  The head row of a later
+  // segment is combined into the row the segment before it ended with by the one rule (logic::peak_hold), which is associative and
+  // commutative: how the segments cut a window does not show in the bits.
+  bool sdft_power_peak_n(size_t n, const TD* x, size_t every, size_t first, size_t bin0, size_t nbins_out, int hold, FD* peaks, size_t& rows)
+  {
+    static const char* fn = "sdft_hip_sdft_power_peak_n";
+    rows = 0;
+    if (every == 0) { set_error(fn, "every must be at least 1"); return false; }
+    if (nbins_out == 0) { set_error(fn, "nbins must be at least 1"); return false; }
+    if (!logic::power_band_ok(nbins, bin0, nbins_out)) { set_error(fn, "the band bin0 ... bin0 + nbins - 1 does not lie within the plan's bins"); return false; }
+    if (!logic::peak_hold_ok(hold)) { set_error(fn, "hold must be sdft_hip_hold_max (0) or sdft_hip_hold_min (1)"); return false; }
+    rows = logic::power_sum_rows(n, every, first);
+    if (rows > 0 && !peaks) { set_error(fn, "peaks is NULL but the call writes rows"); return false; }
+    if (n == 0) return true;
+    if (!bind()) return false;
+    if (!pipe_join()) return false;
+    if (every > n) every = n;                                // (the same windows; keeps first + k * every in range)
+    const bool xd = on_device(x);
+    const bool od = on_device(peaks);
+    const size_t row_bytes = channels * nbins_out * sizeof(FD);
+    auto band = [&](FD* row0, size_t row0_stride, FD* rest, size_t rest_stride, size_t f) {
+      return PowerSumArgs<FD>{row0, row0_stride, rest, rest_stride, nullptr, (unsigned long long)every, (unsigned long long)f, (unsigned)bin0, (unsigned)nbins_out};
+    };
+    const size_t stride = logic::power_channel_stride(rows, nbins_out);
+    if (xd && od)
+    {
+      const PowerSumArgs<FD> g = band(peaks, stride, peaks + nbins_out, stride, first);
+      return forward_device(n, x, n, nullptr, 0, nullptr, nullptr, nullptr, nullptr, &g, nullptr, nullptr, nullptr, nullptr, hold) && finish(rows * row_bytes);
+    }
+    // host memory: segments of at most seg samples (rows written and samples within stage_bytes); where the grid allows it, of
+    // whole windows, so that no row is made of two segments
+    size_t seg = n;
+    if (!od) seg = std::min(seg, logic::stage_rows(n, row_bytes, stage_bytes) * every);
+    if (!xd) seg = std::min(seg, std::max<size_t>((size_t)logic::kHopSamples, logic::stage_rows(n, channels * sizeof(TD), stage_bytes)));
+    if (seg < n && seg > every && first % every == 0) seg -= seg % every;
+    std::vector<FD> head;                                    // host buffers: a segment's head row on its way to the row it completes
+    return staged_segments(n, seg, StagedCall{true, const_cast<TD*>(x), !xd, peaks, !od, rows, (seg + every - 1) / every + 1, nbins_out * sizeof(FD)}, [&](Segment& s) {
+      const size_t f = logic::every_first_from(s.t, every, first);
+      const logic::PowerSumWindow w0 = logic::power_sum_window(s.t, n, every, first);      // of the segment's row 0 in the call
+      const bool joins = w0.begin < s.t;                     // row 0 is a head: it completes row w0.row of the call
+      const size_t seg_rows = logic::power_sum_rows(s.m, every, f), kept = seg_rows - (joins ? 1 : 0);
+      if (joins && !d_psum_head.reserve(channels * nbins_out)) return false;
+      s.row0 = w0.row + (joins ? 1 : 0); s.rows = kept;
+      PowerSumArgs<FD> g;
+      if (od)
+      {
+        FD* const at = peaks + s.row0 * nbins_out;           // the segment's first row of its own
+        s.mat = at;
+        g = joins ? band(d_psum_head.p, nbins_out, at, stride, f) : band(at, stride, at + nbins_out, stride, f);
+      }
+      else
+      {
+        FD* const at = static_cast<FD*>(s.mat);              // scratch, [channels][kept][nbins_out]
+        s.mat_rows = kept;
+        g = joins ? band(d_psum_head.p, nbins_out, at, kept * nbins_out, f) : band(at, kept * nbins_out, at + nbins_out, kept * nbins_out, f);
+      }
+      if (!forward_device(s.m, s.td, s.td_stride, nullptr, 0, nullptr, nullptr, nullptr, nullptr, &g, nullptr, nullptr, nullptr, nullptr, hold)) return false;
+      if (!joins) return true;
+      if (od)
+      {
+        const unsigned long long threads = (unsigned long long)channels * nbins_out;
+        hipLaunchKernelGGL((peak_join_kernel<FD>), dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
+                           peaks + w0.row * nbins_out, stride, d_psum_head.p, (unsigned)nbins_out, (unsigned)channels, hold);
+        SDFT_TRY(hipGetLastError());
+        return true;
+      }
+      head.resize(channels * nbins_out);
+      if (!to_host(head.data(), d_psum_head.p, head.size() * sizeof(FD))) return false;
+      SDFT_TRY(hipStreamSynchronize(stream));
+      for (size_t c = 0; c < channels; ++c)
+        for (size_t k = 0; k < nbins_out; ++k)
+        {
+          FD& held = peaks[c * stride + w0.row * nbins_out + k];
+          held = logic::peak_hold(held, head[c * nbins_out + k], hold);
+        }
+      return true;
+    });
+  }
   // ---- pooled cross-spectrum analysis ------------------------------------------------------------------------------------------
   // sdft_hip_set_pairs: the arrays are host memory and are copied; a refused list leaves the installed one as it is.  The work
   // items of the list (logic::cross_items) go to the device once, here.

@@ -333,6 +333,22 @@
       default:           hipLaunchKernelGGL((forward_pooled_power_kernel<FD, BPL, WIN_BOXCAR>), gr, b, 0, stream, fa, g); break;
     }
   }
+  template <int HOLD> void launch_forward_power_peak_h(const ForwardArgs<FD>& fa, const PowerSumArgs<FD>& g, unsigned blocks)
+  {
+    constexpr int BPL = sizeof(fdx) == 16 ? 1 : 2;
+    const dim3 gr(blocks), b(kBlock);
+    switch (window)
+    {
+      case WIN_HANN:     hipLaunchKernelGGL((forward_power_peak_kernel<FD, BPL, WIN_HANN, HOLD>), gr, b, 0, stream, fa, g); break;
+      case WIN_HAMMING:  hipLaunchKernelGGL((forward_power_peak_kernel<FD, BPL, WIN_HAMMING, HOLD>), gr, b, 0, stream, fa, g); break;
+      case WIN_BLACKMAN: hipLaunchKernelGGL((forward_power_peak_kernel<FD, BPL, WIN_BLACKMAN, HOLD>), gr, b, 0, stream, fa, g); break;
+      default:           hipLaunchKernelGGL((forward_power_peak_kernel<FD, BPL, WIN_BOXCAR, HOLD>), gr, b, 0, stream, fa, g); break;
+    }
+  }
+  void launch_forward_power_peak(const ForwardArgs<FD>& fa, const PowerSumArgs<FD>& g, unsigned blocks, int hold)
+  {
+    if (hold == logic::kHoldMin) launch_forward_power_peak_h<logic::kHoldMin>(fa, g, blocks); else launch_forward_power_peak_h<logic::kHoldMax>(fa, g, blocks);
+  }
   void launch_forward_filterbank(const ForwardArgs<FD>& fa, const FilterbankArgs<FD>& g, unsigned blocks)
   {
     constexpr int BPL = sizeof(fdx) == 16 ? 1 : 2;
@@ -471,6 +487,15 @@
     const unsigned long long blocks = (threads + kBlock - 1) / kBlock;
     if (!grid_fits(blocks)) return false;
     hipLaunchKernelGGL((pooled_power_rows_kernel<FD>), dim3((unsigned)blocks), dim3(kBlock), 0, stream, g, n, (unsigned)chunks, (unsigned)len, (unsigned)shift, (unsigned)nch);
+    return true;
+  }
+  // likewise for the peak-hold call: the pieces combined by its rule
+  bool launch_peak_rows(const PowerSumArgs<FD>& g, size_t n, long chunks, long len, long shift, size_t nch, int hold)
+  {
+    const unsigned long long threads = (unsigned long long)nch * (unsigned long long)(chunks - 1) * g.nbins_out;
+    const unsigned long long blocks = (threads + kBlock - 1) / kBlock;
+    if (!grid_fits(blocks)) return false;
+    hipLaunchKernelGGL((peak_rows_kernel<FD>), dim3((unsigned)blocks), dim3(kBlock), 0, stream, g, n, (unsigned)chunks, (unsigned)len, (unsigned)shift, (unsigned)nch, hold);
     return true;
   }
 

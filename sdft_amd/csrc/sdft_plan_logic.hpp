@@ -297,6 +297,20 @@ inline PowerSumRowChunks power_sum_row_chunks(const PowerSumWindow& w, long len,
 // bin for pooled_power_rows_kernel) 1.495 against 1.712 / 1.577 / 1.556 / 1.637 / 1.845 / 2.343 ms (profiles/power_sum_rates.txt).
 inline Chunking choose_power_sum_chunks(const EveryQuery& q) { return choose_power_chunks(q, 1); }
 
+// ---- peak-hold analysis (sdft_hip_sdft_power_peak_n) ---------------------------------------------------------------------------
+// The pooled power call's grid, windows, head row, chunks, pieces and workspace with the other statistic: row r is the largest
+// (hold 0) or the smallest (hold 1) of the window's powers.  One rule combines a held value m with a term p, in the kernel
+// (forward_power_peak_kernel), the cut-window pass (peak_rows_kernel), the segment join (peak_join_kernel, or this function on a
+// host buffer) and a host that joins the head row of a call to the last row of the call before it.  A NaN term takes the place
+// of whatever is held and nothing replaces it, so a window with a NaN term gives NaN; without one the result is one of the terms.
+// Every window and every piece of one has a sample: accumulators start at -inf (max) or +inf (min), which the first term replaces.
+constexpr int kHoldMax = 0, kHoldMin = 1;                    // enum sdft_hip_hold
+inline bool peak_hold_ok(int hold) { return hold == kHoldMax || hold == kHoldMin; }
+template <typename T> inline T peak_hold(T m, T p, int hold)
+{
+  return hold == kHoldMin ? ((p < m || p != p) ? p : m) : ((p > m || p != p) ? p : m);
+}
+
 // ---- pooled cross-spectrum analysis (sdft_hip_sdft_cross_sum_n) ------------------------------------------------------------------
 // Row r of pair p = (a, b) is the sum over the r-th window of the pooled power call's grid of A conj(B), A and B the windowed bins
 // of the channels a and b.  A wave of forward_cross_sum_kernel steps the recurrences of the two channels of ONE work item, so the
@@ -922,6 +936,7 @@ struct ForwardQuery
   bool power = false;                     // power-spectrogram analysis (forward_power_kernel) on a grid of ...
   size_t power_every = 1;                 // ... every power_every-th sample
   bool power_sum = false;                 // pooled power analysis (forward_pooled_power_kernel)
+  bool power_peak = false;                // peak-hold analysis (forward_power_peak_kernel): the pooled power call's route (never with power_sum)
   bool filterbank = false;                // filterbank analysis (forward_filterbank_kernel) on the grid of power_every
   bool cross_sum = false;                 // pooled cross-spectrum analysis (forward_cross_sum_kernel) of ...
   size_t cross_items = 0;                 // ... this many work items (logic::cross_items), which take the channels' place in the launch
@@ -937,7 +952,7 @@ struct ForwardQuery
        chain_L = 0, relay_flow = 1, segments = 0, xcd_map = 1, rows_f32 = 1, pipeline = 1;
   long prefix_cells = 1;                  // test hook: 0 = never the prefix-cell route, 1 = calls beyond kSelfMax, 2 = whatever the length
 };
-enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6, FK_FILTERBANK = 7, FK_CROSS_SUM = 8, FK_COVARIANCE = 9, FK_MIX = 10 };     // = get_option "last_kernel"
+enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6, FK_FILTERBANK = 7, FK_CROSS_SUM = 8, FK_COVARIANCE = 9, FK_MIX = 10, FK_POWER_PEAK = 11 };     // = get_option "last_kernel"
 // carries: the single chunk's are the stream state (delta_kernel copies it); pre-pass partial sums + scan (carries from the
 // closed-form table); the serial exact pass (carry_exact_kernel); the relay form of the exact pass (carry_relay_kernel)
 enum CarryForm : int { CARRY_STATE = 0, CARRY_SUMS = 1, CARRY_SERIAL = 2, CARRY_RELAY = 3 };
@@ -985,8 +1000,8 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   ForwardRoute r;
   const size_t nb = q.nbins, span = 2 * nb, n = q.n, ch = std::max<size_t>(q.channels, 1);
   const bool pow2 = (span & (span - 1)) == 0;
-  // the decimated, the power-spectrogram, the pooled power, the filterbank, the cross-spectrum, the covariance and the mix analysis have the tile form only
-  const bool grid = q.every || q.power || q.power_sum || q.filterbank || q.cross_sum || q.covariance || q.mix;
+  // the decimated, the power-spectrogram, the pooled power, the peak-hold, the filterbank, the cross-spectrum, the covariance and the mix analysis have the tile form only
+  const bool grid = q.every || q.power || q.power_sum || q.power_peak || q.filterbank || q.cross_sum || q.covariance || q.mix;
   // (channel, chunk) groups of a tile launch per chunk: the cross-spectrum, the covariance and the mix call's are their work items
   const size_t lanes = (q.cross_sum || q.covariance || q.mix) ? std::max<size_t>(q.cross_items, 1) : ch;
   const bool rows = !grid && rows_kernel_ok(nb, q.fdx_bytes, q.row_pointers, q.rows_kernel != 0, q.row_slots_max);
@@ -1014,12 +1029,12 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   {
     EveryQuery e;
     e.n = n; e.channels = lanes; e.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); e.exact = q.exact; e.forced_chunk = q.chunk; e.compute_units = q.compute_units;
-    c = (q.power_sum || q.cross_sum || q.covariance) ? choose_power_sum_chunks(e) : (q.power || q.filterbank || q.mix) ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
+    c = (q.power_sum || q.power_peak || q.cross_sum || q.covariance) ? choose_power_sum_chunks(e) : (q.power || q.filterbank || q.mix) ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
   }
   else c = choose_chunks(chunk_query(q, rows, r.pipelined));
   r.chunks = c.chunks; r.len = c.len;
   r.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); r.interior = interior_lanes(q.window, q.fdx_bytes, q.interior);
-  r.kernel = q.mix ? FK_MIX : q.covariance ? FK_COVARIANCE : q.cross_sum ? FK_CROSS_SUM : q.filterbank ? FK_FILTERBANK : q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
+  r.kernel = q.mix ? FK_MIX : q.covariance ? FK_COVARIANCE : q.cross_sum ? FK_CROSS_SUM : q.filterbank ? FK_FILTERBANK : q.power_peak ? FK_POWER_PEAK : q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
   if (r.chunks == 1 && q.hop_kernel && nb >= 2 && !q.fuse && !grid) { r.kernel = FK_HOP; return r; }
 
   // self-carried chunks: every workgroup derives its carry-in from the raw samples (fold + one FFT in LDS) and forms

@@ -618,6 +618,49 @@ class SDFT:
         assert got == rows, (got, rows)
         return out
 
+    def power_peak(self, x, every: int = 1, first: int = 0, bins=None, hold="max", out=None):
+        """Peak-hold analysis (``sdft_hip_sdft_power_peak_n``): :meth:`power_sum`'s grid, windows, head row, shapes and pointers,
+        with the other statistic: row r is the largest (``hold="max"`` or 0) or the smallest (``hold="min"`` or 1) of
+        :meth:`power`'s ``every = 1`` values over the r-th window, bit for bit one of them (NaN if the window holds a NaN).  With
+        ``first > 0`` row 0 is the head window ``[0, first)``: it completes the previous call's last row (``np.maximum`` /
+        ``np.minimum`` of the two); the next call's ``first`` is :func:`every_next_first`.  The plan's state advances over all n
+        samples and all bins, as with :meth:`sdft`."""
+        self.api.clear()
+        every, first = int(every), int(first)
+        bin0, nb = (0, self.dftsize) if bins is None else (int(bins[0]), int(bins[1]))
+        if every < 1 or first < 0:
+            raise ValueError(f"every must be >= 1 and first >= 0, got every={every}, first={first}")
+        if bin0 < 0 or nb < 1 or bin0 + nb > self.dftsize:
+            raise ValueError(f"bins = (bin0, nbins) must select at least one of the {self.dftsize} bins, got {(bin0, nb)}")
+        if hold not in HOLDS:
+            raise ValueError(f"hold must be 'max' (0) or 'min' (1), got {hold!r}")
+        hold = HOLDS[hold]
+        if _is_tensor(x):
+            torch = _torch()
+            n = self._shape_x(x.shape)
+            self._check_tensor(x, "samples", self.td)
+            rows = power_sum_rows(n, every, first)
+            shape = (rows, nb) if x.dim() == 1 else (self.channels, rows, nb)
+            if out is None:
+                out = torch.empty(shape, dtype=getattr(torch, np.dtype(self.fd).name), device=x.device)
+            self._check_tensor(out, "out", self.fd, shape)
+            got = self.api.sdft_power_peak_n(self._p, n, C.c_void_p(x.data_ptr()), every, first, bin0, nb, hold, C.c_void_p(out.data_ptr() if rows else None))
+        else:
+            x = np.ascontiguousarray(x, dtype=self.td)
+            n = self._shape_x(x.shape)
+            rows = power_sum_rows(n, every, first)
+            shape = (rows, nb) if x.ndim == 1 else (self.channels, rows, nb)
+            if out is None:
+                out = np.empty(shape, dtype=self.fd)
+            assert out.flags.c_contiguous and out.shape == shape and out.dtype == self.fd
+            got = self.api.sdft_power_peak_n(self._p, n, C.c_void_p(x.ctypes.data), every, first, bin0, nb, hold, C.c_void_p(out.ctypes.data if rows else None))
+        if got < 0:
+            self.api.check()
+            raise SdftHipError("sdft_hip_sdft_power_peak_n failed")
+        self.api.check()
+        assert got == rows, (got, rows)
+        return out
+
     def isdft(self, dfts, out=None):
         """Synthesise samples from a DFT matrix (n, dftsize) [(channels, n, dftsize)]."""
         self.api.clear()
@@ -736,6 +779,9 @@ def power_sum_rows(n: int, every: int, first: int) -> int:
     """Rows a pooled power analysis call of n samples writes (sdft_hip_sdft_power_sum_n): the head window, if any, and one row per
     grid point."""
     return (1 if first > 0 and n > 0 else 0) + every_rows(n, every, first)
+
+
+HOLDS = {"max": 0, "min": 1, 0: 0, 1: 1}                     # SDFT.power_peak's hold -> enum sdft_hip_hold
 
 
 def covariance_pairs(nch: int):
