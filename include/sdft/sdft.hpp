@@ -47,6 +47,8 @@ const char* sdft_hip_last_error(void);
   std::size_t sdft_hip_pairs_##SUF(const void* plan);                                                                  \
   long sdft_hip_sdft_cross_sum_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, \
                                        std::size_t bin0, std::size_t nbins, void* sums);                               \
+  long sdft_hip_sdft_lag_sum_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, \
+                                     std::size_t bin0, std::size_t nbins, void* sums);                                 \
   int sdft_hip_set_array_##SUF(void* plan, std::size_t nch, const std::size_t* chan);                                  \
   std::size_t sdft_hip_array_channels_##SUF(const void* plan);                                                         \
   long sdft_hip_sdft_covariance_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, \
@@ -105,6 +107,7 @@ namespace sdft
       static int set_pairs(void* p, std::size_t np, const std::size_t* a, const std::size_t* b) { return sdft_hip_set_pairs_##SUF(p, np, a, b); } \
       static std::size_t pairs(const void* p) { return sdft_hip_pairs_##SUF(p); } \
       static long sdft_cross_sum_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_cross_sum_n_##SUF(p, n, x, e, f, b, k, d); } \
+      static long sdft_lag_sum_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_lag_sum_n_##SUF(p, n, x, e, f, b, k, d); } \
       static int set_array(void* p, std::size_t nc, const std::size_t* c) { return sdft_hip_set_array_##SUF(p, nc, c); } \
       static std::size_t array_channels(const void* p) { return sdft_hip_array_channels_##SUF(p); } \
       static long sdft_covariance_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_covariance_n_##SUF(p, n, x, e, f, b, k, d); } \
@@ -314,6 +317,26 @@ namespace sdft
       {
         const char* e = sdft_hip_last_error();
         throw std::runtime_error(std::string("sdft_hip_sdft_cross_sum_n: ") + (e ? e : "failed"));
+      }
+      return static_cast<std::size_t>(rows);
+    }
+
+    /**
+     * Lag-product analysis (sdft_hip_sdft_lag_sum_n): the sum of X[t] conj(X[t - 1]) over the windows of power_sum()'s grid, for
+     * the bins bin0 <= k < bin0 + nbins; out is dense (rows, nbins) [(channels, rows, nbins)].  The angle of a sum over 2 pi,
+     * times the sample rate, is the bin's power-weighted mean frequency over the window.  The row before the first sample is the
+     * row of the plan's state (the zero row of a fresh plan).  Sums, not means; first > 0 makes row 0 the head window that
+     * completes the previous call's last row.  The state advances over all samples and all bins.  Returns the number of rows
+     * written.
+     **/
+    std::size_t lag_sum(const std::size_t nsamples, const T* samples, const std::size_t every, const std::size_t first,
+                        const std::size_t bin0, const std::size_t nbins, std::complex<F>* const out)
+    {
+      const long rows = api::sdft_lag_sum_n(plan_, nsamples, samples, every, first, bin0, nbins, out);
+      if (rows < 0)
+      {
+        const char* e = sdft_hip_last_error();
+        throw std::runtime_error(std::string("sdft_hip_sdft_lag_sum_n: ") + (e ? e : "failed"));
       }
       return static_cast<std::size_t>(rows);
     }

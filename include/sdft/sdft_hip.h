@@ -347,6 +347,50 @@ long sdft_hip_sdft_cross_sum_n(sdft_t* sdft, const sdft_size_t nsamples, const s
                                const sdft_size_t bin0, const sdft_size_t nbins,
                                sdft_fdx_t* sums) SDFT_HIP_SYMBOL(sdft_cross_sum_n);
 
+/* ---- lag-product analysis --------------------------------------------------------------------------
+   What a sliding DFT has over a hopped STFT is a row per sample, and the first thing a phase vocoder, a sinusoidal tracker, a
+   reassignment or a Doppler (pulse-pair) estimator does with a row per sample is the phase advance of every bin from one sample to
+   the next:
+     R[k] = sum over the samples t of a window of X[t][k] * conj(X[t - 1][k])
+   arg(R[k]) / (2 pi) * samplerate is the power-weighted mean frequency of bin k over the window (with hop 1: no unwrapping, no
+   bin-centre correction), |R[k]| against sdft_hip_sdft_power_sum_n's sum its coherence.  The call keeps the phase that the power,
+   pooled, peak-hold and filterbank calls discard, without storing the complex rows and with ONE recurrence per channel.
+   sdft_hip_sdft_lag_sum_n takes its grid, windows, head row, row count, streaming rule, the next call's first, the band,
+   every > nsamples and the pointer rules from sdft_hip_sdft_power_sum_n / sdft_hip_sdft_cross_sum_n, unchanged: rows =
+   (first > 0 && nsamples > 0 ? 1 : 0) + (rows of sdft_hip_sdft_every_n); sums are returned, not means; with first > 0, row 0
+   completes the previous call's last row (the host adds the two).
+   Let A = (ar, ai) be the windowed, weighted bin sdft_sdft_n stores at sample t and B = (br, bi) the one it stores at sample
+   t - 1.  The term is A * conj(B) in the cross-spectrum call's expression, formed in sdft_fd_t with no fused multiply-add:
+     re = fl( fl(ar*br) + fl(ai*bi) )        im = fl( fl(ai*br) - fl(ar*bi) )
+   Row r holds, for bin0 <= k < bin0 + nbins, the sum of these terms over the r-th window, each component accumulated separately
+   in sdft_fd_t from a -0 start in ascending time order; pieces of a window that a time chunk cuts are added in ascending time
+   order (no floating-point atomics).  sums is [rows][nbins] complex numbers (re, im), dense, aligned to sizeof(sdft_fd_t) only;
+   batched plans: samples [channels][nsamples], sums [channels][rows][nbins], each channel by itself.  samples and sums may each
+   be host or device memory (option "async" applies to device pointers).
+   The row before the call's first sample is the row of the plan's state: the window applied to the demodulated state, which is
+   acc where the cursor is 0 modulo 2 * dftsize and acc * conj(fid) elsewhere.  For a stream that is the last row the previous call
+   produced, whichever entry point that call was; for a fresh or reset plan it is the zero row, so the first term is zero; after
+   sdft_hip_set_state it is the row of the installed state.
+   Five things are promised.
+   (1) The same plan, options and input give the same bits on every run.
+   (2) At every == 1, first == 0, each value is exactly the expression above on consecutive sdft_sdft_n rows, wherever that call
+       is bit-identical to the reference: FD float, FD double with option "carry" = 1, calls shorter than 512 samples -- for any
+       cut of time into chunks, any host staging and any cut of a stream into calls.  A term whose previous row is the zero row
+       of a fresh plan is zero as a number; its sign is unspecified.
+   (3) On those routes and for other grids, promise (5) of sdft_hip_sdft_cross_sum_n holds per component:
+       |sum - S| <= gamma_(L-1) * sum |term|.
+   (4) On the other routes that call's term deviation comes on top: 2.1e-11 times the call's largest |X|^2 times L.  The previous
+       row at a chunk start comes from the chunk's own carry, which lies inside the same row deviation.
+   (5) The stream state of every channel is afterwards the one sdft_sdft_n of the same samples leaves -- bins outside the band
+       step every sample too.  Any other entry point may follow.
+   The call is never resident, pipelined or fused and always runs its own kernel ("last_kernel" = 12).  Returns the number of rows
+   written (0 only for nsamples == 0), or -1 with sdft_hip_last_error() set and the stream state untouched: a NULL plan,
+   every == 0, nbins == 0, bin0 + nbins > dftsize, sums == NULL with rows > 0, or a workspace that cannot be reserved. */
+long sdft_hip_sdft_lag_sum_n(sdft_t* sdft, const sdft_size_t nsamples, const sdft_td_t* samples,
+                             const sdft_size_t every, const sdft_size_t first,
+                             const sdft_size_t bin0, const sdft_size_t nbins,
+                             sdft_fdx_t* sums) SDFT_HIP_SYMBOL(sdft_lag_sum_n);
+
 /* ---- array covariance analysis -----------------------------------------------------------------------
    The spatial covariance matrix per bin of an ARRAY of channels -- what MVDR / GEV beamformers, MUSIC and multichannel Wiener
    filters start from: the pooled cross-spectrum of ALL pairs of the array's channels.  As a pair list that costs two recurrences
@@ -546,7 +590,7 @@ double sdft_hip_time_hops(sdft_t* sdft, size_t hops, size_t hop, const sdft_td_t
    "relay_flow", "relay_groups", "chain_debug", "inverse_nt", "inverse_nt_skip_mb", "inverse_step", "inverse_ordered", "host_direct", "copy_streams", "prefix_cells", "array_group", "mix_group", "mix_block" (sdft_capi.inc names what each selects);
    get_option "test_hooks" = 1 in that build.
    get_option additionally answers "tiles", "bins_per_lane", "row_slots", "last_chunks",
-   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis, 6 pooled power analysis, 7 filterbank analysis, 8 pooled cross-spectrum analysis, 9 array covariance analysis, 10 channel-mix analysis, 11 peak-hold analysis), "last_segments", "last_fused",
+   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis, 6 pooled power analysis, 7 filterbank analysis, 8 pooled cross-spectrum analysis, 9 array covariance analysis, 10 channel-mix analysis, 11 peak-hold analysis) or 12 (lag-product analysis), "last_segments", "last_fused",
    "last_filterbank_launches" (forward_filterbank_kernel launches of the last filterbank call, over all of its host segments: more than its carry segments once its pieces exceed the workspace bound),
    "last_chain", "last_fused_exact", "last_fused_fold", "last_process_path" (1 fused kernel, 2 hop pair, 3 two-pass),
    "last_self" (no pre-pass launch), "last_prefix" (long calls: one pre-pass launch, prefix_cells_kernel), "last_inverse_nt" / "last_inverse_skip" (what the last synthesis launch used: non-temporal loads, rows read with ordinary loads),

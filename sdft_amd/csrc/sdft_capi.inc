@@ -147,6 +147,15 @@ long SDFT_FN(sdft_cross_sum_n)(void* p, size_t n, const SDFT_TD* x, size_t every
   if (rows > (size_t)LONG_MAX) { sdfthip::set_error("sdft_hip_sdft_cross_sum_n", "more rows than a long can count"); return -1; }
   return (long)rows;
 }
+// lag-product analysis: X[t] conj(X[t - 1]) of every channel summed over those windows; see sdft_hip.h
+long SDFT_FN(sdft_lag_sum_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, size_t bin0, size_t nbins, SDFT_FD* sums)
+{
+  if (!p) { sdfthip::set_error("sdft_hip_sdft_lag_sum_n", "NULL plan"); return -1; }
+  size_t rows = 0;
+  if (!P(p)->sdft_lag_sum_n(n, x, every, first, bin0, nbins, sums, rows)) return -1;
+  if (rows > (size_t)LONG_MAX) { sdfthip::set_error("sdft_hip_sdft_lag_sum_n", "more rows than a long can count"); return -1; }
+  return (long)rows;
+}
 // array covariance analysis: the cross-spectrum call's sums for all pairs of the channels of an array, by blocks; see sdft_hip.h
 int SDFT_FN(set_array)(void* p, size_t nch, const size_t* chan)
 {

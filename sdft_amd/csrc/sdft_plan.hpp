@@ -205,7 +205,7 @@ class Plan
   long opt_prefix_cells = 1;     // test hook: the prefix-cell route of long calls (logic::ForwardQuery::prefix_cells)
   long last_prefix = 0;          // the last analysis call took it (one pre-pass launch: prefix_cells_kernel)
 
-  long last_kernel = 0;          // 1 = forward_kernel (independent tiles), 2 = forward_rows_kernel, 3 = hop, 4 = forward_every_kernel, 5 = forward_power_kernel, 6 = forward_pooled_power_kernel, 7 = forward_filterbank_kernel, 8 = forward_cross_sum_kernel, 9 = forward_covariance_kernel, 10 = forward_mix_kernel, 11 = forward_power_peak_kernel
+  long last_kernel = 0;          // 1 = forward_kernel (independent tiles), 2 = forward_rows_kernel, 3 = hop, 4 = forward_every_kernel, 5 = forward_power_kernel, 6 = forward_pooled_power_kernel, 7 = forward_filterbank_kernel, 8 = forward_cross_sum_kernel, 9 = forward_covariance_kernel, 10 = forward_mix_kernel, 11 = forward_power_peak_kernel, 12 = forward_lag_sum_kernel
 
   // device-resident stream state
   DevBuf<fdx> d_tw, d_syn, d_wtab;
@@ -597,16 +597,17 @@ class Plan
   // peak: with psum, peak-hold analysis (sdft_power_peak_n) -- forward_power_peak_kernel holds its largest (0) or smallest (1) over those windows; -1: no such call
   // fbk: filterbank analysis (sdft_filterbank_n) -- forward_filterbank_kernel stores the band sums of the plan's filterbank (out is unused)
   // cross: cross-spectrum analysis (sdft_cross_sum_n) -- forward_cross_sum_kernel sums A conj(B) of the plan's pairs over the grid's windows (out is unused)
+  // lag: with cross, lag-product analysis (sdft_lag_sum_n) -- forward_lag_sum_kernel sums X[t] conj(X[t - 1]) of every channel over those windows; cross has the plan's channels in the pairs' place and no items
   // cov: covariance analysis (sdft_covariance_n) -- forward_covariance_kernel does that for all pairs of the plan's array, by blocks (out is unused)
   // mixa: channel-mix analysis (sdft_mix_n) -- forward_mix_kernel stores the weighted sums of the plan's mix on the grid (out is unused)
   bool forward_device(size_t n, const TD* x, size_t x_stride, fdx* out, size_t out_stride, fdx* const* rows,
                       const FuseArgs<TD, FD>* fuse = nullptr, const EveryGrid* every = nullptr, const PowerArgs<FD>* power = nullptr,
                       const PowerSumArgs<FD>* psum = nullptr, const FilterbankArgs<FD>* fbk = nullptr,
-                      const CrossSumArgs<FD>* cross = nullptr, const CovarianceArgs<FD>* cov = nullptr, const MixArgs<FD>* mixa = nullptr, int peak = -1)
+                      const CrossSumArgs<FD>* cross = nullptr, const CovarianceArgs<FD>* cov = nullptr, const MixArgs<FD>* mixa = nullptr, int peak = -1, bool lag = false)
   {
     const struct { size_t cursor; int st_cur, hist_cur; bool fid_canonical; } was{cursor, st_cur, hist_cur, fid_canonical};
     auto restore = [&] { cursor = was.cursor; st_cur = was.st_cur; hist_cur = was.hist_cur; fid_canonical = was.fid_canonical; };
-    if (!forward_launch(n, x, x_stride, out, out_stride, rows, fuse, every, power, psum, fbk, cross, cov, mixa, peak))
+    if (!forward_launch(n, x, x_stride, out, out_stride, rows, fuse, every, power, psum, fbk, cross, cov, mixa, peak, lag))
     {
       // a launch that failed half-way (a host expression that does not compile, a grid that does not fit, an allocation)
       // must not leave the stream half-advanced: what was queued wrote the OTHER buffer set and the workspace only
@@ -620,7 +621,7 @@ class Plan
     restore();
     const long saved = opt_chain;
     opt_chain = 0;
-    const bool ok = forward_launch(n, x, x_stride, out, out_stride, rows, fuse, every, power, psum, fbk, cross, cov, mixa, peak) && (hipStreamSynchronize(stream) == hipSuccess);
+    const bool ok = forward_launch(n, x, x_stride, out, out_stride, rows, fuse, every, power, psum, fbk, cross, cov, mixa, peak, lag) && (hipStreamSynchronize(stream) == hipSuccess);
     opt_chain = saved;
     ++ring_recoveries;
     // a recovered call is a valid call: it goes to the warning channel (and the counter), not to the error channel, so a
@@ -636,13 +637,13 @@ class Plan
 
   logic::ForwardQuery forward_query(size_t n, const fdx* out, size_t out_stride, fdx* const* rows, const FuseArgs<TD, FD>* fuse, const EveryGrid* every,
                                    const PowerArgs<FD>* power, const PowerSumArgs<FD>* psum, const FilterbankArgs<FD>* fbk, const CrossSumArgs<FD>* cross,
-                                   const CovarianceArgs<FD>* cov, const MixArgs<FD>* mixa, int peak) const
+                                   const CovarianceArgs<FD>* cov, const MixArgs<FD>* mixa, int peak, bool lag) const
   {
     logic::ForwardQuery q;
     q.n = n; q.nbins = nbins; q.channels = channels; q.fd_bytes = sizeof(FD); q.fdx_bytes = sizeof(fdx);
     q.window = window; q.compute_units = compute_units; q.cursor = cursor; q.exact = carry_mode == CARRY_EXACT; q.fid_canonical = fid_canonical;
     q.fuse = fuse != nullptr; q.fuse_store = fuse && fuse->store; q.reference_order = fuse && wants_reference_order(); q.coeff_ready = coeff_ready;
-    q.every = every != nullptr; q.power = power != nullptr; q.power_every = power ? (size_t)power->every : fbk ? (size_t)fbk->every : mixa ? (size_t)mixa->every : 1; q.power_sum = psum != nullptr && peak < 0; q.power_peak = psum != nullptr && peak >= 0; q.filterbank = fbk != nullptr; q.cross_sum = cross != nullptr; q.cross_items = cross ? cross->nitems : cov ? cov->nitems : mixa ? mixa->nitems : 0; q.covariance = cov != nullptr; q.mix = mixa != nullptr; q.row_pointers = rows != nullptr; q.out = reinterpret_cast<uintptr_t>(out); q.out_stride = out_stride;
+    q.every = every != nullptr; q.power = power != nullptr; q.power_every = power ? (size_t)power->every : fbk ? (size_t)fbk->every : mixa ? (size_t)mixa->every : 1; q.power_sum = psum != nullptr && peak < 0; q.power_peak = psum != nullptr && peak >= 0; q.filterbank = fbk != nullptr; q.cross_sum = cross != nullptr && !lag; q.lag_sum = cross != nullptr && lag; q.cross_items = cross ? cross->nitems : cov ? cov->nitems : mixa ? mixa->nitems : 0; q.covariance = cov != nullptr; q.mix = mixa != nullptr; q.row_pointers = rows != nullptr; q.out = reinterpret_cast<uintptr_t>(out); q.out_stride = out_stride;
     q.analysis_batch = calls.analysis_batch; q.pipe_wanted = pipe_wanted(nullptr); q.prev_out = prev_out;
     q.rows_kernel = opt_rows_kernel; q.row_slots_max = opt_row_slots_max; q.interior = opt_interior; q.chunk = opt_chunk; q.self = opt_self;
     q.fused = opt_fused; q.fold = opt_fold; q.fft_carry = opt_fft_carry; q.hop_kernel = opt_hop_kernel; q.chain = opt_chain; q.chain_L = opt_chain_L;
@@ -656,13 +657,13 @@ class Plan
   bool forward_launch(size_t n, const TD* x, size_t x_stride, fdx* out, size_t out_stride, fdx* const* rows,
                       const FuseArgs<TD, FD>* fuse = nullptr, const EveryGrid* every = nullptr, const PowerArgs<FD>* power = nullptr,
                       const PowerSumArgs<FD>* psum = nullptr, const FilterbankArgs<FD>* fbk = nullptr,
-                      const CrossSumArgs<FD>* cross = nullptr, const CovarianceArgs<FD>* cov = nullptr, const MixArgs<FD>* mixa = nullptr, int peak = -1)
+                      const CrossSumArgs<FD>* cross = nullptr, const CovarianceArgs<FD>* cov = nullptr, const MixArgs<FD>* mixa = nullptr, int peak = -1, bool lag = false)
   {
     if (n == 0 || nbins == 0) return true;
     SDFT_TRY(hipSetDevice(device));
     flag_pending = false;                                    // only the hop kernel signals its completion
     calls.on_analysis(fuse != nullptr);                      // (which kind of host is calling: logic::CallPattern)
-    const logic::ForwardRoute r = logic::forward_route(forward_query(n, out, out_stride, rows, fuse, every, power, psum, fbk, cross, cov, mixa, peak), [this] { return gate_ok(); });
+    const logic::ForwardRoute r = logic::forward_route(forward_query(n, out, out_stride, rows, fuse, every, power, psum, fbk, cross, cov, mixa, peak, lag), [this] { return gate_ok(); });
     pipe_this = r.pipelined;
     if (r.out.hi) prev_out = r.out;
     last_kernel = r.kernel; last_chunks = r.chunks; last_chunk_len = r.len; last_tiles = r.tiles; last_interior = r.interior;
@@ -691,7 +692,7 @@ class Plan
     }
 
     DeltaIn<TD, FD> din;
-    if (!forward_delta(r, n, x, x_stride, din) || !forward_carries(r, n, din) || !forward_rows_stage(r, n, out, out_stride, rows, fuse, every, power, psum, fbk, cross, cov, mixa, peak)) return false;
+    if (!forward_delta(r, n, x, x_stride, din) || !forward_carries(r, n, din) || !forward_rows_stage(r, n, out, out_stride, rows, fuse, every, power, psum, fbk, cross, cov, mixa, peak, lag)) return false;
 
     // fid stays on the canonical rotation sequence unless this call seeded chunks from the closed-form
     // table; a call that crosses the roll-over with serial fid arithmetic puts it back
@@ -848,7 +849,7 @@ class Plan
   // it, see forward_device)
   bool forward_rows_stage(const logic::ForwardRoute& r, size_t n, fdx* out, size_t out_stride, fdx* const* rows,
                           const FuseArgs<TD, FD>* fuse, const EveryGrid* every, const PowerArgs<FD>* power, const PowerSumArgs<FD>* psum,
-                          const FilterbankArgs<FD>* fbk, const CrossSumArgs<FD>* cross, const CovarianceArgs<FD>* cov, const MixArgs<FD>* mixa, int peak)
+                          const FilterbankArgs<FD>* fbk, const CrossSumArgs<FD>* cross, const CovarianceArgs<FD>* cov, const MixArgs<FD>* mixa, int peak, bool lag)
   {
     const size_t nb = nbins;
     const long chunks = r.chunks, segments = r.segments;
@@ -957,6 +958,7 @@ class Plan
           ja = sp.jb;
         }
       }
+      else if (cross && lag) { if (!grid_fits(blocks)) return false; launch_forward_lag_sum(fa, cs, (unsigned)blocks); }
       else if (cross) { if (!grid_fits(blocks)) return false; launch_forward_cross_sum(fa, cs, (unsigned)blocks); }
       else if (cov) { if (!grid_fits(blocks)) return false; if (!launch_forward_covariance(fa, cv, (unsigned)blocks)) return false; }
       else if (mixa) { if (!grid_fits(blocks)) return false; if (!launch_forward_mix(fa, *mixa, (unsigned)blocks)) return false; }
@@ -975,7 +977,8 @@ class Plan
     }
     if (cross && chunks > 1)
     {
-      // (complex sums over nbins_out bins are real sums over 2 * nbins_out numbers: the pooled power call's adder, pairs for channels)
+      // (complex sums over nbins_out bins are real sums over 2 * nbins_out numbers: the pooled power call's adder, pairs for channels;
+      // the lag-product call's pairs are the plan's channels)
       const PowerSumArgs<FD> pieces{cs.row0, cs.row0_stride, cs.rest, cs.rest_stride, cs.ws, cs.every, cs.first, cs.bin0, 2u * cs.nbins_out};
       if (!launch_power_sum_rows(pieces, n, chunks, r.len, r.shift, cs.npairs)) return false;
       SDFT_TRY(hipGetLastError());

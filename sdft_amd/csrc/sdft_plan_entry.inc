@@ -568,6 +568,80 @@
     });
   }
 
+  // lag-product analysis (sdft_hip_sdft_lag_sum_n): per channel the sums of X[t] conj(X[t - 1]) over the windows of
+  // sdft_power_sum_n's grid, dense [channels][rows][nbins_out] complex numbers, row 0 the head window [0, first) when first > 0.
+  // The cross-spectrum call above with the plan's channels in the pairs' place -- its arguments (no items), workspace, head and
+  // stage buffers, pooled_power_rows_kernel and pooled_power_add_kernel -- and forward_lag_sum_kernel, which steps one recurrence per
+  // wave on the pooled power call's route.  The row before a call's (and so a segment's) first sample is the row of the state the
+  // call starts from, which the kernel demodulates itself: a later segment's first term needs nothing from this side.
+  bool sdft_lag_sum_n(size_t n, const TD* x, size_t every, size_t first, size_t bin0, size_t nbins_out, FD* sums, size_t& rows)
+  {
+    static const char* fn = "sdft_hip_sdft_lag_sum_n";
+    rows = 0;
+    if (every == 0) { set_error(fn, "every must be at least 1"); return false; }
+    if (nbins_out == 0) { set_error(fn, "nbins must be at least 1"); return false; }
+    if (!logic::power_band_ok(nbins, bin0, nbins_out)) { set_error(fn, "the band bin0 ... bin0 + nbins - 1 does not lie within the plan's bins"); return false; }
+    rows = logic::power_sum_rows(n, every, first);
+    if (rows > 0 && !sums) { set_error(fn, "sums is NULL but the call writes rows"); return false; }
+    if (n == 0) return true;
+    if (!bind()) return false;
+    if (!pipe_join()) return false;
+    if (every > n) every = n;                                // (the same windows; keeps first + k * every in range)
+    const bool xd = on_device(x);
+    const bool od = on_device(sums);
+    const size_t nb2 = 2 * nbins_out;                        // numbers of a row of one channel
+    const size_t row_bytes = channels * nb2 * sizeof(FD);
+    auto band = [&](FD* row0, size_t row0_stride, FD* rest, size_t rest_stride, size_t f) {
+      return CrossSumArgs<FD>{row0, row0_stride, rest, rest_stride, nullptr, nullptr, (unsigned)channels, (unsigned)channels,
+                              (unsigned long long)every, (unsigned long long)f, (unsigned)bin0, (unsigned)nbins_out};
+    };
+    auto run = [&](size_t m, const TD* td, size_t td_stride, const CrossSumArgs<FD>& g) {
+      return forward_device(m, td, td_stride, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &g, nullptr, nullptr, -1, true);
+    };
+    const size_t stride = logic::lag_channel_stride(rows, nbins_out);
+    if (xd && od)
+    {
+      const CrossSumArgs<FD> g = band(sums, stride, sums + nb2, stride, first);
+      return run(n, x, n, g) && finish(rows * row_bytes);
+    }
+    // host memory: segments of at most seg samples (logic::lag_sum_segment)
+    const size_t seg = logic::lag_sum_segment(n, every, first, channels, nbins_out, sizeof(FD), sizeof(TD), stage_bytes, xd, od);
+    const size_t seg_rows_max = (seg + every - 1) / every + 1;
+    if (!od && !d_cross_stage.reserve(channels * seg_rows_max * nb2)) return false;
+    std::vector<FD> head;                                    // host buffers: a segment's head rows on their way to the rows they complete
+    return staged_segments(n, seg, StagedCall{true, const_cast<TD*>(x), !xd, nullptr, false, rows, seg_rows_max, nb2 * sizeof(FD)}, [&](Segment& s) {
+      const size_t f = logic::every_first_from(s.t, every, first);
+      const logic::PowerSumWindow w0 = logic::power_sum_window(s.t, n, every, first);      // of the segment's row 0 in the call
+      const bool joins = w0.begin < s.t;                     // row 0 is a head: it completes row w0.row of the call
+      const size_t seg_rows = logic::power_sum_rows(s.m, every, f), kept = seg_rows - (joins ? 1 : 0);
+      if (joins && !d_cross_head.reserve(channels * nb2)) return false;
+      const size_t r0 = w0.row + (joins ? 1 : 0);            // the segment's first row of its own
+      s.rows = 0;                                            // (nothing for staged_segments to copy)
+      FD* const at = od ? sums + r0 * nb2 : d_cross_stage.p; // scratch: [channels][kept][nbins_out] complex
+      const size_t at_stride = od ? stride : kept * nb2;
+      const CrossSumArgs<FD> g = joins ? band(d_cross_head.p, nb2, at, at_stride, f) : band(at, at_stride, at + nb2, at_stride, f);
+      if (!run(s.m, s.td, s.td_stride, g)) return false;
+      if (od)
+      {
+        if (!joins) return true;
+        const unsigned long long threads = (unsigned long long)channels * nb2;
+        hipLaunchKernelGGL((pooled_power_add_kernel<FD>), dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
+                           sums + w0.row * nb2, stride, d_cross_head.p, (unsigned)nb2, (unsigned)channels);
+        SDFT_TRY(hipGetLastError());
+        return true;
+      }
+      for (size_t c = 0; c < channels && kept; ++c)
+        if (!to_host(sums + c * stride + r0 * nb2, d_cross_stage.p + c * kept * nb2, kept * nb2 * sizeof(FD))) return false;
+      if (!joins) return true;
+      head.resize(channels * nb2);
+      if (!to_host(head.data(), d_cross_head.p, head.size() * sizeof(FD))) return false;
+      SDFT_TRY(hipStreamSynchronize(stream));
+      for (size_t c = 0; c < channels; ++c)
+        for (size_t k = 0; k < nb2; ++k) sums[c * stride + w0.row * nb2 + k] += head[c * nb2 + k];
+      return true;
+    });
+  }
+
   // ---- array covariance analysis ------------------------------------------------------------------------------------------------
   // sdft_hip_set_array: the list is host memory and is copied (nullptr: the channels 0 ... nch - 1); a refused list leaves the
   // installed one as it is.  The work items (logic::covariance_items) and the list go to the device here, and again when a test

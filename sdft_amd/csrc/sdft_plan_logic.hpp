@@ -362,6 +362,16 @@ inline size_t cross_sum_slot(size_t item, size_t chunks, size_t chunk, int slot,
 // numbers (not complex numbers) from one pair's first sum to the next pair's
 inline size_t cross_pair_stride(size_t rows, size_t nbins_out) { return power_channel_stride(rows, 2 * nbins_out); }
 
+// ---- lag-product analysis (sdft_hip_sdft_lag_sum_n) -----------------------------------------------------------------------------
+// Row r of a channel is the sum over the r-th window of the pooled power call's grid of A conj(B), A the windowed bin of sample t
+// and B that of sample t - 1 of the SAME channel: the cross-spectrum call's term, rows, workspace and strides with the plan's
+// channels in the pairs' place, on the pooled power call's route (one recurrence per wave, its chunk choice).  The row before a
+// chunk's first sample is demodulated from the chunk's carry-in (forward_lag_sum_kernel), so no carry pass and no launch changes.
+inline size_t lag_sum_workspace(size_t channels, size_t chunks, size_t nbins_out) { return cross_sum_workspace(std::max<size_t>(channels, 1), chunks, nbins_out); }
+inline size_t lag_sum_slot(size_t channel, size_t chunks, size_t chunk, int slot, size_t nbins_out) { return cross_sum_slot(channel, chunks, chunk, slot, nbins_out); }
+inline size_t lag_channel_stride(size_t rows, size_t nbins_out) { return cross_pair_stride(rows, nbins_out); }
+// (the time segments of a call on host memory: lag_sum_segment, beside stage_rows)
+
 // ---- array covariance analysis (sdft_hip_sdft_covariance_n) ------------------------------------------------------------------------
 // The array is an ordered list of nch distinct channels of the plan (sdft_hip_set_array); the call returns the cross-spectrum
 // call's sums for ALL pairs of its elements: the upper triangle in row-major order, element (i <= j) -- the pair of the channels
@@ -937,6 +947,7 @@ struct ForwardQuery
   size_t power_every = 1;                 // ... every power_every-th sample
   bool power_sum = false;                 // pooled power analysis (forward_pooled_power_kernel)
   bool power_peak = false;                // peak-hold analysis (forward_power_peak_kernel): the pooled power call's route (never with power_sum)
+  bool lag_sum = false;                   // lag-product analysis (forward_lag_sum_kernel): the pooled power call's route (never with power_sum or power_peak)
   bool filterbank = false;                // filterbank analysis (forward_filterbank_kernel) on the grid of power_every
   bool cross_sum = false;                 // pooled cross-spectrum analysis (forward_cross_sum_kernel) of ...
   size_t cross_items = 0;                 // ... this many work items (logic::cross_items), which take the channels' place in the launch
@@ -952,7 +963,7 @@ struct ForwardQuery
        chain_L = 0, relay_flow = 1, segments = 0, xcd_map = 1, rows_f32 = 1, pipeline = 1;
   long prefix_cells = 1;                  // test hook: 0 = never the prefix-cell route, 1 = calls beyond kSelfMax, 2 = whatever the length
 };
-enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6, FK_FILTERBANK = 7, FK_CROSS_SUM = 8, FK_COVARIANCE = 9, FK_MIX = 10, FK_POWER_PEAK = 11 };     // = get_option "last_kernel"
+enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6, FK_FILTERBANK = 7, FK_CROSS_SUM = 8, FK_COVARIANCE = 9, FK_MIX = 10, FK_POWER_PEAK = 11, FK_LAG_SUM = 12 };     // = get_option "last_kernel"
 // carries: the single chunk's are the stream state (delta_kernel copies it); pre-pass partial sums + scan (carries from the
 // closed-form table); the serial exact pass (carry_exact_kernel); the relay form of the exact pass (carry_relay_kernel)
 enum CarryForm : int { CARRY_STATE = 0, CARRY_SUMS = 1, CARRY_SERIAL = 2, CARRY_RELAY = 3 };
@@ -1000,8 +1011,8 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   ForwardRoute r;
   const size_t nb = q.nbins, span = 2 * nb, n = q.n, ch = std::max<size_t>(q.channels, 1);
   const bool pow2 = (span & (span - 1)) == 0;
-  // the decimated, the power-spectrogram, the pooled power, the peak-hold, the filterbank, the cross-spectrum, the covariance and the mix analysis have the tile form only
-  const bool grid = q.every || q.power || q.power_sum || q.power_peak || q.filterbank || q.cross_sum || q.covariance || q.mix;
+  // the decimated, the power-spectrogram, the pooled power, the peak-hold, the lag-product, the filterbank, the cross-spectrum, the covariance and the mix analysis have the tile form only
+  const bool grid = q.every || q.power || q.power_sum || q.power_peak || q.lag_sum || q.filterbank || q.cross_sum || q.covariance || q.mix;
   // (channel, chunk) groups of a tile launch per chunk: the cross-spectrum, the covariance and the mix call's are their work items
   const size_t lanes = (q.cross_sum || q.covariance || q.mix) ? std::max<size_t>(q.cross_items, 1) : ch;
   const bool rows = !grid && rows_kernel_ok(nb, q.fdx_bytes, q.row_pointers, q.rows_kernel != 0, q.row_slots_max);
@@ -1029,12 +1040,12 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   {
     EveryQuery e;
     e.n = n; e.channels = lanes; e.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); e.exact = q.exact; e.forced_chunk = q.chunk; e.compute_units = q.compute_units;
-    c = (q.power_sum || q.power_peak || q.cross_sum || q.covariance) ? choose_power_sum_chunks(e) : (q.power || q.filterbank || q.mix) ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
+    c = (q.power_sum || q.power_peak || q.lag_sum || q.cross_sum || q.covariance) ? choose_power_sum_chunks(e) : (q.power || q.filterbank || q.mix) ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
   }
   else c = choose_chunks(chunk_query(q, rows, r.pipelined));
   r.chunks = c.chunks; r.len = c.len;
   r.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); r.interior = interior_lanes(q.window, q.fdx_bytes, q.interior);
-  r.kernel = q.mix ? FK_MIX : q.covariance ? FK_COVARIANCE : q.cross_sum ? FK_CROSS_SUM : q.filterbank ? FK_FILTERBANK : q.power_peak ? FK_POWER_PEAK : q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
+  r.kernel = q.mix ? FK_MIX : q.covariance ? FK_COVARIANCE : q.cross_sum ? FK_CROSS_SUM : q.filterbank ? FK_FILTERBANK : q.lag_sum ? FK_LAG_SUM : q.power_peak ? FK_POWER_PEAK : q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
   if (r.chunks == 1 && q.hop_kernel && nb >= 2 && !q.fuse && !grid) { r.kernel = FK_HOP; return r; }
 
   // self-carried chunks: every workgroup derives its carry-in from the raw samples (fold + one FFT in LDS) and forms
@@ -1279,6 +1290,21 @@ inline size_t stage_rows(size_t n, size_t row_bytes, size_t stage_bytes)
 {
   const size_t seg = std::max<size_t>(1, stage_bytes / std::max<size_t>(row_bytes, 1));
   return std::min(seg, std::max<size_t>(n, 1));
+}
+// The lag-product call on host memory goes in time segments of at most this many samples: the cross-spectrum call's bounds with
+// npairs = channels -- the rows a segment writes (channels * 2 * nbins_out numbers each) and the samples it reads stay within
+// stage_bytes, and where the grid allows it a segment is made of whole windows, so that no row is made of two segments.
+// every <= n (the entry point has clamped it); samples_on_device / sums_on_device: that side needs no staging.
+inline size_t lag_sum_segment(size_t n, size_t every, size_t first, size_t channels, size_t nbins_out, size_t fd_bytes, size_t td_bytes,
+                              size_t stage_bytes, bool samples_on_device, bool sums_on_device)
+{
+  const size_t ch = std::max<size_t>(channels, 1);
+  const size_t row_bytes = ch * 2 * nbins_out * fd_bytes;
+  size_t seg = n;
+  if (!sums_on_device) seg = std::min(seg, stage_rows(n, row_bytes, stage_bytes) * every);
+  if (!samples_on_device) seg = std::min(seg, std::max<size_t>((size_t)kHopSamples, stage_rows(n, ch * td_bytes, stage_bytes)));
+  if (seg < n && seg > every && first % every == 0) seg -= seg % every;
+  return seg;
 }
 
 // ---- host memory: the route of an analysis or a synthesis call (Plan::sdft_n / isdft_n run it) -----------------------------

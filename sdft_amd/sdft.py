@@ -661,6 +661,49 @@ class SDFT:
         assert got == rows, (got, rows)
         return out
 
+    def lag_sum(self, samples, every: int, first: int = 0, band=None, out=None):
+        """Lag-product analysis (``sdft_hip_sdft_lag_sum_n``): the sum of ``X[t] * conj(X[t - 1])`` over the windows
+        :meth:`power_sum` cuts the n samples into, for the bins ``band = (bin0, nbins)`` (``None``: all) -> complex array of shape
+        (rows, nbins) [(channels, rows, nbins)], ``rows = power_sum_rows(n, every, first)``, numpy for numpy input, a device
+        tensor for a device tensor.  ``X[t]`` is the row :meth:`sdft` stores at sample t; the row before the first sample is the
+        row of the plan's state: the last row of the call before (whichever entry point), the zero row of a fresh plan.
+        :func:`lag_frequency` turns the sums into frequencies.  Head row, streaming and sums-not-means as with :meth:`power_sum`.
+        The plan's state advances over all n samples and all bins, as with :meth:`sdft`."""
+        self.api.clear()
+        x = samples
+        every, first = int(every), int(first)
+        bin0, nb = (0, self.dftsize) if band is None else (int(band[0]), int(band[1]))
+        if every < 1 or first < 0:
+            raise ValueError(f"every must be >= 1 and first >= 0, got every={every}, first={first}")
+        if bin0 < 0 or nb < 1 or bin0 + nb > self.dftsize:
+            raise ValueError(f"band = (bin0, nbins) must select at least one of the {self.dftsize} bins, got {(bin0, nb)}")
+        cdtype = np.dtype(np.complex64 if np.dtype(self.fd) == np.float32 else np.complex128)
+        if _is_tensor(x):
+            torch = _torch()
+            n = self._shape_x(x.shape)
+            self._check_tensor(x, "samples", self.td)
+            rows = power_sum_rows(n, every, first)
+            shape = (rows, nb) if x.dim() == 1 else (self.channels, rows, nb)
+            if out is None:
+                out = torch.empty(shape, dtype=getattr(torch, cdtype.name), device=x.device)
+            self._check_tensor(out, "out", cdtype, shape)
+            got = self.api.sdft_lag_sum_n(self._p, n, C.c_void_p(x.data_ptr()), every, first, bin0, nb, C.c_void_p(out.data_ptr() if rows else None))
+        else:
+            x = np.ascontiguousarray(x, dtype=self.td)
+            n = self._shape_x(x.shape)
+            rows = power_sum_rows(n, every, first)
+            shape = (rows, nb) if x.ndim == 1 else (self.channels, rows, nb)
+            if out is None:
+                out = np.empty(shape, dtype=cdtype)
+            assert out.flags.c_contiguous and out.shape == shape and out.dtype == cdtype
+            got = self.api.sdft_lag_sum_n(self._p, n, C.c_void_p(x.ctypes.data), every, first, bin0, nb, C.c_void_p(out.ctypes.data if rows else None))
+        if got < 0:
+            self.api.check()
+            raise SdftHipError("sdft_hip_sdft_lag_sum_n failed")
+        self.api.check()
+        assert got == rows, (got, rows)
+        return out
+
     def isdft(self, dfts, out=None):
         """Synthesise samples from a DFT matrix (n, dftsize) [(channels, n, dftsize)]."""
         self.api.clear()
@@ -782,6 +825,18 @@ def power_sum_rows(n: int, every: int, first: int) -> int:
 
 
 HOLDS = {"max": 0, "min": 1, 0: 0, 1: 1}                     # SDFT.power_peak's hold -> enum sdft_hip_hold
+
+
+def lag_frequency(sums, samplerate: float = 1.0):
+    """The frequency estimate of :meth:`SDFT.lag_sum`'s sums: ``angle(sums) / (2 pi) * samplerate``, the power-weighted mean
+    frequency of each bin over its window (the pulse-pair estimator; with one sample per row the angle needs no unwrapping), in
+    ``(-samplerate / 2, samplerate / 2]``; ``nan`` where the sum is 0, whose angle says nothing.  Takes a numpy array or a
+    tensor (which is copied to the host) and returns a float64 numpy array of the same shape."""
+    if _is_tensor(sums):
+        sums = sums.detach().cpu().numpy()
+    z = np.asarray(sums).astype(np.complex128)
+    f = np.angle(z) / (2.0 * np.pi) * float(samplerate)
+    return np.where(z == 0, np.nan, f)
 
 
 def covariance_pairs(nch: int):
