@@ -15,6 +15,17 @@ using plan_t = sdfthip::Plan<SDFT_TD, SDFT_FD>;
 using fdx_t = sdfthip::cx<SDFT_FD>;
 inline plan_t* P(void* p) { return static_cast<plan_t*>(p); }
 inline const plan_t* P(const void* p) { return static_cast<const plan_t*>(p); }
+// the wrapper of a grid analysis call (Plan::sdft_*_n, which hands back its row count): NULL plan, the call, the rows as a long
+template <class Call>
+inline long grid_call(void* p, const char* fn, Call&& call)
+{
+  if (!p) { sdfthip::set_error(fn, "NULL plan"); return -1; }
+  size_t rows = 0;
+  if (!call(*P(p), rows)) return -1;
+  if (rows > (size_t)LONG_MAX) { sdfthip::set_error(fn, "more rows than a long can count"); return -1; }
+  return (long)rows;
+}
+#define SDFT_GRID_CALL(name, ...) grid_call(p, "sdft_hip_" #name, [&](plan_t& q, size_t& rows) { return q.name(__VA_ARGS__, rows); })
 }
 
 extern "C" {
@@ -83,40 +94,16 @@ int SDFT_FN(process_n)(void* p, size_t n, const SDFT_TD* x, SDFT_TD* y, int op, 
 }
 // decimated analysis: the rows of sdft_n at the call's samples first, first + every, ... < n; see sdft_hip.h
 long SDFT_FN(sdft_every_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, void* dfts)
-{
-  if (!p) { sdfthip::set_error("sdft_hip_sdft_every_n", "NULL plan"); return -1; }
-  size_t rows = 0;
-  if (!P(p)->sdft_every_n(n, x, every, first, static_cast<fdx_t*>(dfts), rows)) return -1;
-  if (rows > (size_t)LONG_MAX) { sdfthip::set_error("sdft_hip_sdft_every_n", "more rows than a long can count"); return -1; }
-  return (long)rows;
-}
+{ return SDFT_GRID_CALL(sdft_every_n, n, x, every, first, static_cast<fdx_t*>(dfts)); }
 // power-spectrogram analysis: re^2 + im^2 of a band of bins of the rows of that grid; see sdft_hip.h
 long SDFT_FN(sdft_power_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, size_t bin0, size_t nbins, SDFT_FD* power)
-{
-  if (!p) { sdfthip::set_error("sdft_hip_sdft_power_n", "NULL plan"); return -1; }
-  size_t rows = 0;
-  if (!P(p)->sdft_power_n(n, x, every, first, bin0, nbins, power, rows)) return -1;
-  if (rows > (size_t)LONG_MAX) { sdfthip::set_error("sdft_hip_sdft_power_n", "more rows than a long can count"); return -1; }
-  return (long)rows;
-}
+{ return SDFT_GRID_CALL(sdft_power_n, n, x, every, first, bin0, nbins, power); }
 // pooled power analysis: those powers at every sample, summed over the windows of the grid; see sdft_hip.h
 long SDFT_FN(sdft_power_sum_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, size_t bin0, size_t nbins, SDFT_FD* sums)
-{
-  if (!p) { sdfthip::set_error("sdft_hip_sdft_power_sum_n", "NULL plan"); return -1; }
-  size_t rows = 0;
-  if (!P(p)->sdft_power_sum_n(n, x, every, first, bin0, nbins, sums, rows)) return -1;
-  if (rows > (size_t)LONG_MAX) { sdfthip::set_error("sdft_hip_sdft_power_sum_n", "more rows than a long can count"); return -1; }
-  return (long)rows;
-}
+{ return SDFT_GRID_CALL(sdft_power_sum_n, n, x, every, first, bin0, nbins, sums); }
 // peak-hold analysis: the largest or the smallest of those powers over the windows of the grid; see sdft_hip.h
 long SDFT_FN(sdft_power_peak_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, size_t bin0, size_t nbins, int hold, SDFT_FD* peaks)
-{
-  if (!p) { sdfthip::set_error("sdft_hip_sdft_power_peak_n", "NULL plan"); return -1; }
-  size_t rows = 0;
-  if (!P(p)->sdft_power_peak_n(n, x, every, first, bin0, nbins, hold, peaks, rows)) return -1;
-  if (rows > (size_t)LONG_MAX) { sdfthip::set_error("sdft_hip_sdft_power_peak_n", "more rows than a long can count"); return -1; }
-  return (long)rows;
-}
+{ return SDFT_GRID_CALL(sdft_power_peak_n, n, x, every, first, bin0, nbins, hold, peaks); }
 // filterbank analysis: weighted band sums of those powers on the grid; see sdft_hip.h
 int SDFT_FN(set_filterbank)(void* p, size_t nbands, const size_t* band_bin0, const size_t* band_nbins, const SDFT_FD* weights)
 {
@@ -125,13 +112,7 @@ int SDFT_FN(set_filterbank)(void* p, size_t nbands, const size_t* band_bin0, con
 }
 size_t SDFT_FN(filterbank_bands)(const void* p) { return p ? P(p)->filterbank_bands() : 0; }
 long SDFT_FN(sdft_filterbank_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, SDFT_FD* out)
-{
-  if (!p) { sdfthip::set_error("sdft_hip_sdft_filterbank_n", "NULL plan"); return -1; }
-  size_t rows = 0;
-  if (!P(p)->sdft_filterbank_n(n, x, every, first, out, rows)) return -1;
-  if (rows > (size_t)LONG_MAX) { sdfthip::set_error("sdft_hip_sdft_filterbank_n", "more rows than a long can count"); return -1; }
-  return (long)rows;
-}
+{ return SDFT_GRID_CALL(sdft_filterbank_n, n, x, every, first, out); }
 // pooled cross-spectrum analysis: A conj(B) of the plan's channel pairs summed over the windows of the grid; see sdft_hip.h
 int SDFT_FN(set_pairs)(void* p, size_t npairs, const size_t* pair_a, const size_t* pair_b)
 {
@@ -140,22 +121,10 @@ int SDFT_FN(set_pairs)(void* p, size_t npairs, const size_t* pair_a, const size_
 }
 size_t SDFT_FN(pairs)(const void* p) { return p ? P(p)->pairs_count() : 0; }
 long SDFT_FN(sdft_cross_sum_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, size_t bin0, size_t nbins, SDFT_FD* sums)
-{
-  if (!p) { sdfthip::set_error("sdft_hip_sdft_cross_sum_n", "NULL plan"); return -1; }
-  size_t rows = 0;
-  if (!P(p)->sdft_cross_sum_n(n, x, every, first, bin0, nbins, sums, rows)) return -1;
-  if (rows > (size_t)LONG_MAX) { sdfthip::set_error("sdft_hip_sdft_cross_sum_n", "more rows than a long can count"); return -1; }
-  return (long)rows;
-}
+{ return SDFT_GRID_CALL(sdft_cross_sum_n, n, x, every, first, bin0, nbins, sums); }
 // lag-product analysis: X[t] conj(X[t - 1]) of every channel summed over those windows; see sdft_hip.h
 long SDFT_FN(sdft_lag_sum_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, size_t bin0, size_t nbins, SDFT_FD* sums)
-{
-  if (!p) { sdfthip::set_error("sdft_hip_sdft_lag_sum_n", "NULL plan"); return -1; }
-  size_t rows = 0;
-  if (!P(p)->sdft_lag_sum_n(n, x, every, first, bin0, nbins, sums, rows)) return -1;
-  if (rows > (size_t)LONG_MAX) { sdfthip::set_error("sdft_hip_sdft_lag_sum_n", "more rows than a long can count"); return -1; }
-  return (long)rows;
-}
+{ return SDFT_GRID_CALL(sdft_lag_sum_n, n, x, every, first, bin0, nbins, sums); }
 // array covariance analysis: the cross-spectrum call's sums for all pairs of the channels of an array, by blocks; see sdft_hip.h
 int SDFT_FN(set_array)(void* p, size_t nch, const size_t* chan)
 {
@@ -164,13 +133,7 @@ int SDFT_FN(set_array)(void* p, size_t nch, const size_t* chan)
 }
 size_t SDFT_FN(array_channels)(const void* p) { return p ? P(p)->array_channels() : 0; }
 long SDFT_FN(sdft_covariance_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, size_t bin0, size_t nbins, SDFT_FD* cov)
-{
-  if (!p) { sdfthip::set_error("sdft_hip_sdft_covariance_n", "NULL plan"); return -1; }
-  size_t rows = 0;
-  if (!P(p)->sdft_covariance_n(n, x, every, first, bin0, nbins, cov, rows)) return -1;
-  if (rows > (size_t)LONG_MAX) { sdfthip::set_error("sdft_hip_sdft_covariance_n", "more rows than a long can count"); return -1; }
-  return (long)rows;
-}
+{ return SDFT_GRID_CALL(sdft_covariance_n, n, x, every, first, bin0, nbins, cov); }
 // channel-mix analysis: per-bin weighted sums of the windowed bins of the channels of a mix on a row grid; see sdft_hip.h
 int SDFT_FN(set_mix)(void* p, size_t nout, size_t nch, const size_t* chan, const SDFT_FD* weights)
 {
@@ -179,13 +142,7 @@ int SDFT_FN(set_mix)(void* p, size_t nout, size_t nch, const size_t* chan, const
 }
 size_t SDFT_FN(mix_outputs)(const void* p) { return p ? P(p)->mix_outputs() : 0; }
 long SDFT_FN(sdft_mix_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, size_t bin0, size_t nbins, SDFT_FD* out)
-{
-  if (!p) { sdfthip::set_error("sdft_hip_sdft_mix_n", "NULL plan"); return -1; }
-  size_t rows = 0;
-  if (!P(p)->sdft_mix_n(n, x, every, first, bin0, nbins, out, rows)) return -1;
-  if (rows > (size_t)LONG_MAX) { sdfthip::set_error("sdft_hip_sdft_mix_n", "more rows than a long can count"); return -1; }
-  return (long)rows;
-}
+{ return SDFT_GRID_CALL(sdft_mix_n, n, x, every, first, bin0, nbins, out); }
 int SDFT_FN(set_stream)(void* p, void* hip_stream) { return p && P(p)->set_stream(static_cast<hipStream_t>(hip_stream)) ? 0 : -1; }
 // (a host that asks for the stream may queue work of its own behind a call: from here on every kernel of the plan is on it)
 void* SDFT_FN(get_stream)(void* p)

@@ -591,23 +591,50 @@ class Plan
     status_seen = now;
     return true;
   }
-  // every: decimated analysis (sdft_every_n) -- only the rows of that grid are stored, by forward_every_kernel
-  // power: power-spectrogram analysis (sdft_power_n) -- forward_power_kernel stores |X|^2 of its band on its grid (out is unused)
-  // psum: pooled power analysis (sdft_power_sum_n) -- forward_pooled_power_kernel sums it over the grid's windows (out is unused)
-  // peak: with psum, peak-hold analysis (sdft_power_peak_n) -- forward_power_peak_kernel holds its largest (0) or smallest (1) over those windows; -1: no such call
-  // fbk: filterbank analysis (sdft_filterbank_n) -- forward_filterbank_kernel stores the band sums of the plan's filterbank (out is unused)
-  // cross: cross-spectrum analysis (sdft_cross_sum_n) -- forward_cross_sum_kernel sums A conj(B) of the plan's pairs over the grid's windows (out is unused)
-  // lag: with cross, lag-product analysis (sdft_lag_sum_n) -- forward_lag_sum_kernel sums X[t] conj(X[t - 1]) of every channel over those windows; cross has the plan's channels in the pairs' place and no items
-  // cov: covariance analysis (sdft_covariance_n) -- forward_covariance_kernel does that for all pairs of the plan's array, by blocks (out is unused)
-  // mixa: channel-mix analysis (sdft_mix_n) -- forward_mix_kernel stores the weighted sums of the plan's mix on the grid (out is unused)
-  bool forward_device(size_t n, const TD* x, size_t x_stride, fdx* out, size_t out_stride, fdx* const* rows,
-                      const FuseArgs<TD, FD>* fuse = nullptr, const EveryGrid* every = nullptr, const PowerArgs<FD>* power = nullptr,
-                      const PowerSumArgs<FD>* psum = nullptr, const FilterbankArgs<FD>* fbk = nullptr,
-                      const CrossSumArgs<FD>* cross = nullptr, const CovarianceArgs<FD>* cov = nullptr, const MixArgs<FD>* mixa = nullptr, int peak = -1, bool lag = false)
+  // What a forward call computes: one kind, and that kind's arguments (which the caller keeps alive for the call).  A
+  // default-constructed bundle is the plain analysis: every row to out / rows.  The kinds from EVERY on carry the number of the
+  // kernel that serves them (logic::ForwardKernel, option "last_kernel"); all but EVERY leave `out` unused.
+  // FUSE: the fused call (process_n) -- synthesis in the same launch
+  // EVERY: decimated analysis (sdft_every_n) -- only the rows of that grid are stored, by forward_every_kernel
+  // POWER: power-spectrogram analysis (sdft_power_n) -- forward_power_kernel stores |X|^2 of its band on its grid
+  // POWER_SUM: pooled power analysis (sdft_power_sum_n) -- forward_pooled_power_kernel sums it over the grid's windows
+  // POWER_PEAK: peak-hold analysis (sdft_power_peak_n) -- forward_power_peak_kernel holds its largest (hold 0) or smallest (hold 1) over those windows; psum as POWER_SUM's
+  // FILTERBANK: filterbank analysis (sdft_filterbank_n) -- forward_filterbank_kernel stores the band sums of the plan's filterbank
+  // CROSS_SUM: cross-spectrum analysis (sdft_cross_sum_n) -- forward_cross_sum_kernel sums A conj(B) of the plan's pairs over the grid's windows
+  // LAG_SUM: lag-product analysis (sdft_lag_sum_n) -- forward_lag_sum_kernel sums X[t] conj(X[t - 1]) of every channel over those windows; cross has the plan's channels in the pairs' place and no items
+  // COVARIANCE: covariance analysis (sdft_covariance_n) -- forward_covariance_kernel does that for all pairs of the plan's array, by blocks
+  // MIX: channel-mix analysis (sdft_mix_n) -- forward_mix_kernel stores the weighted sums of the plan's mix on the grid
+  struct ForwardCall
+  {
+    enum Kind : int { PLAIN = 0, FUSE = -1, EVERY = logic::FK_EVERY, POWER = logic::FK_POWER, POWER_SUM = logic::FK_POWER_SUM, FILTERBANK = logic::FK_FILTERBANK,
+                      CROSS_SUM = logic::FK_CROSS_SUM, COVARIANCE = logic::FK_COVARIANCE, MIX = logic::FK_MIX, POWER_PEAK = logic::FK_POWER_PEAK, LAG_SUM = logic::FK_LAG_SUM };
+    Kind kind = PLAIN;
+    int hold = 0;                                            // POWER_PEAK
+    const FuseArgs<TD, FD>* fuse = nullptr;                  // FUSE
+    const EveryGrid* every = nullptr;                        // EVERY
+    const PowerArgs<FD>* power = nullptr;                    // POWER
+    const PowerSumArgs<FD>* psum = nullptr;                  // POWER_SUM, POWER_PEAK
+    const FilterbankArgs<FD>* fbk = nullptr;                 // FILTERBANK
+    const CrossSumArgs<FD>* cross = nullptr;                 // CROSS_SUM, LAG_SUM
+    const CovarianceArgs<FD>* cov = nullptr;                 // COVARIANCE
+    const MixArgs<FD>* mix = nullptr;                        // MIX
+    static ForwardCall of(Kind k) { ForwardCall c; c.kind = k; return c; }
+    static ForwardCall fused(const FuseArgs<TD, FD>& a) { ForwardCall c = of(FUSE); c.fuse = &a; return c; }
+    static ForwardCall decimated(const EveryGrid& a) { ForwardCall c = of(EVERY); c.every = &a; return c; }
+    static ForwardCall band_power(const PowerArgs<FD>& a) { ForwardCall c = of(POWER); c.power = &a; return c; }
+    static ForwardCall power_sum(const PowerSumArgs<FD>& a) { ForwardCall c = of(POWER_SUM); c.psum = &a; return c; }
+    static ForwardCall power_peak(const PowerSumArgs<FD>& a, int hold) { ForwardCall c = of(POWER_PEAK); c.psum = &a; c.hold = hold; return c; }
+    static ForwardCall filterbank(const FilterbankArgs<FD>& a) { ForwardCall c = of(FILTERBANK); c.fbk = &a; return c; }
+    static ForwardCall cross_sum(const CrossSumArgs<FD>& a) { ForwardCall c = of(CROSS_SUM); c.cross = &a; return c; }
+    static ForwardCall lag_sum(const CrossSumArgs<FD>& a) { ForwardCall c = of(LAG_SUM); c.cross = &a; return c; }
+    static ForwardCall covariance(const CovarianceArgs<FD>& a) { ForwardCall c = of(COVARIANCE); c.cov = &a; return c; }
+    static ForwardCall channel_mix(const MixArgs<FD>& a) { ForwardCall c = of(MIX); c.mix = &a; return c; }
+  };
+  bool forward_device(size_t n, const TD* x, size_t x_stride, fdx* out, size_t out_stride, fdx* const* rows, const ForwardCall& c = ForwardCall())
   {
     const struct { size_t cursor; int st_cur, hist_cur; bool fid_canonical; } was{cursor, st_cur, hist_cur, fid_canonical};
     auto restore = [&] { cursor = was.cursor; st_cur = was.st_cur; hist_cur = was.hist_cur; fid_canonical = was.fid_canonical; };
-    if (!forward_launch(n, x, x_stride, out, out_stride, rows, fuse, every, power, psum, fbk, cross, cov, mixa, peak, lag))
+    if (!forward_launch(n, x, x_stride, out, out_stride, rows, c))
     {
       // a launch that failed half-way (a host expression that does not compile, a grid that does not fit, an allocation)
       // must not leave the stream half-advanced: what was queued wrote the OTHER buffer set and the workspace only
@@ -621,7 +648,7 @@ class Plan
     restore();
     const long saved = opt_chain;
     opt_chain = 0;
-    const bool ok = forward_launch(n, x, x_stride, out, out_stride, rows, fuse, every, power, psum, fbk, cross, cov, mixa, peak, lag) && (hipStreamSynchronize(stream) == hipSuccess);
+    const bool ok = forward_launch(n, x, x_stride, out, out_stride, rows, c) && (hipStreamSynchronize(stream) == hipSuccess);
     opt_chain = saved;
     ++ring_recoveries;
     // a recovered call is a valid call: it goes to the warning channel (and the counter), not to the error channel, so a
@@ -635,15 +662,29 @@ class Plan
     return ok;
   }
 
-  logic::ForwardQuery forward_query(size_t n, const fdx* out, size_t out_stride, fdx* const* rows, const FuseArgs<TD, FD>* fuse, const EveryGrid* every,
-                                   const PowerArgs<FD>* power, const PowerSumArgs<FD>* psum, const FilterbankArgs<FD>* fbk, const CrossSumArgs<FD>* cross,
-                                   const CovarianceArgs<FD>* cov, const MixArgs<FD>* mixa, int peak, bool lag) const
+  logic::ForwardQuery forward_query(size_t n, const fdx* out, size_t out_stride, fdx* const* rows, const ForwardCall& c) const
   {
     logic::ForwardQuery q;
     q.n = n; q.nbins = nbins; q.channels = channels; q.fd_bytes = sizeof(FD); q.fdx_bytes = sizeof(fdx);
     q.window = window; q.compute_units = compute_units; q.cursor = cursor; q.exact = carry_mode == CARRY_EXACT; q.fid_canonical = fid_canonical;
-    q.fuse = fuse != nullptr; q.fuse_store = fuse && fuse->store; q.reference_order = fuse && wants_reference_order(); q.coeff_ready = coeff_ready;
-    q.every = every != nullptr; q.power = power != nullptr; q.power_every = power ? (size_t)power->every : fbk ? (size_t)fbk->every : mixa ? (size_t)mixa->every : 1; q.power_sum = psum != nullptr && peak < 0; q.power_peak = psum != nullptr && peak >= 0; q.filterbank = fbk != nullptr; q.cross_sum = cross != nullptr && !lag; q.lag_sum = cross != nullptr && lag; q.cross_items = cross ? cross->nitems : cov ? cov->nitems : mixa ? mixa->nitems : 0; q.covariance = cov != nullptr; q.mix = mixa != nullptr; q.row_pointers = rows != nullptr; q.out = reinterpret_cast<uintptr_t>(out); q.out_stride = out_stride;
+    q.fuse = c.kind == ForwardCall::FUSE;
+    q.fuse_store = q.fuse && c.fuse->store;
+    q.reference_order = q.fuse && wants_reference_order();
+    q.coeff_ready = coeff_ready;
+    q.every = c.kind == ForwardCall::EVERY;
+    q.power = c.kind == ForwardCall::POWER;
+    q.power_sum = c.kind == ForwardCall::POWER_SUM;
+    q.power_peak = c.kind == ForwardCall::POWER_PEAK;
+    q.filterbank = c.kind == ForwardCall::FILTERBANK;
+    q.cross_sum = c.kind == ForwardCall::CROSS_SUM;
+    q.lag_sum = c.kind == ForwardCall::LAG_SUM;
+    q.covariance = c.kind == ForwardCall::COVARIANCE;
+    q.mix = c.kind == ForwardCall::MIX;
+    q.power_every = q.power ? (size_t)c.power->every : q.filterbank ? (size_t)c.fbk->every : q.mix ? (size_t)c.mix->every : 1;
+    q.cross_items = c.cross ? c.cross->nitems : q.covariance ? c.cov->nitems : q.mix ? c.mix->nitems : 0;
+    q.row_pointers = rows != nullptr;
+    q.out = reinterpret_cast<uintptr_t>(out);
+    q.out_stride = out_stride;
     q.analysis_batch = calls.analysis_batch; q.pipe_wanted = pipe_wanted(nullptr); q.prev_out = prev_out;
     q.rows_kernel = opt_rows_kernel; q.row_slots_max = opt_row_slots_max; q.interior = opt_interior; q.chunk = opt_chunk; q.self = opt_self;
     q.fused = opt_fused; q.fold = opt_fold; q.fft_carry = opt_fft_carry; q.hop_kernel = opt_hop_kernel; q.chain = opt_chain; q.chain_L = opt_chain_L;
@@ -654,22 +695,19 @@ class Plan
 
   // The route (logic::forward_route) decides; this runs it: the hop and self-carried routes in a launch of their own, every
   // other route as delta -> carries -> forward
-  bool forward_launch(size_t n, const TD* x, size_t x_stride, fdx* out, size_t out_stride, fdx* const* rows,
-                      const FuseArgs<TD, FD>* fuse = nullptr, const EveryGrid* every = nullptr, const PowerArgs<FD>* power = nullptr,
-                      const PowerSumArgs<FD>* psum = nullptr, const FilterbankArgs<FD>* fbk = nullptr,
-                      const CrossSumArgs<FD>* cross = nullptr, const CovarianceArgs<FD>* cov = nullptr, const MixArgs<FD>* mixa = nullptr, int peak = -1, bool lag = false)
+  bool forward_launch(size_t n, const TD* x, size_t x_stride, fdx* out, size_t out_stride, fdx* const* rows, const ForwardCall& c)
   {
     if (n == 0 || nbins == 0) return true;
     SDFT_TRY(hipSetDevice(device));
     flag_pending = false;                                    // only the hop kernel signals its completion
-    calls.on_analysis(fuse != nullptr);                      // (which kind of host is calling: logic::CallPattern)
-    const logic::ForwardRoute r = logic::forward_route(forward_query(n, out, out_stride, rows, fuse, every, power, psum, fbk, cross, cov, mixa, peak, lag), [this] { return gate_ok(); });
+    calls.on_analysis(c.kind == ForwardCall::FUSE);          // (which kind of host is calling: logic::CallPattern)
+    const logic::ForwardRoute r = logic::forward_route(forward_query(n, out, out_stride, rows, c), [this] { return gate_ok(); });
     pipe_this = r.pipelined;
     if (r.out.hi) prev_out = r.out;
     last_kernel = r.kernel; last_chunks = r.chunks; last_chunk_len = r.len; last_tiles = r.tiles; last_interior = r.interior;
     last_segments = r.segments; last_fused = r.fused; last_self = r.self; last_prefix = r.prefix; last_chain = r.carry == logic::CARRY_RELAY ? 3 : 0;
     if (r.kernel == logic::FK_HOP) { if (!pipe_join()) return false; return forward_hop(n, x, x_stride, out, out_stride, rows); }
-    if (r.self || r.prefix) return forward_self(n, x, x_stride, out, out_stride, r.chunks, r.len, fuse, r.prefix);
+    if (r.self || r.prefix) return forward_self(n, x, x_stride, out, out_stride, r.chunks, r.len, c, r.prefix);
     if (!pipe_join()) return false;
 
     // workspace
@@ -692,7 +730,7 @@ class Plan
     }
 
     DeltaIn<TD, FD> din;
-    if (!forward_delta(r, n, x, x_stride, din) || !forward_carries(r, n, din) || !forward_rows_stage(r, n, out, out_stride, rows, fuse, every, power, psum, fbk, cross, cov, mixa, peak, lag)) return false;
+    if (!forward_delta(r, n, x, x_stride, din) || !forward_carries(r, n, din) || !forward_rows_stage(r, n, out, out_stride, rows, c)) return false;
 
     // fid stays on the canonical rotation sequence unless this call seeded chunks from the closed-form
     // table; a call that crosses the roll-over with serial fid arithmetic puts it back
@@ -847,41 +885,42 @@ class Plan
   }
   // K1: the rows, one launch per time segment (the new state goes to the other buffer set: the one a call started from survives
   // it, see forward_device)
-  bool forward_rows_stage(const logic::ForwardRoute& r, size_t n, fdx* out, size_t out_stride, fdx* const* rows,
-                          const FuseArgs<TD, FD>* fuse, const EveryGrid* every, const PowerArgs<FD>* power, const PowerSumArgs<FD>* psum,
-                          const FilterbankArgs<FD>* fbk, const CrossSumArgs<FD>* cross, const CovarianceArgs<FD>* cov, const MixArgs<FD>* mixa, int peak, bool lag)
+  bool forward_rows_stage(const logic::ForwardRoute& r, size_t n, fdx* out, size_t out_stride, fdx* const* rows, const ForwardCall& c)
   {
+    using K = ForwardCall;
+    const FuseArgs<TD, FD>* const fuse = c.fuse;
     const size_t nb = nbins;
     const long chunks = r.chunks, segments = r.segments;
-    // cross-spectrum analysis: the workspace of the windows a chunk boundary cuts (grown on demand, kept by the plan); the work
-    // items take the channels' place in the launch
+    // cross-spectrum and lag-product analysis: the workspace of the windows a chunk boundary cuts (grown on demand, kept by the
+    // plan); the work items take the channels' place in the launch
     CrossSumArgs<FD> cs{};
-    if (cross)
+    if (c.cross)
     {
-      cs = *cross;
+      cs = *c.cross;
       if (!d_cross_ws.reserve(logic::cross_sum_workspace(cs.nitems, (size_t)chunks, cs.nbins_out))) return false;
       cs.ws = chunks > 1 ? d_cross_ws.p : nullptr;
     }
     // covariance analysis: likewise, one workspace slot per output index
     CovarianceArgs<FD> cv{};
-    if (cov)
+    if (c.cov)
     {
-      cv = *cov;
+      cv = *c.cov;
       if (!d_cov_ws.reserve(logic::covariance_workspace(cv.nch, (size_t)chunks, cv.nbins_out))) return false;
       cv.ws = chunks > 1 ? d_cov_ws.p : nullptr;
     }
-    const size_t launch_channels = cross ? cs.nitems : cov ? cv.nitems : mixa ? mixa->nitems : channels;
-    // pooled power analysis: the workspace of the windows a chunk boundary cuts (grown on demand, kept by the plan)
+    const size_t launch_channels = c.cross ? cs.nitems : c.cov ? cv.nitems : c.mix ? c.mix->nitems : channels;
+    // pooled power and peak-hold analysis: the workspace of the windows a chunk boundary cuts (grown on demand, kept by the plan)
     PowerSumArgs<FD> ps{};
-    if (psum)
+    if (c.psum)
     {
-      ps = *psum;
+      ps = *c.psum;
       if (!d_psum_ws.reserve(logic::power_sum_workspace(channels, (size_t)chunks, ps.nbins_out))) return false;
       ps.ws = chunks > 1 ? d_psum_ws.p : nullptr;
     }
     // filterbank analysis: the workspace of the bands a tile boundary cuts, [channels][rows of a launch][slots] (likewise); the
     // chunks go in launches whose rows keep it within its bound (logic::filterbank_next_span)
     FilterbankArgs<FD> fb{};
+    const FilterbankArgs<FD>* const fbk = c.fbk;
     const size_t fb_rows = fbk ? logic::filterbank_segment_rows(channels, fbk->nslots, sizeof(FD)) : 0;
     if (fbk)
     {
@@ -931,16 +970,19 @@ class Plan
       if (segments > 1) SDFT_TRY(hipStreamWaitEvent(stream, seg_events[sg], 0));      // (flow mode: the kernel waits chunk by chunk)
       const unsigned long long blocks = (fa.total_waves + kWavesPerBlock - 1) / kWavesPerBlock;
       const unsigned threads = (unsigned)(row_waves() * kWave);
-      if (fuse)
+      switch (c.kind)
       {
+      case K::FUSE:
         // rows never leave the workgroup: synthesis in the same launch (caller checked rows_kernel_ok())
         if (r.folded) { if (!launch_process(fa, *fuse, (unsigned)groups, r.fused)) return false; }
         else if (r.kernel != logic::FK_ROWS) { set_error("sdft_hip_process_n", "rows of this length are fused in the folded form only"); return false; }
         else if (!launch_syn(fa, *fuse, (unsigned)groups, threads, r.fused && !exact_order, exact_order)) return false;
-      }
-      else if (r.kernel == logic::FK_ROWS) launch_forward_rows(fa, (unsigned)groups, threads, r.fused, r.rows_f32);
-      else if (fbk)
-      {
+        break;
+      case K::PLAIN:
+        if (r.kernel == logic::FK_ROWS) launch_forward_rows(fa, (unsigned)groups, threads, r.fused, r.rows_f32);
+        else launch_forward(fa, (unsigned)blocks);
+        break;
+      case K::FILTERBANK:
         for (long ja = j0; ja < j1;)
         {
           const logic::FilterbankSpan sp = logic::filterbank_next_span(ja, j1, r.len, r.shift, n, (size_t)fb.every, (size_t)fb.first, fb_rows);
@@ -957,36 +999,29 @@ class Plan
           if (fb.nsplits && sp.rows && !launch_filterbank_rows(fb)) return false;   // the split bands of these rows, before the next launch reuses the workspace
           ja = sp.jb;
         }
+        break;
+      case K::LAG_SUM: if (!grid_fits(blocks)) return false; launch_forward_lag_sum(fa, cs, (unsigned)blocks); break;
+      case K::CROSS_SUM: if (!grid_fits(blocks)) return false; launch_forward_cross_sum(fa, cs, (unsigned)blocks); break;
+      case K::COVARIANCE: if (!grid_fits(blocks)) return false; if (!launch_forward_covariance(fa, cv, (unsigned)blocks)) return false; break;
+      case K::MIX: if (!grid_fits(blocks)) return false; if (!launch_forward_mix(fa, *c.mix, (unsigned)blocks)) return false; break;
+      case K::POWER_PEAK: if (!grid_fits(blocks)) return false; launch_forward_power_peak(fa, ps, (unsigned)blocks, c.hold); break;
+      case K::POWER_SUM: if (!grid_fits(blocks)) return false; launch_forward_power_sum(fa, ps, (unsigned)blocks); break;
+      case K::POWER: if (!grid_fits(blocks)) return false; launch_forward_power(fa, *c.power, (unsigned)blocks); break;
+      case K::EVERY: if (!grid_fits(blocks)) return false; launch_forward_every(fa, *c.every, (unsigned)blocks); break;
       }
-      else if (cross && lag) { if (!grid_fits(blocks)) return false; launch_forward_lag_sum(fa, cs, (unsigned)blocks); }
-      else if (cross) { if (!grid_fits(blocks)) return false; launch_forward_cross_sum(fa, cs, (unsigned)blocks); }
-      else if (cov) { if (!grid_fits(blocks)) return false; if (!launch_forward_covariance(fa, cv, (unsigned)blocks)) return false; }
-      else if (mixa) { if (!grid_fits(blocks)) return false; if (!launch_forward_mix(fa, *mixa, (unsigned)blocks)) return false; }
-      else if (psum && peak >= 0) { if (!grid_fits(blocks)) return false; launch_forward_power_peak(fa, ps, (unsigned)blocks, peak); }
-      else if (psum) { if (!grid_fits(blocks)) return false; launch_forward_power_sum(fa, ps, (unsigned)blocks); }
-      else if (power) { if (!grid_fits(blocks)) return false; launch_forward_power(fa, *power, (unsigned)blocks); }
-      else if (every) { if (!grid_fits(blocks)) return false; launch_forward_every(fa, *every, (unsigned)blocks); }
-      else launch_forward(fa, (unsigned)blocks);
       SDFT_TRY(hipGetLastError());
     }
     SDFT_TRY(hipGetLastError());
-    if (psum && chunks > 1)
+    // the rows a chunk boundary cut, from the workspace: per channel for the pooled power and the peak-hold call (which holds instead
+    // of adding); per pair for the cross-spectrum, the lag-product (its pairs are the plan's channels) and the covariance call,
+    // whose complex sums over nbins_out bins are real sums over 2 * nbins_out numbers -- the pooled power call's adder
+    if (chunks > 1 && (c.psum || c.cross || c.cov))
     {
-      if (!(peak >= 0 ? launch_peak_rows(ps, n, chunks, r.len, r.shift, channels, peak) : launch_power_sum_rows(ps, n, chunks, r.len, r.shift, channels))) return false;
-      SDFT_TRY(hipGetLastError());
-    }
-    if (cross && chunks > 1)
-    {
-      // (complex sums over nbins_out bins are real sums over 2 * nbins_out numbers: the pooled power call's adder, pairs for channels;
-      // the lag-product call's pairs are the plan's channels)
-      const PowerSumArgs<FD> pieces{cs.row0, cs.row0_stride, cs.rest, cs.rest_stride, cs.ws, cs.every, cs.first, cs.bin0, 2u * cs.nbins_out};
-      if (!launch_power_sum_rows(pieces, n, chunks, r.len, r.shift, cs.npairs)) return false;
-      SDFT_TRY(hipGetLastError());
-    }
-    if (cov && chunks > 1)
-    {
-      const PowerSumArgs<FD> pieces{cv.row0, cv.row0_stride, cv.rest, cv.rest_stride, cv.ws, cv.every, cv.first, cv.bin0, 2u * cv.nbins_out};
-      if (!launch_power_sum_rows(pieces, n, chunks, r.len, r.shift, cv.npairs)) return false;
+      const PowerSumArgs<FD> pieces = c.psum ? ps
+                                    : c.cross ? PowerSumArgs<FD>{cs.row0, cs.row0_stride, cs.rest, cs.rest_stride, cs.ws, cs.every, cs.first, cs.bin0, 2u * cs.nbins_out}
+                                              : PowerSumArgs<FD>{cv.row0, cv.row0_stride, cv.rest, cv.rest_stride, cv.ws, cv.every, cv.first, cv.bin0, 2u * cv.nbins_out};
+      const size_t units = c.psum ? channels : c.cross ? cs.npairs : cv.npairs;
+      if (!(c.kind == K::POWER_PEAK ? launch_peak_rows(pieces, n, chunks, r.len, r.shift, units, c.hold) : launch_power_sum_rows(pieces, n, chunks, r.len, r.shift, units))) return false;
       SDFT_TRY(hipGetLastError());
     }
     if (r.flow) SDFT_TRY(hipStreamWaitEvent(stream, seg_events[0], 0));          // the call ends when both launches have
@@ -1162,8 +1197,9 @@ class Plan
   // prefix: the folded cells of every chunk come from one pre-pass launch (prefix_cells_kernel, logic::ForwardRoute::prefix);
   // one stream, never fused
   bool forward_self(size_t n, const TD* x, size_t x_stride, fdx* out, size_t out_stride, long chunks, long len,
-                    const FuseArgs<TD, FD>* fuse, bool prefix = false)
+                    const ForwardCall& c, bool prefix = false)
   {
+    const FuseArgs<TD, FD>* const fuse = c.fuse;             // (the plain analysis or the fused call: no other kind has the form)
     const size_t nb = nbins, span = 2 * nbins;
     SelfArgs<TD, FD> sa;
     sa.x = x; sa.x_stride = x_stride;

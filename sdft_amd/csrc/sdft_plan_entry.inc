@@ -106,88 +106,154 @@
     return true;
   }
 
-  // decimated analysis (sdft_hip_sdft_every_n): the rows sdft_n would write at the call's samples first, first + every, ...
-  // < n, dense [channels][rows][N]; the stream state afterwards is the one sdft_n leaves.  `rows` receives the row count.
-  // Never resident, pipelined or fused: whatever is in flight is retired / joined first, then one forward_launch on the
-  // plan's stream (forward_every_kernel).  Host memory goes through device scratch and the plan's pinned copy path, in
-  // time segments that keep both scratch buffers within stage_bytes.
-  bool sdft_every_n(size_t n, const TD* x, size_t every, size_t first, fdx* dfts, size_t& rows)
+  // ---- grid analysis calls: sdft_every_n and its eight siblings -----------------------------------------------------------------
+  // What the nine share.  The stream state after a call is the one sdft_n leaves on the same samples.  A call is never resident,
+  // pipelined or fused: whatever is in flight is retired / joined first, then one forward call on the plan's stream with the
+  // call's own kernel (ForwardCall).  `rows` receives the row count.  Device samples and a device output take that one call; host
+  // memory goes through device scratch in time segments of at most logic::grid_segment samples, each segment a call of its own
+  // under the streaming contract, with its own first.
+  // The every-grid calls (every, power, filterbank, mix) keep the rows of the samples first, first + every, ... < n; a segment
+  // keeps the rows of the grid that fall into it.  The pooled calls (power_sum, power_peak, cross_sum, lag_sum, covariance) write
+  // one row per window the grid cuts the call into (logic::power_sum_window), row 0 the head window [0, first) when first > 0; a
+  // segment that starts inside a window has a head row of its own, which is kept apart (the call's head buffer) and joined into
+  // the row the segment before it ended with -- on the host for a host buffer, by a small kernel for a device buffer.
+  // The output is dense [units][rows][unit_row] numbers: the units are the plan's channels, or the pairs / outputs a call has
+  // installed.  Rows on their way to a host buffer go through staged_segments' own scratch and copy (per channel), or -- where
+  // the units are not the channels, or the kernel re-reads what it wrote -- through a stage buffer of the call's and out unit by unit.
+
+  // one forward call of a grid analysis -- the whole call, or a segment of it on device scratch -- with its grid
+  struct GridPiece { size_t m; const TD* td; size_t td_stride; EveryGrid grid; };
+
+  // The argument checks of a grid call, in the order a host sees them win: the grid, the band (has_band: the call takes one), the
+  // call's own (refused: its message, or nullptr), the output.  pooled: the rows are windows, which the call "writes".
+  bool grid_args(const char* fn, size_t n, size_t every, size_t first, bool has_band, size_t bin0, size_t nbins_out, const char* refused,
+                 bool pooled, const void* out, const char* out_name, size_t& rows)
   {
-    static const char* fn = "sdft_hip_sdft_every_n";
     rows = 0;
     if (every == 0) { set_error(fn, "every must be at least 1"); return false; }
-    rows = logic::every_rows(n, every, first);
-    if (rows > 0 && !dfts) { set_error(fn, "dfts is NULL but the call keeps rows"); return false; }
-    if (n == 0 || nbins == 0) return true;
-    if (every == 1 && first == 0) return sdft_n(n, x, dfts);      // every row: the analysis itself
-    if (!bind()) return false;
-    if (!pipe_join()) return false;
+    if (has_band && nbins_out == 0) { set_error(fn, "nbins must be at least 1"); return false; }
+    if (has_band && !logic::power_band_ok(nbins, bin0, nbins_out)) { set_error(fn, "the band bin0 ... bin0 + nbins - 1 does not lie within the plan's bins"); return false; }
+    if (refused) { set_error(fn, refused); return false; }
+    rows = pooled ? logic::power_sum_rows(n, every, first) : logic::every_rows(n, every, first);
+    if (rows > 0 && !out) { set_error(fn, (std::string(out_name) + " is NULL but the call " + (pooled ? "writes" : "keeps") + " rows").c_str()); return false; }
+    return true;
+  }
+  static bool grid_ready() { return true; }                  // (a call with nothing to re-upload)
+
+  // The every-grid calls, after grid_args.  ready(): what the call prepares once the plan is bound and joined (tables a test hook
+  // invalidated).  launch(piece, at, at_rows): builds the call's arguments for the rows at `at` ([units][at_rows][unit_row] of T)
+  // and runs forward_device.  stage: the call's own stage buffer (see above), nullptr: staged_segments' (units == channels).
+  template <class T, class Ready, class Launch>
+  bool every_grid_call(size_t n, const TD* x, size_t every, size_t first, T* out, size_t rows, size_t units, size_t unit_row,
+                       Ready&& ready, Launch&& launch, DevBuf<T>* stage = nullptr)
+  {
+    if (n == 0) return true;
+    if (!bind() || !pipe_join() || !ready()) return false;
     if (every > n) every = n;                                // (the same grid: at most one row; keeps first + k * every in range)
-    const size_t nb = nbins;
     const bool xd = on_device(x);
-    const bool od = rows == 0 || on_device(dfts);
-    const size_t row_bytes = channels * nb * sizeof(fdx);
-    if (xd && od)
-    {
-      const EveryGrid g{(unsigned long long)every, (unsigned long long)first};
-      return forward_device(n, x, n, dfts, rows * nb, nullptr, nullptr, &g) && finish(rows * row_bytes);
-    }
-    // host memory: segments of at most seg samples (rows kept and samples within stage_bytes), each one forward launch on device scratch
-    size_t seg = n;
-    if (!od) seg = std::min(seg, logic::stage_rows(n, row_bytes, stage_bytes) * every);
-    if (!xd) seg = std::min(seg, std::max<size_t>((size_t)logic::kHopSamples, logic::stage_rows(n, channels * sizeof(TD), stage_bytes)));
-    return staged_segments(n, seg, StagedCall{true, const_cast<TD*>(x), !xd, dfts, !od, rows, (seg + every - 1) / every, bins_row_bytes()}, [&](Segment& s) {
+    const bool od = rows == 0 || on_device(out);
+    const size_t row_bytes = units * unit_row * sizeof(T);
+    if (xd && od) return launch(GridPiece{n, x, n, {every, first}}, out, rows) && finish(rows * row_bytes);
+    const size_t seg = logic::grid_segment(n, every, first, row_bytes, channels * sizeof(TD), stage_bytes, xd, od, false);
+    const size_t seg_rows_max = (seg + every - 1) / every;
+    if (stage && !od && !stage->reserve(units * seg_rows_max * unit_row)) return false;
+    const StagedCall c{true, const_cast<TD*>(x), !xd, stage ? nullptr : out, !stage && !od, rows, seg_rows_max, unit_row * sizeof(T)};
+    return staged_segments(n, seg, c, [&](Segment& s) {
       const size_t f = logic::every_first_from(s.t, every, first);
-      s.rows = logic::every_rows(s.m, every, f);
-      s.row0 = s.rows ? (s.t + f - first) / every : 0;       // the segment's first row in the call's grid
-      if (od) s.mat = s.rows ? dfts + s.row0 * nb : nullptr;
-      else s.mat_rows = s.rows;
-      const EveryGrid g{(unsigned long long)every, (unsigned long long)f};
-      return forward_device(s.m, s.td, s.td_stride, s.bins(), s.mat_rows * nb, nullptr, nullptr, &g);
+      const size_t kept = logic::every_rows(s.m, every, f);
+      const size_t r0 = kept ? (s.t + f - first) / every : 0; // the segment's first row in the call's grid
+      s.row0 = r0; s.rows = stage ? 0 : kept;                // (a call with a stage buffer leaves staged_segments nothing to copy)
+      T* const at = od ? (kept ? out + r0 * unit_row : nullptr) : stage ? stage->p : static_cast<T*>(s.mat);
+      if (!launch(GridPiece{s.m, s.td, s.td_stride, {every, f}}, at, od ? rows : kept)) return false;
+      for (size_t u = 0; u < units && stage && !od && kept; ++u)
+        if (!to_host(out + (u * rows + r0) * unit_row, stage->p + u * kept * unit_row, kept * unit_row * sizeof(T))) return false;
+      return true;
     });
   }
 
-  // power-spectrogram analysis (sdft_hip_sdft_power_n): re^2 + im^2 of the bins [bin0, bin0 + nbins_out) of the rows sdft_n would
-  // write at the call's samples first, first + every, ... < n, dense [channels][rows][nbins_out] real numbers; the stream state
-  // afterwards is the one sdft_n leaves (bins outside the band step all the same).  The call is sdft_every_n's in every other respect:
-  // never resident, pipelined or fused, one forward launch on the plan's stream -- forward_power_kernel, for the full grid and the
-  // full band too --, host memory in time segments through device scratch.
+  // The pooled calls, after grid_args; ready() as above.  launch(piece, row0, row0_stride, rest, rest_stride): builds the call's
+  // arguments for a first row at row0 and the rows after it at rest, and runs forward_device.  head: the call's head buffer.
+  // hold: how a head row joins the row it completes -- kJoinAdd: it is added (pooled_power_add_kernel, + on the host); 0 / 1: the
+  // peak-hold call's rule (peak_join_kernel, logic::peak_hold), which is associative and commutative: there, how the segments cut
+  // a window does not show in the bits.
+  static constexpr int kJoinAdd = -1;
+  template <class Ready, class Launch>
+  bool pooled_grid_call(size_t n, const TD* x, size_t every, size_t first, FD* out, size_t rows, size_t units, size_t unit_row,
+                        DevBuf<FD>& head, DevBuf<FD>* stage, int hold, Ready&& ready, Launch&& launch)
+  {
+    if (n == 0) return true;
+    if (!bind() || !pipe_join() || !ready()) return false;
+    if (every > n) every = n;                                // (the same windows; keeps first + k * every in range)
+    const bool xd = on_device(x);
+    const bool od = on_device(out);
+    const size_t row_bytes = units * unit_row * sizeof(FD);
+    const size_t stride = logic::power_channel_stride(rows, unit_row);
+    if (xd && od) return launch(GridPiece{n, x, n, {every, first}}, out, stride, out + unit_row, stride) && finish(rows * row_bytes);
+    const size_t seg = logic::grid_segment(n, every, first, row_bytes, channels * sizeof(TD), stage_bytes, xd, od, true);
+    const size_t seg_rows_max = (seg + every - 1) / every + 1;
+    if (stage && !od && !stage->reserve(units * seg_rows_max * unit_row)) return false;
+    std::vector<FD> head_host;                               // host buffers: a segment's head rows on their way to the rows they complete
+    const StagedCall c{true, const_cast<TD*>(x), !xd, stage ? nullptr : out, !stage && !od, rows, seg_rows_max, unit_row * sizeof(FD)};
+    return staged_segments(n, seg, c, [&](Segment& s) {
+      const size_t f = logic::every_first_from(s.t, every, first);
+      const logic::PowerSumWindow w0 = logic::power_sum_window(s.t, n, every, first);      // of the segment's row 0 in the call
+      const bool joins = w0.begin < s.t;                     // row 0 is a head: it completes row w0.row of the call
+      const size_t kept = logic::power_sum_rows(s.m, every, f) - (joins ? 1 : 0);
+      if (joins && !head.reserve(units * unit_row)) return false;
+      const size_t r0 = w0.row + (joins ? 1 : 0);            // the segment's first row of its own
+      s.row0 = r0; s.rows = stage ? 0 : kept;                // (a call with a stage buffer leaves staged_segments nothing to copy)
+      FD* const at = od ? out + r0 * unit_row : stage ? stage->p : static_cast<FD*>(s.mat);      // scratch: [units][kept][unit_row]
+      const size_t at_stride = od ? stride : kept * unit_row;
+      const GridPiece piece{s.m, s.td, s.td_stride, {every, f}};
+      if (!(joins ? launch(piece, head.p, unit_row, at, at_stride) : launch(piece, at, at_stride, at + unit_row, at_stride))) return false;
+      FD* const joined = out + w0.row * unit_row;            // (of unit 0) the row a head completes
+      if (od)
+      {
+        if (!joins) return true;
+        const unsigned long long threads = (unsigned long long)units * unit_row;
+        const dim3 blocks((unsigned)((threads + kBlock - 1) / kBlock));
+        if (hold == kJoinAdd) hipLaunchKernelGGL((pooled_power_add_kernel<FD>), blocks, dim3(kBlock), 0, stream, joined, stride, head.p, (unsigned)unit_row, (unsigned)units);
+        else hipLaunchKernelGGL((peak_join_kernel<FD>), blocks, dim3(kBlock), 0, stream, joined, stride, head.p, (unsigned)unit_row, (unsigned)units, hold);
+        SDFT_TRY(hipGetLastError());
+        return true;
+      }
+      for (size_t u = 0; u < units && stage && kept; ++u)
+        if (!to_host(out + u * stride + r0 * unit_row, stage->p + u * kept * unit_row, kept * unit_row * sizeof(FD))) return false;
+      if (!joins) return true;
+      head_host.resize(units * unit_row);
+      if (!to_host(head_host.data(), head.p, head_host.size() * sizeof(FD))) return false;
+      SDFT_TRY(hipStreamSynchronize(stream));
+      for (size_t u = 0; u < units; ++u)
+        for (size_t k = 0; k < unit_row; ++k)
+        {
+          FD& to = joined[u * stride + k];
+          to = hold == kJoinAdd ? to + head_host[u * unit_row + k] : logic::peak_hold(to, head_host[u * unit_row + k], hold);
+        }
+      return true;
+    });
+  }
+
+  // decimated analysis (sdft_hip_sdft_every_n): the rows sdft_n would write on the grid, dense [channels][rows][N]
+  // (forward_every_kernel); the full grid is the analysis itself
+  bool sdft_every_n(size_t n, const TD* x, size_t every, size_t first, fdx* dfts, size_t& rows)
+  {
+    if (!grid_args("sdft_hip_sdft_every_n", n, every, first, false, 0, 0, nullptr, false, dfts, "dfts", rows)) return false;
+    if (n == 0 || nbins == 0) return true;
+    if (every == 1 && first == 0) return sdft_n(n, x, dfts);      // every row: the analysis itself
+    return every_grid_call(n, x, every, first, dfts, rows, channels, nbins, grid_ready, [&](const GridPiece& p, fdx* at, size_t at_rows) {
+      return forward_device(p.m, p.td, p.td_stride, at, at_rows * nbins, nullptr, ForwardCall::decimated(p.grid));
+    });
+  }
+
+  // power-spectrogram analysis (sdft_hip_sdft_power_n): re^2 + im^2 of the bins [bin0, bin0 + nbins_out) of the rows of the grid,
+  // dense [channels][rows][nbins_out] real numbers (bins outside the band step all the same) -- forward_power_kernel, for the
+  // full grid and the full band too
   bool sdft_power_n(size_t n, const TD* x, size_t every, size_t first, size_t bin0, size_t nbins_out, FD* power, size_t& rows)
   {
-    static const char* fn = "sdft_hip_sdft_power_n";
-    rows = 0;
-    if (every == 0) { set_error(fn, "every must be at least 1"); return false; }
-    if (nbins_out == 0) { set_error(fn, "nbins must be at least 1"); return false; }
-    if (!logic::power_band_ok(nbins, bin0, nbins_out)) { set_error(fn, "the band bin0 ... bin0 + nbins - 1 does not lie within the plan's bins"); return false; }
-    rows = logic::every_rows(n, every, first);
-    if (rows > 0 && !power) { set_error(fn, "power is NULL but the call keeps rows"); return false; }
-    if (n == 0) return true;
-    if (!bind()) return false;
-    if (!pipe_join()) return false;
-    if (every > n) every = n;                                // (the same grid: at most one row; keeps first + k * every in range)
-    const bool xd = on_device(x);
-    const bool od = rows == 0 || on_device(power);
-    const size_t row_bytes = channels * nbins_out * sizeof(FD);
-    auto band = [&](FD* out, size_t out_rows, size_t f) {
-      return PowerArgs<FD>{out, logic::power_channel_stride(out_rows, nbins_out), (unsigned long long)every, (unsigned long long)f, (unsigned)bin0, (unsigned)nbins_out};
-    };
-    if (xd && od)
-    {
-      const PowerArgs<FD> g = band(power, rows, first);
-      return forward_device(n, x, n, nullptr, 0, nullptr, nullptr, nullptr, &g) && finish(rows * row_bytes);
-    }
-    // host memory: segments of at most seg samples (rows kept and samples within stage_bytes), each one forward launch on device scratch
-    size_t seg = n;
-    if (!od) seg = std::min(seg, logic::stage_rows(n, row_bytes, stage_bytes) * every);
-    if (!xd) seg = std::min(seg, std::max<size_t>((size_t)logic::kHopSamples, logic::stage_rows(n, channels * sizeof(TD), stage_bytes)));
-    return staged_segments(n, seg, StagedCall{true, const_cast<TD*>(x), !xd, power, !od, rows, (seg + every - 1) / every, nbins_out * sizeof(FD)}, [&](Segment& s) {
-      const size_t f = logic::every_first_from(s.t, every, first);
-      s.rows = logic::every_rows(s.m, every, f);
-      s.row0 = s.rows ? (s.t + f - first) / every : 0;       // the segment's first row in the call's grid
-      if (od) s.mat = s.rows ? power + s.row0 * nbins_out : nullptr;
-      else s.mat_rows = s.rows;
-      const PowerArgs<FD> g = band(static_cast<FD*>(s.mat), s.mat_rows, f);
-      return forward_device(s.m, s.td, s.td_stride, nullptr, 0, nullptr, nullptr, nullptr, &g);
+    if (!grid_args("sdft_hip_sdft_power_n", n, every, first, true, bin0, nbins_out, nullptr, false, power, "power", rows)) return false;
+    return every_grid_call(n, x, every, first, power, rows, channels, nbins_out, grid_ready, [&](const GridPiece& p, FD* at, size_t at_rows) {
+      const PowerArgs<FD> g{at, logic::power_channel_stride(at_rows, nbins_out), p.grid.every, p.grid.first, (unsigned)bin0, (unsigned)nbins_out};
+      return forward_device(p.m, p.td, p.td_stride, nullptr, 0, nullptr, ForwardCall::band_power(g));
     });
   }
 
@@ -240,50 +306,27 @@
   size_t filterbank_bands() const { return fbank.bin0.size(); }
 
   // filterbank analysis (sdft_hip_sdft_filterbank_n): per band of the installed filterbank the sum of fl(weight * power) over the
-  // band's bins, of the rows of sdft_power_n's grid, dense [channels][rows][nbands] real numbers; state, pointers and launches as
-  // sdft_power_n: never resident, pipelined or fused, forward_filterbank_kernel on the plan's stream, then filterbank_rows_kernel
-  // for the bands a tile boundary cuts (forward_rows_stage: in as many launches as keep the workspace within its bound).  Host
-  // memory goes in time segments through device scratch.
+  // band's bins, of the rows of the grid, dense [channels][rows][nbands] real numbers -- forward_filterbank_kernel, then
+  // filterbank_rows_kernel for the bands a tile boundary cuts (forward_rows_stage: in as many launches as keep the workspace
+  // within its bound)
   bool sdft_filterbank_n(size_t n, const TD* x, size_t every, size_t first, FD* out, size_t& rows)
   {
     static const char* fn = "sdft_hip_sdft_filterbank_n";
     rows = 0;
     const size_t nbands = filterbank_bands();
     if (nbands == 0) { set_error(fn, "no filterbank is installed (sdft_hip_set_filterbank)"); return false; }
-    if (every == 0) { set_error(fn, "every must be at least 1"); return false; }
-    rows = logic::every_rows(n, every, first);
-    if (rows > 0 && !out) { set_error(fn, "out is NULL but the call keeps rows"); return false; }
+    if (!grid_args(fn, n, every, first, false, 0, 0, nullptr, false, out, "out", rows)) return false;
     last_filterbank_launches = 0;                            // (forward_rows_stage counts, over all host segments of the call)
-    if (n == 0) return true;
-    if (!bind()) return false;
-    if (!pipe_join()) return false;
-    if (fbank.interior != interior_lanes() && !upload_filterbank(fbank)) { fbank.interior = -1; return false; }   // (option "interior" changed the tiles)
-    if (every > n) every = n;                                // (the same grid: at most one row; keeps first + k * every in range)
-    const bool xd = on_device(x);
-    const bool od = rows == 0 || on_device(out);
-    const size_t row_bytes = channels * nbands * sizeof(FD);
-    const logic::FilterbankLayout& l = fbank.layout;
-    auto bank = [&](FD* to, size_t out_rows, size_t f) {
-      return FilterbankArgs<FD>{to, out_rows * nbands, nullptr, 0, 0, (unsigned long long)every, (unsigned long long)f, d_fb_pieces.p, d_fb_tile0.p,
-                                d_fb_weights.p, d_fb_splits.p, (unsigned)nbands, (unsigned)l.nslots, (unsigned)l.splits.size()};
+    auto ready = [&] {                                       // (option "interior" changed the tiles)
+      if (fbank.interior == interior_lanes() || upload_filterbank(fbank)) return true;
+      fbank.interior = -1;
+      return false;
     };
-    if (xd && od)
-    {
-      const FilterbankArgs<FD> g = bank(out, rows, first);
-      return forward_device(n, x, n, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &g) && finish(rows * row_bytes);
-    }
-    // host memory: segments of at most seg samples (rows kept and samples within stage_bytes), each one call on device scratch
-    size_t seg = n;
-    if (!od) seg = std::min(seg, logic::stage_rows(n, row_bytes, stage_bytes) * every);
-    if (!xd) seg = std::min(seg, std::max<size_t>((size_t)logic::kHopSamples, logic::stage_rows(n, channels * sizeof(TD), stage_bytes)));
-    return staged_segments(n, seg, StagedCall{true, const_cast<TD*>(x), !xd, out, !od, rows, (seg + every - 1) / every, nbands * sizeof(FD)}, [&](Segment& s) {
-      const size_t f = logic::every_first_from(s.t, every, first);
-      s.rows = logic::every_rows(s.m, every, f);
-      s.row0 = s.rows ? (s.t + f - first) / every : 0;       // the segment's first row in the call's grid
-      if (od) s.mat = s.rows ? out + s.row0 * nbands : nullptr;
-      else s.mat_rows = s.rows;
-      const FilterbankArgs<FD> g = bank(static_cast<FD*>(s.mat), s.mat_rows, f);
-      return forward_device(s.m, s.td, s.td_stride, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &g);
+    return every_grid_call(n, x, every, first, out, rows, channels, nbands, ready, [&](const GridPiece& p, FD* at, size_t at_rows) {
+      const logic::FilterbankLayout& l = fbank.layout;
+      const FilterbankArgs<FD> g{at, at_rows * nbands, nullptr, 0, 0, p.grid.every, p.grid.first, d_fb_pieces.p, d_fb_tile0.p,
+                                 d_fb_weights.p, d_fb_splits.p, (unsigned)nbands, (unsigned)l.nslots, (unsigned)l.splits.size()};
+      return forward_device(p.m, p.td, p.td_stride, nullptr, 0, nullptr, ForwardCall::filterbank(g));
     });
   }
 
@@ -296,161 +339,28 @@
     return false;
   }
 
-  // pooled power analysis (sdft_hip_sdft_power_sum_n): the sums of sdft_power_n's every == 1 powers over the windows the grid
-  // first, first + every, ... cuts the call into (logic::power_sum_window), dense [channels][rows][nbins_out] real numbers, row 0
-  // the head window [0, first) when first > 0.  State, pointers and launches as sdft_power_n: never resident, pipelined or fused,
-  // forward_pooled_power_kernel on the plan's stream, then pooled_power_rows_kernel for the windows a chunk boundary cut.
-  // Host memory goes in time segments through device scratch; each segment is a pooled call of its own under the streaming
-  // contract, with its own first: the head row of a later segment is kept apart (d_psum_head) and added to the row the segment
-  // before it ended with, on the host for a host buffer, by pooled_power_add_kernel for a device buffer.
+  // pooled power analysis (sdft_hip_sdft_power_sum_n): the sums of sdft_power_n's every == 1 powers over the windows of the grid,
+  // dense [channels][rows][nbins_out] real numbers -- forward_pooled_power_kernel, then pooled_power_rows_kernel for the windows
+  // a chunk boundary cut; head rows in d_psum_head
   bool sdft_power_sum_n(size_t n, const TD* x, size_t every, size_t first, size_t bin0, size_t nbins_out, FD* sums, size_t& rows)
   {
-    static const char* fn = "sdft_hip_sdft_power_sum_n";
-    rows = 0;
-    if (every == 0) { set_error(fn, "every must be at least 1"); return false; }
-    if (nbins_out == 0) { set_error(fn, "nbins must be at least 1"); return false; }
-    if (!logic::power_band_ok(nbins, bin0, nbins_out)) { set_error(fn, "the band bin0 ... bin0 + nbins - 1 does not lie within the plan's bins"); return false; }
-    rows = logic::power_sum_rows(n, every, first);
-    if (rows > 0 && !sums) { set_error(fn, "sums is NULL but the call writes rows"); return false; }
-    if (n == 0) return true;
-    if (!bind()) return false;
-    if (!pipe_join()) return false;
-    if (every > n) every = n;                                // (the same windows; keeps first + k * every in range)
-    const bool xd = on_device(x);
-    const bool od = on_device(sums);
-    const size_t row_bytes = channels * nbins_out * sizeof(FD);
-    auto band = [&](FD* row0, size_t row0_stride, FD* rest, size_t rest_stride, size_t f) {
-      return PowerSumArgs<FD>{row0, row0_stride, rest, rest_stride, nullptr, (unsigned long long)every, (unsigned long long)f, (unsigned)bin0, (unsigned)nbins_out};
-    };
-    const size_t stride = logic::power_channel_stride(rows, nbins_out);
-    if (xd && od)
-    {
-      const PowerSumArgs<FD> g = band(sums, stride, sums + nbins_out, stride, first);
-      return forward_device(n, x, n, nullptr, 0, nullptr, nullptr, nullptr, nullptr, &g) && finish(rows * row_bytes);
-    }
-    // host memory: segments of at most seg samples (rows written and samples within stage_bytes); where the grid allows it, of
-    // whole windows, so that no row is made of two segments
-    size_t seg = n;
-    if (!od) seg = std::min(seg, logic::stage_rows(n, row_bytes, stage_bytes) * every);
-    if (!xd) seg = std::min(seg, std::max<size_t>((size_t)logic::kHopSamples, logic::stage_rows(n, channels * sizeof(TD), stage_bytes)));
-    if (seg < n && seg > every && first % every == 0) seg -= seg % every;
-    std::vector<FD> head;                                    // host buffers: a segment's head row on its way to the row it completes
-    return staged_segments(n, seg, StagedCall{true, const_cast<TD*>(x), !xd, sums, !od, rows, (seg + every - 1) / every + 1, nbins_out * sizeof(FD)}, [&](Segment& s) {
-      const size_t f = logic::every_first_from(s.t, every, first);
-      const logic::PowerSumWindow w0 = logic::power_sum_window(s.t, n, every, first);      // of the segment's row 0 in the call
-      const bool joins = w0.begin < s.t;                     // row 0 is a head: it completes row w0.row of the call
-      const size_t seg_rows = logic::power_sum_rows(s.m, every, f), kept = seg_rows - (joins ? 1 : 0);
-      if (joins && !d_psum_head.reserve(channels * nbins_out)) return false;
-      s.row0 = w0.row + (joins ? 1 : 0); s.rows = kept;
-      PowerSumArgs<FD> g;
-      if (od)
-      {
-        FD* const at = sums + s.row0 * nbins_out;            // the segment's first row of its own
-        s.mat = at;
-        g = joins ? band(d_psum_head.p, nbins_out, at, stride, f) : band(at, stride, at + nbins_out, stride, f);
-      }
-      else
-      {
-        FD* const at = static_cast<FD*>(s.mat);              // scratch, [channels][kept][nbins_out]
-        s.mat_rows = kept;
-        g = joins ? band(d_psum_head.p, nbins_out, at, kept * nbins_out, f) : band(at, kept * nbins_out, at + nbins_out, kept * nbins_out, f);
-      }
-      if (!forward_device(s.m, s.td, s.td_stride, nullptr, 0, nullptr, nullptr, nullptr, nullptr, &g)) return false;
-      if (!joins) return true;
-      if (od)
-      {
-        const unsigned long long threads = (unsigned long long)channels * nbins_out;
-        hipLaunchKernelGGL((pooled_power_add_kernel<FD>), dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
-                           sums + w0.row * nbins_out, stride, d_psum_head.p, (unsigned)nbins_out, (unsigned)channels);
-        SDFT_TRY(hipGetLastError());
-        return true;
-      }
-      head.resize(channels * nbins_out);
-      if (!to_host(head.data(), d_psum_head.p, head.size() * sizeof(FD))) return false;
-      SDFT_TRY(hipStreamSynchronize(stream));
-      for (size_t c = 0; c < channels; ++c)
-        for (size_t k = 0; k < nbins_out; ++k) sums[c * stride + w0.row * nbins_out + k] += head[c * nbins_out + k];
-      return true;
+    if (!grid_args("sdft_hip_sdft_power_sum_n", n, every, first, true, bin0, nbins_out, nullptr, true, sums, "sums", rows)) return false;
+    return pooled_grid_call(n, x, every, first, sums, rows, channels, nbins_out, d_psum_head, nullptr, kJoinAdd, grid_ready,
+                            [&](const GridPiece& p, FD* row0, size_t row0_stride, FD* rest, size_t rest_stride) {
+      const PowerSumArgs<FD> g{row0, row0_stride, rest, rest_stride, nullptr, p.grid.every, p.grid.first, (unsigned)bin0, (unsigned)nbins_out};
+      return forward_device(p.m, p.td, p.td_stride, nullptr, 0, nullptr, ForwardCall::power_sum(g));
     });
   }
-  // peak-hold analysis (sdft_hip_sdft_power_peak_n): the largest (hold 0) or the smallest (hold 1) of sdft_power_n's every == 1 powers
-  // over the windows of sdft_power_sum_n's grid; rows, head row, output, state, pointers, launches and host segments are that
-  // call's, with forward_power_peak_kernel, peak_rows_kernel and peak_join_kernel in its kernels' places.  The head row of a later
-  // segment is combined into the row the segment before it ended with by the one rule (logic::peak_hold), which is associative and
-  // commutative: how the segments cut a window does not show in the bits.
+  // peak-hold analysis (sdft_hip_sdft_power_peak_n): the largest (hold 0) or the smallest (hold 1) of those powers over the windows
+  // of the grid; the pooled power call with forward_power_peak_kernel, peak_rows_kernel and peak_join_kernel in its kernels' places
   bool sdft_power_peak_n(size_t n, const TD* x, size_t every, size_t first, size_t bin0, size_t nbins_out, int hold, FD* peaks, size_t& rows)
   {
-    static const char* fn = "sdft_hip_sdft_power_peak_n";
-    rows = 0;
-    if (every == 0) { set_error(fn, "every must be at least 1"); return false; }
-    if (nbins_out == 0) { set_error(fn, "nbins must be at least 1"); return false; }
-    if (!logic::power_band_ok(nbins, bin0, nbins_out)) { set_error(fn, "the band bin0 ... bin0 + nbins - 1 does not lie within the plan's bins"); return false; }
-    if (!logic::peak_hold_ok(hold)) { set_error(fn, "hold must be sdft_hip_hold_max (0) or sdft_hip_hold_min (1)"); return false; }
-    rows = logic::power_sum_rows(n, every, first);
-    if (rows > 0 && !peaks) { set_error(fn, "peaks is NULL but the call writes rows"); return false; }
-    if (n == 0) return true;
-    if (!bind()) return false;
-    if (!pipe_join()) return false;
-    if (every > n) every = n;                                // (the same windows; keeps first + k * every in range)
-    const bool xd = on_device(x);
-    const bool od = on_device(peaks);
-    const size_t row_bytes = channels * nbins_out * sizeof(FD);
-    auto band = [&](FD* row0, size_t row0_stride, FD* rest, size_t rest_stride, size_t f) {
-      return PowerSumArgs<FD>{row0, row0_stride, rest, rest_stride, nullptr, (unsigned long long)every, (unsigned long long)f, (unsigned)bin0, (unsigned)nbins_out};
-    };
-    const size_t stride = logic::power_channel_stride(rows, nbins_out);
-    if (xd && od)
-    {
-      const PowerSumArgs<FD> g = band(peaks, stride, peaks + nbins_out, stride, first);
-      return forward_device(n, x, n, nullptr, 0, nullptr, nullptr, nullptr, nullptr, &g, nullptr, nullptr, nullptr, nullptr, hold) && finish(rows * row_bytes);
-    }
-    // host memory: segments of at most seg samples (rows written and samples within stage_bytes); where the grid allows it, of
-    // whole windows, so that no row is made of two segments
-    size_t seg = n;
-    if (!od) seg = std::min(seg, logic::stage_rows(n, row_bytes, stage_bytes) * every);
-    if (!xd) seg = std::min(seg, std::max<size_t>((size_t)logic::kHopSamples, logic::stage_rows(n, channels * sizeof(TD), stage_bytes)));
-    if (seg < n && seg > every && first % every == 0) seg -= seg % every;
-    std::vector<FD> head;                                    // host buffers: a segment's head row on its way to the row it completes
-    return staged_segments(n, seg, StagedCall{true, const_cast<TD*>(x), !xd, peaks, !od, rows, (seg + every - 1) / every + 1, nbins_out * sizeof(FD)}, [&](Segment& s) {
-      const size_t f = logic::every_first_from(s.t, every, first);
-      const logic::PowerSumWindow w0 = logic::power_sum_window(s.t, n, every, first);      // of the segment's row 0 in the call
-      const bool joins = w0.begin < s.t;                     // row 0 is a head: it completes row w0.row of the call
-      const size_t seg_rows = logic::power_sum_rows(s.m, every, f), kept = seg_rows - (joins ? 1 : 0);
-      if (joins && !d_psum_head.reserve(channels * nbins_out)) return false;
-      s.row0 = w0.row + (joins ? 1 : 0); s.rows = kept;
-      PowerSumArgs<FD> g;
-      if (od)
-      {
-        FD* const at = peaks + s.row0 * nbins_out;           // the segment's first row of its own
-        s.mat = at;
-        g = joins ? band(d_psum_head.p, nbins_out, at, stride, f) : band(at, stride, at + nbins_out, stride, f);
-      }
-      else
-      {
-        FD* const at = static_cast<FD*>(s.mat);              // scratch, [channels][kept][nbins_out]
-        s.mat_rows = kept;
-        g = joins ? band(d_psum_head.p, nbins_out, at, kept * nbins_out, f) : band(at, kept * nbins_out, at + nbins_out, kept * nbins_out, f);
-      }
-      if (!forward_device(s.m, s.td, s.td_stride, nullptr, 0, nullptr, nullptr, nullptr, nullptr, &g, nullptr, nullptr, nullptr, nullptr, hold)) return false;
-      if (!joins) return true;
-      if (od)
-      {
-        const unsigned long long threads = (unsigned long long)channels * nbins_out;
-        hipLaunchKernelGGL((peak_join_kernel<FD>), dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
-                           peaks + w0.row * nbins_out, stride, d_psum_head.p, (unsigned)nbins_out, (unsigned)channels, hold);
-        SDFT_TRY(hipGetLastError());
-        return true;
-      }
-      head.resize(channels * nbins_out);
-      if (!to_host(head.data(), d_psum_head.p, head.size() * sizeof(FD))) return false;
-      SDFT_TRY(hipStreamSynchronize(stream));
-      for (size_t c = 0; c < channels; ++c)
-        for (size_t k = 0; k < nbins_out; ++k)
-        {
-          FD& held = peaks[c * stride + w0.row * nbins_out + k];
-          held = logic::peak_hold(held, head[c * nbins_out + k], hold);
-        }
-      return true;
+    const char* const refused = logic::peak_hold_ok(hold) ? nullptr : "hold must be sdft_hip_hold_max (0) or sdft_hip_hold_min (1)";
+    if (!grid_args("sdft_hip_sdft_power_peak_n", n, every, first, true, bin0, nbins_out, refused, true, peaks, "peaks", rows)) return false;
+    return pooled_grid_call(n, x, every, first, peaks, rows, channels, nbins_out, d_psum_head, nullptr, hold, grid_ready,
+                            [&](const GridPiece& p, FD* row0, size_t row0_stride, FD* rest, size_t rest_stride) {
+      const PowerSumArgs<FD> g{row0, row0_stride, rest, rest_stride, nullptr, p.grid.every, p.grid.first, (unsigned)bin0, (unsigned)nbins_out};
+      return forward_device(p.m, p.td, p.td_stride, nullptr, 0, nullptr, ForwardCall::power_peak(g, hold));
     });
   }
   // ---- pooled cross-spectrum analysis ------------------------------------------------------------------------------------------
@@ -490,155 +400,37 @@
   size_t pairs_count() const { return pairs.a.size(); }
 
   // pooled cross-spectrum analysis (sdft_hip_sdft_cross_sum_n): per pair (a, b) of the installed list the sums of A conj(B) over the
-  // windows of sdft_power_sum_n's grid, dense [npairs][rows][nbins_out] complex numbers, row 0 the head window [0, first) when
-  // first > 0.  State, pointers and launches as sdft_power_sum_n: never resident, pipelined or fused, forward_cross_sum_kernel on
-  // the plan's stream, then pooled_power_rows_kernel for the windows a chunk boundary cut.  Host memory goes in time segments
-  // through device scratch; each segment is a call of its own under the streaming contract, with its own first: the head rows of
-  // a later segment are kept apart (d_cross_head) and added to the rows the segment before it ended with, on the host for a host
-  // buffer, by pooled_power_add_kernel for a device buffer.  The matrix side of a segment is per PAIR, not per channel, so it
-  // does not go through staged_segments' own copy (which is per channel): the sums of a host buffer pass d_cross_stage here.
+  // windows of the grid, dense [npairs][rows][nbins_out] complex numbers -- forward_cross_sum_kernel, then pooled_power_rows_kernel
+  // for the windows a chunk boundary cut.  The units are the pairs, not the channels: head rows in d_cross_head, the rows of a host
+  // buffer through d_cross_stage.
   bool sdft_cross_sum_n(size_t n, const TD* x, size_t every, size_t first, size_t bin0, size_t nbins_out, FD* sums, size_t& rows)
   {
     static const char* fn = "sdft_hip_sdft_cross_sum_n";
     rows = 0;
     const size_t npairs = pairs_count();
     if (npairs == 0) { set_error(fn, "no pairs are installed (sdft_hip_set_pairs)"); return false; }
-    if (every == 0) { set_error(fn, "every must be at least 1"); return false; }
-    if (nbins_out == 0) { set_error(fn, "nbins must be at least 1"); return false; }
-    if (!logic::power_band_ok(nbins, bin0, nbins_out)) { set_error(fn, "the band bin0 ... bin0 + nbins - 1 does not lie within the plan's bins"); return false; }
-    rows = logic::power_sum_rows(n, every, first);
-    if (rows > 0 && !sums) { set_error(fn, "sums is NULL but the call writes rows"); return false; }
-    if (n == 0) return true;
-    if (!bind()) return false;
-    if (!pipe_join()) return false;
-    if (every > n) every = n;                                // (the same windows; keeps first + k * every in range)
-    const bool xd = on_device(x);
-    const bool od = on_device(sums);
-    const size_t nb2 = 2 * nbins_out;                        // numbers of a row of one pair
-    const size_t row_bytes = npairs * nb2 * sizeof(FD);
-    auto band = [&](FD* row0, size_t row0_stride, FD* rest, size_t rest_stride, size_t f) {
-      return CrossSumArgs<FD>{row0, row0_stride, rest, rest_stride, nullptr, d_cross_items.p, (unsigned)pairs.items.size(), (unsigned)npairs,
-                              (unsigned long long)every, (unsigned long long)f, (unsigned)bin0, (unsigned)nbins_out};
-    };
-    const size_t stride = logic::cross_pair_stride(rows, nbins_out);
-    if (xd && od)
-    {
-      const CrossSumArgs<FD> g = band(sums, stride, sums + nb2, stride, first);
-      return forward_device(n, x, n, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &g) && finish(rows * row_bytes);
-    }
-    // host memory: segments of at most seg samples (rows written and samples within stage_bytes); where the grid allows it, of
-    // whole windows, so that no row is made of two segments
-    size_t seg = n;
-    if (!od) seg = std::min(seg, logic::stage_rows(n, row_bytes, stage_bytes) * every);
-    if (!xd) seg = std::min(seg, std::max<size_t>((size_t)logic::kHopSamples, logic::stage_rows(n, channels * sizeof(TD), stage_bytes)));
-    if (seg < n && seg > every && first % every == 0) seg -= seg % every;
-    const size_t seg_rows_max = (seg + every - 1) / every + 1;
-    if (!od && !d_cross_stage.reserve(npairs * seg_rows_max * nb2)) return false;
-    std::vector<FD> head;                                    // host buffers: a segment's head rows on their way to the rows they complete
-    return staged_segments(n, seg, StagedCall{true, const_cast<TD*>(x), !xd, nullptr, false, rows, seg_rows_max, nb2 * sizeof(FD)}, [&](Segment& s) {
-      const size_t f = logic::every_first_from(s.t, every, first);
-      const logic::PowerSumWindow w0 = logic::power_sum_window(s.t, n, every, first);      // of the segment's row 0 in the call
-      const bool joins = w0.begin < s.t;                     // row 0 is a head: it completes row w0.row of the call
-      const size_t seg_rows = logic::power_sum_rows(s.m, every, f), kept = seg_rows - (joins ? 1 : 0);
-      if (joins && !d_cross_head.reserve(npairs * nb2)) return false;
-      const size_t r0 = w0.row + (joins ? 1 : 0);            // the segment's first row of its own
-      s.rows = 0;                                            // (nothing for staged_segments to copy)
-      FD* const at = od ? sums + r0 * nb2 : d_cross_stage.p; // scratch: [npairs][kept][nbins_out] complex
-      const size_t at_stride = od ? stride : kept * nb2;
-      const CrossSumArgs<FD> g = joins ? band(d_cross_head.p, nb2, at, at_stride, f) : band(at, at_stride, at + nb2, at_stride, f);
-      if (!forward_device(s.m, s.td, s.td_stride, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &g)) return false;
-      if (od)
-      {
-        if (!joins) return true;
-        const unsigned long long threads = (unsigned long long)npairs * nb2;
-        hipLaunchKernelGGL((pooled_power_add_kernel<FD>), dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
-                           sums + w0.row * nb2, stride, d_cross_head.p, (unsigned)nb2, (unsigned)npairs);
-        SDFT_TRY(hipGetLastError());
-        return true;
-      }
-      for (size_t p = 0; p < npairs && kept; ++p)
-        if (!to_host(sums + p * stride + r0 * nb2, d_cross_stage.p + p * kept * nb2, kept * nb2 * sizeof(FD))) return false;
-      if (!joins) return true;
-      head.resize(npairs * nb2);
-      if (!to_host(head.data(), d_cross_head.p, head.size() * sizeof(FD))) return false;
-      SDFT_TRY(hipStreamSynchronize(stream));
-      for (size_t p = 0; p < npairs; ++p)
-        for (size_t k = 0; k < nb2; ++k) sums[p * stride + w0.row * nb2 + k] += head[p * nb2 + k];
-      return true;
+    if (!grid_args(fn, n, every, first, true, bin0, nbins_out, nullptr, true, sums, "sums", rows)) return false;
+    return pooled_grid_call(n, x, every, first, sums, rows, npairs, 2 * nbins_out, d_cross_head, &d_cross_stage, kJoinAdd, grid_ready,
+                            [&](const GridPiece& p, FD* row0, size_t row0_stride, FD* rest, size_t rest_stride) {
+      const CrossSumArgs<FD> g{row0, row0_stride, rest, rest_stride, nullptr, d_cross_items.p, (unsigned)pairs.items.size(), (unsigned)npairs,
+                               p.grid.every, p.grid.first, (unsigned)bin0, (unsigned)nbins_out};
+      return forward_device(p.m, p.td, p.td_stride, nullptr, 0, nullptr, ForwardCall::cross_sum(g));
     });
   }
 
-  // lag-product analysis (sdft_hip_sdft_lag_sum_n): per channel the sums of X[t] conj(X[t - 1]) over the windows of
-  // sdft_power_sum_n's grid, dense [channels][rows][nbins_out] complex numbers, row 0 the head window [0, first) when first > 0.
-  // The cross-spectrum call above with the plan's channels in the pairs' place -- its arguments (no items), workspace, head and
-  // stage buffers, pooled_power_rows_kernel and pooled_power_add_kernel -- and forward_lag_sum_kernel, which steps one recurrence per
-  // wave on the pooled power call's route.  The row before a call's (and so a segment's) first sample is the row of the state the
-  // call starts from, which the kernel demodulates itself: a later segment's first term needs nothing from this side.
+  // lag-product analysis (sdft_hip_sdft_lag_sum_n): per channel the sums of X[t] conj(X[t - 1]) over the windows of the grid, dense
+  // [channels][rows][nbins_out] complex numbers.  The cross-spectrum call above with the plan's channels in the pairs' place -- its
+  // arguments (no items), workspace, head and stage buffers -- and forward_lag_sum_kernel, which steps one recurrence per wave on the
+  // pooled power call's route.  The row before a call's (and so a segment's) first sample is the row of the state the call starts
+  // from, which the kernel demodulates itself: a later segment's first term needs nothing from this side.
   bool sdft_lag_sum_n(size_t n, const TD* x, size_t every, size_t first, size_t bin0, size_t nbins_out, FD* sums, size_t& rows)
   {
-    static const char* fn = "sdft_hip_sdft_lag_sum_n";
-    rows = 0;
-    if (every == 0) { set_error(fn, "every must be at least 1"); return false; }
-    if (nbins_out == 0) { set_error(fn, "nbins must be at least 1"); return false; }
-    if (!logic::power_band_ok(nbins, bin0, nbins_out)) { set_error(fn, "the band bin0 ... bin0 + nbins - 1 does not lie within the plan's bins"); return false; }
-    rows = logic::power_sum_rows(n, every, first);
-    if (rows > 0 && !sums) { set_error(fn, "sums is NULL but the call writes rows"); return false; }
-    if (n == 0) return true;
-    if (!bind()) return false;
-    if (!pipe_join()) return false;
-    if (every > n) every = n;                                // (the same windows; keeps first + k * every in range)
-    const bool xd = on_device(x);
-    const bool od = on_device(sums);
-    const size_t nb2 = 2 * nbins_out;                        // numbers of a row of one channel
-    const size_t row_bytes = channels * nb2 * sizeof(FD);
-    auto band = [&](FD* row0, size_t row0_stride, FD* rest, size_t rest_stride, size_t f) {
-      return CrossSumArgs<FD>{row0, row0_stride, rest, rest_stride, nullptr, nullptr, (unsigned)channels, (unsigned)channels,
-                              (unsigned long long)every, (unsigned long long)f, (unsigned)bin0, (unsigned)nbins_out};
-    };
-    auto run = [&](size_t m, const TD* td, size_t td_stride, const CrossSumArgs<FD>& g) {
-      return forward_device(m, td, td_stride, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &g, nullptr, nullptr, -1, true);
-    };
-    const size_t stride = logic::lag_channel_stride(rows, nbins_out);
-    if (xd && od)
-    {
-      const CrossSumArgs<FD> g = band(sums, stride, sums + nb2, stride, first);
-      return run(n, x, n, g) && finish(rows * row_bytes);
-    }
-    // host memory: segments of at most seg samples (logic::lag_sum_segment)
-    const size_t seg = logic::lag_sum_segment(n, every, first, channels, nbins_out, sizeof(FD), sizeof(TD), stage_bytes, xd, od);
-    const size_t seg_rows_max = (seg + every - 1) / every + 1;
-    if (!od && !d_cross_stage.reserve(channels * seg_rows_max * nb2)) return false;
-    std::vector<FD> head;                                    // host buffers: a segment's head rows on their way to the rows they complete
-    return staged_segments(n, seg, StagedCall{true, const_cast<TD*>(x), !xd, nullptr, false, rows, seg_rows_max, nb2 * sizeof(FD)}, [&](Segment& s) {
-      const size_t f = logic::every_first_from(s.t, every, first);
-      const logic::PowerSumWindow w0 = logic::power_sum_window(s.t, n, every, first);      // of the segment's row 0 in the call
-      const bool joins = w0.begin < s.t;                     // row 0 is a head: it completes row w0.row of the call
-      const size_t seg_rows = logic::power_sum_rows(s.m, every, f), kept = seg_rows - (joins ? 1 : 0);
-      if (joins && !d_cross_head.reserve(channels * nb2)) return false;
-      const size_t r0 = w0.row + (joins ? 1 : 0);            // the segment's first row of its own
-      s.rows = 0;                                            // (nothing for staged_segments to copy)
-      FD* const at = od ? sums + r0 * nb2 : d_cross_stage.p; // scratch: [channels][kept][nbins_out] complex
-      const size_t at_stride = od ? stride : kept * nb2;
-      const CrossSumArgs<FD> g = joins ? band(d_cross_head.p, nb2, at, at_stride, f) : band(at, at_stride, at + nb2, at_stride, f);
-      if (!run(s.m, s.td, s.td_stride, g)) return false;
-      if (od)
-      {
-        if (!joins) return true;
-        const unsigned long long threads = (unsigned long long)channels * nb2;
-        hipLaunchKernelGGL((pooled_power_add_kernel<FD>), dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
-                           sums + w0.row * nb2, stride, d_cross_head.p, (unsigned)nb2, (unsigned)channels);
-        SDFT_TRY(hipGetLastError());
-        return true;
-      }
-      for (size_t c = 0; c < channels && kept; ++c)
-        if (!to_host(sums + c * stride + r0 * nb2, d_cross_stage.p + c * kept * nb2, kept * nb2 * sizeof(FD))) return false;
-      if (!joins) return true;
-      head.resize(channels * nb2);
-      if (!to_host(head.data(), d_cross_head.p, head.size() * sizeof(FD))) return false;
-      SDFT_TRY(hipStreamSynchronize(stream));
-      for (size_t c = 0; c < channels; ++c)
-        for (size_t k = 0; k < nb2; ++k) sums[c * stride + w0.row * nb2 + k] += head[c * nb2 + k];
-      return true;
+    if (!grid_args("sdft_hip_sdft_lag_sum_n", n, every, first, true, bin0, nbins_out, nullptr, true, sums, "sums", rows)) return false;
+    return pooled_grid_call(n, x, every, first, sums, rows, channels, 2 * nbins_out, d_cross_head, &d_cross_stage, kJoinAdd, grid_ready,
+                            [&](const GridPiece& p, FD* row0, size_t row0_stride, FD* rest, size_t rest_stride) {
+      const CrossSumArgs<FD> g{row0, row0_stride, rest, rest_stride, nullptr, nullptr, (unsigned)channels, (unsigned)channels,
+                               p.grid.every, p.grid.first, (unsigned)bin0, (unsigned)nbins_out};
+      return forward_device(p.m, p.td, p.td_stride, nullptr, 0, nullptr, ForwardCall::lag_sum(g));
     });
   }
 
@@ -688,78 +480,21 @@
   size_t array_channels() const { return array.chan.size(); }
 
   // array covariance analysis (sdft_hip_sdft_covariance_n): sdft_cross_sum_n for all pairs (i <= j) of the installed array, dense
-  // [nch (nch + 1) / 2][rows][nbins_out] complex numbers in the order of logic::covariance_pair_index.  Grid, state, pointers,
-  // segments of host memory, head rows and launches are sdft_cross_sum_n's with the output indices for pairs (d_cov_head,
-  // d_cov_stage); forward_covariance_kernel forms the sums by blocks of groups of channels.
+  // [nch (nch + 1) / 2][rows][nbins_out] complex numbers in the order of logic::covariance_pair_index (head rows in d_cov_head, the
+  // rows of a host buffer through d_cov_stage); forward_covariance_kernel forms the sums by blocks of groups of channels
   bool sdft_covariance_n(size_t n, const TD* x, size_t every, size_t first, size_t bin0, size_t nbins_out, FD* sums, size_t& rows)
   {
     static const char* fn = "sdft_hip_sdft_covariance_n";
     rows = 0;
     const size_t nch = array_channels(), npairs = logic::covariance_pairs(nch);
     if (nch == 0) { set_error(fn, "no array is installed (sdft_hip_set_array)"); return false; }
-    if (every == 0) { set_error(fn, "every must be at least 1"); return false; }
-    if (nbins_out == 0) { set_error(fn, "nbins must be at least 1"); return false; }
-    if (!logic::power_band_ok(nbins, bin0, nbins_out)) { set_error(fn, "the band bin0 ... bin0 + nbins - 1 does not lie within the plan's bins"); return false; }
-    rows = logic::power_sum_rows(n, every, first);
-    if (rows > 0 && !sums) { set_error(fn, "cov is NULL but the call writes rows"); return false; }
-    if (n == 0) return true;
-    if (!bind()) return false;
-    if (!pipe_join()) return false;
-    if (array.group != array_group() && !upload_array(array)) return false;       // (a test hook changed the group size)
-    if (every > n) every = n;                                // (the same windows; keeps first + k * every in range)
-    const bool xd = on_device(x);
-    const bool od = on_device(sums);
-    const size_t nb2 = 2 * nbins_out;                        // numbers of a row of one pair
-    const size_t row_bytes = npairs * nb2 * sizeof(FD);
-    auto band = [&](FD* row0, size_t row0_stride, FD* rest, size_t rest_stride, size_t f) {
-      return CovarianceArgs<FD>{row0, row0_stride, rest, rest_stride, nullptr, d_cov_items.p, d_cov_chan.p, (unsigned)array.items.size(), (unsigned)nch,
-                                (unsigned)npairs, (unsigned long long)every, (unsigned long long)f, (unsigned)bin0, (unsigned)nbins_out};
-    };
-    const size_t stride = logic::cross_pair_stride(rows, nbins_out);
-    if (xd && od)
-    {
-      const CovarianceArgs<FD> g = band(sums, stride, sums + nb2, stride, first);
-      return forward_device(n, x, n, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &g) && finish(rows * row_bytes);
-    }
-    // host memory: segments of at most seg samples (rows written and samples within stage_bytes); where the grid allows it, of
-    // whole windows, so that no row is made of two segments
-    size_t seg = n;
-    if (!od) seg = std::min(seg, logic::stage_rows(n, row_bytes, stage_bytes) * every);
-    if (!xd) seg = std::min(seg, std::max<size_t>((size_t)logic::kHopSamples, logic::stage_rows(n, channels * sizeof(TD), stage_bytes)));
-    if (seg < n && seg > every && first % every == 0) seg -= seg % every;
-    const size_t seg_rows_max = (seg + every - 1) / every + 1;
-    if (!od && !d_cov_stage.reserve(npairs * seg_rows_max * nb2)) return false;
-    std::vector<FD> head;                                    // host buffers: a segment's head rows on their way to the rows they complete
-    return staged_segments(n, seg, StagedCall{true, const_cast<TD*>(x), !xd, nullptr, false, rows, seg_rows_max, nb2 * sizeof(FD)}, [&](Segment& s) {
-      const size_t f = logic::every_first_from(s.t, every, first);
-      const logic::PowerSumWindow w0 = logic::power_sum_window(s.t, n, every, first);      // of the segment's row 0 in the call
-      const bool joins = w0.begin < s.t;                     // row 0 is a head: it completes row w0.row of the call
-      const size_t seg_rows = logic::power_sum_rows(s.m, every, f), kept = seg_rows - (joins ? 1 : 0);
-      if (joins && !d_cov_head.reserve(npairs * nb2)) return false;
-      const size_t r0 = w0.row + (joins ? 1 : 0);            // the segment's first row of its own
-      s.rows = 0;                                            // (nothing for staged_segments to copy)
-      FD* const at = od ? sums + r0 * nb2 : d_cov_stage.p;   // scratch: [npairs][kept][nbins_out] complex
-      const size_t at_stride = od ? stride : kept * nb2;
-      const CovarianceArgs<FD> g = joins ? band(d_cov_head.p, nb2, at, at_stride, f) : band(at, at_stride, at + nb2, at_stride, f);
-      if (!forward_device(s.m, s.td, s.td_stride, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &g)) return false;
-      if (od)
-      {
-        if (!joins) return true;
-        const unsigned long long threads = (unsigned long long)npairs * nb2;
-        hipLaunchKernelGGL((pooled_power_add_kernel<FD>), dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
-                           sums + w0.row * nb2, stride, d_cov_head.p, (unsigned)nb2, (unsigned)npairs);
-        SDFT_TRY(hipGetLastError());
-        return true;
-      }
-      for (size_t p = 0; p < npairs && kept; ++p)
-        if (!to_host(sums + p * stride + r0 * nb2, d_cov_stage.p + p * kept * nb2, kept * nb2 * sizeof(FD))) return false;
-      if (!joins) return true;
-      head.resize(npairs * nb2);
-      if (!to_host(head.data(), d_cov_head.p, head.size() * sizeof(FD))) return false;
-      SDFT_TRY(hipStreamSynchronize(stream));
-      for (size_t p = 0; p < npairs; ++p)
-        for (size_t k = 0; k < nb2; ++k) sums[p * stride + w0.row * nb2 + k] += head[p * nb2 + k];
-      return true;
+    if (!grid_args(fn, n, every, first, true, bin0, nbins_out, nullptr, true, sums, "cov", rows)) return false;
+    auto ready = [&] { return array.group == array_group() || upload_array(array); };      // (a test hook changed the group size)
+    return pooled_grid_call(n, x, every, first, sums, rows, npairs, 2 * nbins_out, d_cov_head, &d_cov_stage, kJoinAdd, ready,
+                            [&](const GridPiece& p, FD* row0, size_t row0_stride, FD* rest, size_t rest_stride) {
+      const CovarianceArgs<FD> g{row0, row0_stride, rest, rest_stride, nullptr, d_cov_items.p, d_cov_chan.p, (unsigned)array.items.size(), (unsigned)nch,
+                                 (unsigned)npairs, p.grid.every, p.grid.first, (unsigned)bin0, (unsigned)nbins_out};
+      return forward_device(p.m, p.td, p.td_stride, nullptr, 0, nullptr, ForwardCall::covariance(g));
     });
   }
 
@@ -825,57 +560,22 @@
   }
   size_t mix_outputs() const { return mix.nout; }
 
-  // channel-mix analysis (sdft_hip_sdft_mix_n): the weighted sums of the installed mix at the rows of sdft_every_n's grid, for the
-  // bins of sdft_power_n's band, dense [nout][rows][nbins_out] complex numbers; the stream state afterwards is the one sdft_n
-  // leaves.  Never resident, pipelined or fused: one forward launch on the plan's stream (forward_mix_kernel), host memory in time
-  // segments as in sdft_power_n -- but rows on their way to a host buffer are formed in device scratch (d_mix_stage), so that the
-  // kernel never re-reads a running sum from host memory, and copied out output by output.
+  // channel-mix analysis (sdft_hip_sdft_mix_n): the weighted sums of the installed mix at the rows of the grid, for the bins of
+  // sdft_power_n's band, dense [nout][rows][nbins_out] complex numbers -- forward_mix_kernel.  Rows on their way to a host buffer
+  // are formed in d_mix_stage, so that the kernel never re-reads a running sum from host memory, and copied out output by output.
   bool sdft_mix_n(size_t n, const TD* x, size_t every, size_t first, size_t bin0, size_t nbins_out, FD* out, size_t& rows)
   {
     static const char* fn = "sdft_hip_sdft_mix_n";
     rows = 0;
     const size_t nout = mix.nout, nch = mix.chan.size();
     if (nout == 0) { set_error(fn, "no mix is installed (sdft_hip_set_mix)"); return false; }
-    if (every == 0) { set_error(fn, "every must be at least 1"); return false; }
-    if (nbins_out == 0) { set_error(fn, "nbins must be at least 1"); return false; }
-    if (!logic::power_band_ok(nbins, bin0, nbins_out)) { set_error(fn, "the band bin0 ... bin0 + nbins - 1 does not lie within the plan's bins"); return false; }
-    rows = logic::every_rows(n, every, first);
-    if (rows > 0 && !out) { set_error(fn, "out is NULL but the call keeps rows"); return false; }
-    if (n == 0) return true;
-    if (!bind()) return false;
-    if (!pipe_join()) return false;
-    if (mix.block != mix_block_size() && !upload_mix_items(mix, d_mix_items)) return false;      // (a test hook changed the block size)
-    if (every > n) every = n;                                // (the same grid: at most one row; keeps first + k * every in range)
-    const bool xd = on_device(x);
-    const bool od = rows == 0 || on_device(out);
-    const size_t nb2 = 2 * nbins_out;                        // numbers of a row of one output
-    const size_t row_bytes = nout * nb2 * sizeof(FD);
-    auto band = [&](FD* at, size_t at_rows, size_t f) {
-      return MixArgs<FD>{at, logic::mix_output_stride(at_rows, nbins_out), d_mix_weights.p, d_mix_items.p, d_mix_chan.p, (unsigned)mix.items.size(), (unsigned)nch,
-                         (unsigned)nout, (unsigned long long)every, (unsigned long long)f, (unsigned)bin0, (unsigned)nbins_out};
-    };
-    if (xd && od)
-    {
-      const MixArgs<FD> g = band(out, rows, first);
-      return forward_device(n, x, n, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &g) && finish(rows * row_bytes);
-    }
-    // host memory: segments of at most seg samples (rows kept and samples within stage_bytes), each one forward launch
-    size_t seg = n;
-    if (!od) seg = std::min(seg, logic::stage_rows(n, row_bytes, stage_bytes) * every);
-    if (!xd) seg = std::min(seg, std::max<size_t>((size_t)logic::kHopSamples, logic::stage_rows(n, channels * sizeof(TD), stage_bytes)));
-    const size_t seg_rows_max = (seg + every - 1) / every;
-    if (!od && !d_mix_stage.reserve(nout * seg_rows_max * nb2)) return false;
-    return staged_segments(n, seg, StagedCall{true, const_cast<TD*>(x), !xd, nullptr, false, rows, seg_rows_max, nb2 * sizeof(FD)}, [&](Segment& s) {
-      const size_t f = logic::every_first_from(s.t, every, first);
-      const size_t kept = logic::every_rows(s.m, every, f);
-      const size_t r0 = kept ? (s.t + f - first) / every : 0; // the segment's first row in the call's grid
-      s.rows = 0;                                            // (nothing for staged_segments to copy)
-      const MixArgs<FD> g = od ? band(kept ? out + r0 * nb2 : nullptr, rows, f) : band(d_mix_stage.p, kept, f);
-      if (!forward_device(s.m, s.td, s.td_stride, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &g)) return false;
-      for (size_t o = 0; o < nout && kept && !od; ++o)
-        if (!to_host(out + o * rows * nb2 + r0 * nb2, d_mix_stage.p + o * kept * nb2, kept * nb2 * sizeof(FD))) return false;
-      return true;
-    });
+    if (!grid_args(fn, n, every, first, true, bin0, nbins_out, nullptr, false, out, "out", rows)) return false;
+    auto ready = [&] { return mix.block == mix_block_size() || upload_mix_items(mix, d_mix_items); };      // (a test hook changed the block size)
+    return every_grid_call(n, x, every, first, out, rows, nout, 2 * nbins_out, ready, [&](const GridPiece& p, FD* at, size_t at_rows) {
+      const MixArgs<FD> g{at, logic::mix_output_stride(at_rows, nbins_out), d_mix_weights.p, d_mix_items.p, d_mix_chan.p, (unsigned)mix.items.size(), (unsigned)nch,
+                          (unsigned)nout, p.grid.every, p.grid.first, (unsigned)bin0, (unsigned)nbins_out};
+      return forward_device(p.m, p.td, p.td_stride, nullptr, 0, nullptr, ForwardCall::channel_mix(g));
+    }, &d_mix_stage);
   }
 
   // a host table of device rows goes to the device; nullptr: failed
@@ -1122,7 +822,7 @@
         fz.walked = walked_counter();
         if (r.fold) { if (!fold_coefficients(op)) return false; } else coeff_ready = false;
         last_process_path = 1;
-        if (!forward_device(n, xs, n, dfts, n * nbins, nullptr, &fz)) return false;
+        if (!forward_device(n, xs, n, dfts, n * nbins, nullptr, ForwardCall::fused(fz))) return false;
       }
       else
       {

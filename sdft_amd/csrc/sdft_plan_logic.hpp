@@ -1291,20 +1291,26 @@ inline size_t stage_rows(size_t n, size_t row_bytes, size_t stage_bytes)
   const size_t seg = std::max<size_t>(1, stage_bytes / std::max<size_t>(row_bytes, 1));
   return std::min(seg, std::max<size_t>(n, 1));
 }
-// The lag-product call on host memory goes in time segments of at most this many samples: the cross-spectrum call's bounds with
-// npairs = channels -- the rows a segment writes (channels * 2 * nbins_out numbers each) and the samples it reads stay within
-// stage_bytes, and where the grid allows it a segment is made of whole windows, so that no row is made of two segments.
-// every <= n (the entry point has clamped it); samples_on_device / sums_on_device: that side needs no staging.
+// A grid analysis call (sdft_every_n and its eight siblings) on host memory goes in time segments of at most this many samples:
+// the rows a segment writes (row_bytes each, all channels / pairs / outputs of a row together; one row per `every` samples) and
+// the samples it reads (sample_row_bytes per time step) stay within stage_bytes -- but a segment of host samples is never shorter
+// than a hop.  whole_windows (the pooled calls): where the grid allows it a segment is made of whole windows, so that no row is
+// made of two segments.  every <= n (the entry point has clamped it); samples_on_device / out_on_device: that side needs no staging.
+inline size_t grid_segment(size_t n, size_t every, size_t first, size_t row_bytes, size_t sample_row_bytes, size_t stage_bytes,
+                           bool samples_on_device, bool out_on_device, bool whole_windows)
+{
+  size_t seg = n;
+  if (!out_on_device) seg = std::min(seg, stage_rows(n, row_bytes, stage_bytes) * every);
+  if (!samples_on_device) seg = std::min(seg, std::max<size_t>((size_t)kHopSamples, stage_rows(n, sample_row_bytes, stage_bytes)));
+  if (whole_windows && seg < n && seg > every && first % every == 0) seg -= seg % every;
+  return seg;
+}
+// the lag-product call's: the cross-spectrum call's bounds with npairs = channels (channels * 2 * nbins_out numbers per row)
 inline size_t lag_sum_segment(size_t n, size_t every, size_t first, size_t channels, size_t nbins_out, size_t fd_bytes, size_t td_bytes,
                               size_t stage_bytes, bool samples_on_device, bool sums_on_device)
 {
   const size_t ch = std::max<size_t>(channels, 1);
-  const size_t row_bytes = ch * 2 * nbins_out * fd_bytes;
-  size_t seg = n;
-  if (!sums_on_device) seg = std::min(seg, stage_rows(n, row_bytes, stage_bytes) * every);
-  if (!samples_on_device) seg = std::min(seg, std::max<size_t>((size_t)kHopSamples, stage_rows(n, ch * td_bytes, stage_bytes)));
-  if (seg < n && seg > every && first % every == 0) seg -= seg % every;
-  return seg;
+  return grid_segment(n, every, first, ch * 2 * nbins_out * fd_bytes, ch * td_bytes, stage_bytes, samples_on_device, sums_on_device, true);
 }
 
 // ---- host memory: the route of an analysis or a synthesis call (Plan::sdft_n / isdft_n run it) -----------------------------

@@ -29,6 +29,17 @@ def _is_tensor(a) -> bool:
     return type(a).__module__.startswith("torch")
 
 
+def _grid_args(dftsize: int, every, first, bins=None, banded=True, word="bins"):
+    """The arguments every grid analysis call of :class:`SDFT` takes, checked: (every, first, bin0, nbins)."""
+    every, first = int(every), int(first)
+    bin0, nb = (0, dftsize) if bins is None else (int(bins[0]), int(bins[1]))
+    if every < 1 or first < 0:
+        raise ValueError(f"every must be >= 1 and first >= 0, got every={every}, first={first}")
+    if banded and (bin0 < 0 or nb < 1 or bin0 + nb > dftsize):
+        raise ValueError(f"{word} = (bin0, nbins) must select at least one of the {dftsize} bins, got {(bin0, nb)}")
+    return every, first, bin0, nb
+
+
 class SDFT:
     """One analysis/synthesis plan = one stream (or a batch of independent channels).
 
@@ -221,40 +232,46 @@ class SDFT:
         self.api.check()
         return out
 
+    def _grid_call(self, name, x, rows_rule, every, first, extra, lead, trail, dtype, out):
+        """One grid analysis call ``sdft_hip_<name>(plan, n, x, every, first, *extra, out)`` on checked arguments: a device tensor
+        or a numpy array in, the same kind out, of shape (lead, rows, trail) -- ``lead=None``: (rows, trail) for 1-D samples,
+        (channels, rows, trail) for batched ones --, ``rows = rows_rule(n, every, first)``, which the library must report too."""
+        tensor = _is_tensor(x)
+        if tensor:
+            n = self._shape_x(x.shape)
+            self._check_tensor(x, "samples", self.td)
+        else:
+            x = np.ascontiguousarray(x, dtype=self.td)
+            n = self._shape_x(x.shape)
+        rows = rows_rule(n, every, first)
+        shape = (lead, rows, trail) if lead is not None else (rows, trail) if x.ndim == 1 else (self.channels, rows, trail)
+        if tensor:
+            torch = _torch()
+            if out is None:
+                out = torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=x.device)
+            self._check_tensor(out, "out", dtype, shape)
+            xp, op = x.data_ptr(), (out.data_ptr() if rows else None)
+        else:
+            if out is None:
+                out = np.empty(shape, dtype=dtype)
+            assert out.flags.c_contiguous and out.shape == shape and out.dtype == dtype
+            xp, op = x.ctypes.data, (out.ctypes.data if rows else None)
+        got = getattr(self.api, name)(self._p, n, C.c_void_p(xp), every, first, *extra, C.c_void_p(op))
+        if got < 0:
+            self.api.check()
+            raise SdftHipError(f"sdft_hip_{name} failed")
+        self.api.check()
+        assert got == rows, (got, rows)
+        return out
+
     def sdft_every(self, x, every: int, first: int = 0, out=None):
         """Decimated analysis (``sdft_hip_sdft_every_n``): the rows :meth:`sdft` would return for the samples ``first``,
         ``first + every``, ... < n -> array of shape (rows, dftsize) [(channels, rows, dftsize) if batched], numpy for numpy
         input, a device tensor for a device tensor.  The plan's state advances over all n samples, as with :meth:`sdft`.
         The grid is local to the call: a streaming host passes :func:`every_next_first` as the next call's ``first``."""
         self.api.clear()
-        every, first = int(every), int(first)
-        if every < 1 or first < 0:
-            raise ValueError(f"every must be >= 1 and first >= 0, got every={every}, first={first}")
-        if _is_tensor(x):
-            torch = _torch()
-            n = self._shape_x(x.shape)
-            self._check_tensor(x, "samples", self.td)
-            rows = every_rows(n, every, first)
-            shape = (rows, self.dftsize) if x.dim() == 1 else (self.channels, rows, self.dftsize)
-            if out is None:
-                out = torch.empty(shape, dtype=getattr(torch, np.dtype(self.fdx).name), device=x.device)
-            self._check_tensor(out, "out", self.fdx, shape)
-            got = self.api.sdft_every_n(self._p, n, C.c_void_p(x.data_ptr()), every, first, C.c_void_p(out.data_ptr() if rows else None))
-        else:
-            x = np.ascontiguousarray(x, dtype=self.td)
-            n = self._shape_x(x.shape)
-            rows = every_rows(n, every, first)
-            shape = (rows, self.dftsize) if x.ndim == 1 else (self.channels, rows, self.dftsize)
-            if out is None:
-                out = np.empty(shape, dtype=self.fdx)
-            assert out.flags.c_contiguous and out.shape == shape and out.dtype == self.fdx
-            got = self.api.sdft_every_n(self._p, n, C.c_void_p(x.ctypes.data), every, first, C.c_void_p(out.ctypes.data if rows else None))
-        if got < 0:
-            self.api.check()
-            raise SdftHipError("sdft_hip_sdft_every_n failed")
-        self.api.check()
-        assert got == rows, (got, rows)
-        return out
+        every, first, _, _ = _grid_args(self.dftsize, every, first, banded=False)
+        return self._grid_call("sdft_every_n", x, every_rows, every, first, (), None, self.dftsize, self.fdx, out)
 
     def power(self, x, every: int = 1, first: int = 0, bins=None, out=None):
         """Power-spectrogram analysis (``sdft_hip_sdft_power_n``): ``re*re + im*im`` of the bins ``bins = (bin0, nbins)`` (``None``:
@@ -263,37 +280,8 @@ class SDFT:
         complex rows are never stored.  The plan's state advances over all n samples and all bins, as with :meth:`sdft`; the grid is
         local to the call and streams with :func:`every_next_first`, as that of :meth:`sdft_every`."""
         self.api.clear()
-        every, first = int(every), int(first)
-        bin0, nb = (0, self.dftsize) if bins is None else (int(bins[0]), int(bins[1]))
-        if every < 1 or first < 0:
-            raise ValueError(f"every must be >= 1 and first >= 0, got every={every}, first={first}")
-        if bin0 < 0 or nb < 1 or bin0 + nb > self.dftsize:
-            raise ValueError(f"bins = (bin0, nbins) must select at least one of the {self.dftsize} bins, got {(bin0, nb)}")
-        if _is_tensor(x):
-            torch = _torch()
-            n = self._shape_x(x.shape)
-            self._check_tensor(x, "samples", self.td)
-            rows = every_rows(n, every, first)
-            shape = (rows, nb) if x.dim() == 1 else (self.channels, rows, nb)
-            if out is None:
-                out = torch.empty(shape, dtype=getattr(torch, np.dtype(self.fd).name), device=x.device)
-            self._check_tensor(out, "out", self.fd, shape)
-            got = self.api.sdft_power_n(self._p, n, C.c_void_p(x.data_ptr()), every, first, bin0, nb, C.c_void_p(out.data_ptr() if rows else None))
-        else:
-            x = np.ascontiguousarray(x, dtype=self.td)
-            n = self._shape_x(x.shape)
-            rows = every_rows(n, every, first)
-            shape = (rows, nb) if x.ndim == 1 else (self.channels, rows, nb)
-            if out is None:
-                out = np.empty(shape, dtype=self.fd)
-            assert out.flags.c_contiguous and out.shape == shape and out.dtype == self.fd
-            got = self.api.sdft_power_n(self._p, n, C.c_void_p(x.ctypes.data), every, first, bin0, nb, C.c_void_p(out.ctypes.data if rows else None))
-        if got < 0:
-            self.api.check()
-            raise SdftHipError("sdft_hip_sdft_power_n failed")
-        self.api.check()
-        assert got == rows, (got, rows)
-        return out
+        every, first, bin0, nb = _grid_args(self.dftsize, every, first, bins)
+        return self._grid_call("sdft_power_n", x, every_rows, every, first, (bin0, nb), None, nb, self.fd, out)
 
     def set_filterbank(self, bin0, nbins, weights):
         """Installs a filterbank in the plan (``sdft_hip_set_filterbank``; the arrays are copied): band b covers the bins
@@ -327,37 +315,11 @@ class SDFT:
         input, a device tensor for a device tensor.  Neither the complex rows nor the powers are stored.  State and grid as with
         :meth:`power`."""
         self.api.clear()
-        every, first = int(every), int(first)
-        if every < 1 or first < 0:
-            raise ValueError(f"every must be >= 1 and first >= 0, got every={every}, first={first}")
+        every, first, _, _ = _grid_args(self.dftsize, every, first, banded=False)
         nb = self.filterbank_bands
         if nb == 0:
             raise ValueError("no filterbank is installed: call set_filterbank first")
-        if _is_tensor(x):
-            torch = _torch()
-            n = self._shape_x(x.shape)
-            self._check_tensor(x, "samples", self.td)
-            rows = every_rows(n, every, first)
-            shape = (rows, nb) if x.dim() == 1 else (self.channels, rows, nb)
-            if out is None:
-                out = torch.empty(shape, dtype=getattr(torch, np.dtype(self.fd).name), device=x.device)
-            self._check_tensor(out, "out", self.fd, shape)
-            got = self.api.sdft_filterbank_n(self._p, n, C.c_void_p(x.data_ptr()), every, first, C.c_void_p(out.data_ptr() if rows else None))
-        else:
-            x = np.ascontiguousarray(x, dtype=self.td)
-            n = self._shape_x(x.shape)
-            rows = every_rows(n, every, first)
-            shape = (rows, nb) if x.ndim == 1 else (self.channels, rows, nb)
-            if out is None:
-                out = np.empty(shape, dtype=self.fd)
-            assert out.flags.c_contiguous and out.shape == shape and out.dtype == self.fd
-            got = self.api.sdft_filterbank_n(self._p, n, C.c_void_p(x.ctypes.data), every, first, C.c_void_p(out.ctypes.data if rows else None))
-        if got < 0:
-            self.api.check()
-            raise SdftHipError("sdft_hip_sdft_filterbank_n failed")
-        self.api.check()
-        assert got == rows, (got, rows)
-        return out
+        return self._grid_call("sdft_filterbank_n", x, every_rows, every, first, (), None, nb, self.fd, out)
 
     def set_pairs(self, a, b):
         """Installs a list of channel pairs in the plan (``sdft_hip_set_pairs``; the arrays are copied): pair p is the channels
@@ -390,41 +352,11 @@ class SDFT:
         plan].  Head row, streaming and sums-not-means as with :meth:`power_sum`.  The state of every channel of the plan advances
         over all n samples and all bins, as with :meth:`sdft`."""
         self.api.clear()
-        every, first = int(every), int(first)
-        bin0, nb = (0, self.dftsize) if bins is None else (int(bins[0]), int(bins[1]))
-        if every < 1 or first < 0:
-            raise ValueError(f"every must be >= 1 and first >= 0, got every={every}, first={first}")
-        if bin0 < 0 or nb < 1 or bin0 + nb > self.dftsize:
-            raise ValueError(f"bins = (bin0, nbins) must select at least one of the {self.dftsize} bins, got {(bin0, nb)}")
+        every, first, bin0, nb = _grid_args(self.dftsize, every, first, bins)
         npairs = self.pairs
         if npairs == 0:
             raise ValueError("no pairs are installed: call set_pairs first")
-        cdtype = np.dtype(np.complex64 if np.dtype(self.fd) == np.float32 else np.complex128)
-        if _is_tensor(x):
-            torch = _torch()
-            n = self._shape_x(x.shape)
-            self._check_tensor(x, "samples", self.td)
-            rows = power_sum_rows(n, every, first)
-            shape = (npairs, rows, nb)
-            if out is None:
-                out = torch.empty(shape, dtype=getattr(torch, cdtype.name), device=x.device)
-            self._check_tensor(out, "out", cdtype, shape)
-            got = self.api.sdft_cross_sum_n(self._p, n, C.c_void_p(x.data_ptr()), every, first, bin0, nb, C.c_void_p(out.data_ptr() if rows else None))
-        else:
-            x = np.ascontiguousarray(x, dtype=self.td)
-            n = self._shape_x(x.shape)
-            rows = power_sum_rows(n, every, first)
-            shape = (npairs, rows, nb)
-            if out is None:
-                out = np.empty(shape, dtype=cdtype)
-            assert out.flags.c_contiguous and out.shape == shape and out.dtype == cdtype
-            got = self.api.sdft_cross_sum_n(self._p, n, C.c_void_p(x.ctypes.data), every, first, bin0, nb, C.c_void_p(out.ctypes.data if rows else None))
-        if got < 0:
-            self.api.check()
-            raise SdftHipError("sdft_hip_sdft_cross_sum_n failed")
-        self.api.check()
-        assert got == rows, (got, rows)
-        return out
+        return self._grid_call("sdft_cross_sum_n", x, power_sum_rows, every, first, (bin0, nb), npairs, nb, self.fdx, out)
 
     def set_array(self, chan):
         """Installs an array in the plan (``sdft_hip_set_array``; the list is copied): an ordered list of distinct channels, the
@@ -455,42 +387,11 @@ class SDFT:
         Arguments, grid, head row, streaming and state as with :meth:`cross_sum`; :func:`covariance_matrix` expands the result to
         Hermitian matrices on the host."""
         self.api.clear()
-        every, first = int(every), int(first)
-        bin0, nb = (0, self.dftsize) if bins is None else (int(bins[0]), int(bins[1]))
-        if every < 1 or first < 0:
-            raise ValueError(f"every must be >= 1 and first >= 0, got every={every}, first={first}")
-        if bin0 < 0 or nb < 1 or bin0 + nb > self.dftsize:
-            raise ValueError(f"bins = (bin0, nbins) must select at least one of the {self.dftsize} bins, got {(bin0, nb)}")
+        every, first, bin0, nb = _grid_args(self.dftsize, every, first, bins)
         nch = self.array_channels
         if nch == 0:
             raise ValueError("no array is installed: call set_array first")
-        npairs = nch * (nch + 1) // 2
-        cdtype = np.dtype(np.complex64 if np.dtype(self.fd) == np.float32 else np.complex128)
-        if _is_tensor(x):
-            torch = _torch()
-            n = self._shape_x(x.shape)
-            self._check_tensor(x, "samples", self.td)
-            rows = power_sum_rows(n, every, first)
-            shape = (npairs, rows, nb)
-            if out is None:
-                out = torch.empty(shape, dtype=getattr(torch, cdtype.name), device=x.device)
-            self._check_tensor(out, "out", cdtype, shape)
-            got = self.api.sdft_covariance_n(self._p, n, C.c_void_p(x.data_ptr()), every, first, bin0, nb, C.c_void_p(out.data_ptr() if rows else None))
-        else:
-            x = np.ascontiguousarray(x, dtype=self.td)
-            n = self._shape_x(x.shape)
-            rows = power_sum_rows(n, every, first)
-            shape = (npairs, rows, nb)
-            if out is None:
-                out = np.empty(shape, dtype=cdtype)
-            assert out.flags.c_contiguous and out.shape == shape and out.dtype == cdtype
-            got = self.api.sdft_covariance_n(self._p, n, C.c_void_p(x.ctypes.data), every, first, bin0, nb, C.c_void_p(out.ctypes.data if rows else None))
-        if got < 0:
-            self.api.check()
-            raise SdftHipError("sdft_hip_sdft_covariance_n failed")
-        self.api.check()
-        assert got == rows, (got, rows)
-        return out
+        return self._grid_call("sdft_covariance_n", x, power_sum_rows, every, first, (bin0, nb), nch * (nch + 1) // 2, nb, self.fdx, out)
 
     def set_mix(self, weights, chan=None):
         """Installs a mix in the plan (``sdft_hip_set_mix``; list and weights are copied).  ``weights`` is a complex array of shape
@@ -541,41 +442,11 @@ class SDFT:
         stream state of every channel afterwards is the one :meth:`sdft` leaves; ``every_next_first`` gives the next call's
         ``first``."""
         self.api.clear()
-        every, first = int(every), int(first)
-        bin0, nb = (0, self.dftsize) if bins is None else (int(bins[0]), int(bins[1]))
-        if every < 1 or first < 0:
-            raise ValueError(f"every must be >= 1 and first >= 0, got every={every}, first={first}")
-        if bin0 < 0 or nb < 1 or bin0 + nb > self.dftsize:
-            raise ValueError(f"bins = (bin0, nbins) must select at least one of the {self.dftsize} bins, got {(bin0, nb)}")
+        every, first, bin0, nb = _grid_args(self.dftsize, every, first, bins)
         nout = self.mix_outputs
         if nout == 0:
             raise ValueError("no mix is installed: call set_mix first")
-        cdtype = np.dtype(self.fdx)
-        if _is_tensor(x):
-            torch = _torch()
-            n = self._shape_x(x.shape)
-            self._check_tensor(x, "samples", self.td)
-            rows = every_rows(n, every, first)
-            shape = (nout, rows, nb)
-            if out is None:
-                out = torch.empty(shape, dtype=getattr(torch, cdtype.name), device=x.device)
-            self._check_tensor(out, "out", cdtype, shape)
-            got = self.api.sdft_mix_n(self._p, n, C.c_void_p(x.data_ptr()), every, first, bin0, nb, C.c_void_p(out.data_ptr() if rows else None))
-        else:
-            x = np.ascontiguousarray(x, dtype=self.td)
-            n = self._shape_x(x.shape)
-            rows = every_rows(n, every, first)
-            shape = (nout, rows, nb)
-            if out is None:
-                out = np.empty(shape, dtype=cdtype)
-            assert out.flags.c_contiguous and out.shape == shape and out.dtype == cdtype
-            got = self.api.sdft_mix_n(self._p, n, C.c_void_p(x.ctypes.data), every, first, bin0, nb, C.c_void_p(out.ctypes.data if rows else None))
-        if got < 0:
-            self.api.check()
-            raise SdftHipError("sdft_hip_sdft_mix_n failed")
-        self.api.check()
-        assert got == rows, (got, rows)
-        return out
+        return self._grid_call("sdft_mix_n", x, every_rows, every, first, (bin0, nb), nout, nb, self.fdx, out)
 
     def power_sum(self, x, every: int = 1, first: int = 0, bins=None, out=None):
         """Pooled power analysis (``sdft_hip_sdft_power_sum_n``): the grid points ``first``, ``first + every``, ... cut the n samples
@@ -586,37 +457,8 @@ class SDFT:
         ``first`` is :func:`every_next_first`.  Sums, not means: divide a row by its window's length for a mean.  The plan's state
         advances over all n samples and all bins, as with :meth:`sdft`."""
         self.api.clear()
-        every, first = int(every), int(first)
-        bin0, nb = (0, self.dftsize) if bins is None else (int(bins[0]), int(bins[1]))
-        if every < 1 or first < 0:
-            raise ValueError(f"every must be >= 1 and first >= 0, got every={every}, first={first}")
-        if bin0 < 0 or nb < 1 or bin0 + nb > self.dftsize:
-            raise ValueError(f"bins = (bin0, nbins) must select at least one of the {self.dftsize} bins, got {(bin0, nb)}")
-        if _is_tensor(x):
-            torch = _torch()
-            n = self._shape_x(x.shape)
-            self._check_tensor(x, "samples", self.td)
-            rows = power_sum_rows(n, every, first)
-            shape = (rows, nb) if x.dim() == 1 else (self.channels, rows, nb)
-            if out is None:
-                out = torch.empty(shape, dtype=getattr(torch, np.dtype(self.fd).name), device=x.device)
-            self._check_tensor(out, "out", self.fd, shape)
-            got = self.api.sdft_power_sum_n(self._p, n, C.c_void_p(x.data_ptr()), every, first, bin0, nb, C.c_void_p(out.data_ptr() if rows else None))
-        else:
-            x = np.ascontiguousarray(x, dtype=self.td)
-            n = self._shape_x(x.shape)
-            rows = power_sum_rows(n, every, first)
-            shape = (rows, nb) if x.ndim == 1 else (self.channels, rows, nb)
-            if out is None:
-                out = np.empty(shape, dtype=self.fd)
-            assert out.flags.c_contiguous and out.shape == shape and out.dtype == self.fd
-            got = self.api.sdft_power_sum_n(self._p, n, C.c_void_p(x.ctypes.data), every, first, bin0, nb, C.c_void_p(out.ctypes.data if rows else None))
-        if got < 0:
-            self.api.check()
-            raise SdftHipError("sdft_hip_sdft_power_sum_n failed")
-        self.api.check()
-        assert got == rows, (got, rows)
-        return out
+        every, first, bin0, nb = _grid_args(self.dftsize, every, first, bins)
+        return self._grid_call("sdft_power_sum_n", x, power_sum_rows, every, first, (bin0, nb), None, nb, self.fd, out)
 
     def power_peak(self, x, every: int = 1, first: int = 0, bins=None, hold="max", out=None):
         """Peak-hold analysis (``sdft_hip_sdft_power_peak_n``): :meth:`power_sum`'s grid, windows, head row, shapes and pointers,
@@ -626,40 +468,10 @@ class SDFT:
         ``np.minimum`` of the two); the next call's ``first`` is :func:`every_next_first`.  The plan's state advances over all n
         samples and all bins, as with :meth:`sdft`."""
         self.api.clear()
-        every, first = int(every), int(first)
-        bin0, nb = (0, self.dftsize) if bins is None else (int(bins[0]), int(bins[1]))
-        if every < 1 or first < 0:
-            raise ValueError(f"every must be >= 1 and first >= 0, got every={every}, first={first}")
-        if bin0 < 0 or nb < 1 or bin0 + nb > self.dftsize:
-            raise ValueError(f"bins = (bin0, nbins) must select at least one of the {self.dftsize} bins, got {(bin0, nb)}")
+        every, first, bin0, nb = _grid_args(self.dftsize, every, first, bins)
         if hold not in HOLDS:
             raise ValueError(f"hold must be 'max' (0) or 'min' (1), got {hold!r}")
-        hold = HOLDS[hold]
-        if _is_tensor(x):
-            torch = _torch()
-            n = self._shape_x(x.shape)
-            self._check_tensor(x, "samples", self.td)
-            rows = power_sum_rows(n, every, first)
-            shape = (rows, nb) if x.dim() == 1 else (self.channels, rows, nb)
-            if out is None:
-                out = torch.empty(shape, dtype=getattr(torch, np.dtype(self.fd).name), device=x.device)
-            self._check_tensor(out, "out", self.fd, shape)
-            got = self.api.sdft_power_peak_n(self._p, n, C.c_void_p(x.data_ptr()), every, first, bin0, nb, hold, C.c_void_p(out.data_ptr() if rows else None))
-        else:
-            x = np.ascontiguousarray(x, dtype=self.td)
-            n = self._shape_x(x.shape)
-            rows = power_sum_rows(n, every, first)
-            shape = (rows, nb) if x.ndim == 1 else (self.channels, rows, nb)
-            if out is None:
-                out = np.empty(shape, dtype=self.fd)
-            assert out.flags.c_contiguous and out.shape == shape and out.dtype == self.fd
-            got = self.api.sdft_power_peak_n(self._p, n, C.c_void_p(x.ctypes.data), every, first, bin0, nb, hold, C.c_void_p(out.ctypes.data if rows else None))
-        if got < 0:
-            self.api.check()
-            raise SdftHipError("sdft_hip_sdft_power_peak_n failed")
-        self.api.check()
-        assert got == rows, (got, rows)
-        return out
+        return self._grid_call("sdft_power_peak_n", x, power_sum_rows, every, first, (bin0, nb, HOLDS[hold]), None, nb, self.fd, out)
 
     def lag_sum(self, samples, every: int, first: int = 0, band=None, out=None):
         """Lag-product analysis (``sdft_hip_sdft_lag_sum_n``): the sum of ``X[t] * conj(X[t - 1])`` over the windows
@@ -670,39 +482,8 @@ class SDFT:
         :func:`lag_frequency` turns the sums into frequencies.  Head row, streaming and sums-not-means as with :meth:`power_sum`.
         The plan's state advances over all n samples and all bins, as with :meth:`sdft`."""
         self.api.clear()
-        x = samples
-        every, first = int(every), int(first)
-        bin0, nb = (0, self.dftsize) if band is None else (int(band[0]), int(band[1]))
-        if every < 1 or first < 0:
-            raise ValueError(f"every must be >= 1 and first >= 0, got every={every}, first={first}")
-        if bin0 < 0 or nb < 1 or bin0 + nb > self.dftsize:
-            raise ValueError(f"band = (bin0, nbins) must select at least one of the {self.dftsize} bins, got {(bin0, nb)}")
-        cdtype = np.dtype(np.complex64 if np.dtype(self.fd) == np.float32 else np.complex128)
-        if _is_tensor(x):
-            torch = _torch()
-            n = self._shape_x(x.shape)
-            self._check_tensor(x, "samples", self.td)
-            rows = power_sum_rows(n, every, first)
-            shape = (rows, nb) if x.dim() == 1 else (self.channels, rows, nb)
-            if out is None:
-                out = torch.empty(shape, dtype=getattr(torch, cdtype.name), device=x.device)
-            self._check_tensor(out, "out", cdtype, shape)
-            got = self.api.sdft_lag_sum_n(self._p, n, C.c_void_p(x.data_ptr()), every, first, bin0, nb, C.c_void_p(out.data_ptr() if rows else None))
-        else:
-            x = np.ascontiguousarray(x, dtype=self.td)
-            n = self._shape_x(x.shape)
-            rows = power_sum_rows(n, every, first)
-            shape = (rows, nb) if x.ndim == 1 else (self.channels, rows, nb)
-            if out is None:
-                out = np.empty(shape, dtype=cdtype)
-            assert out.flags.c_contiguous and out.shape == shape and out.dtype == cdtype
-            got = self.api.sdft_lag_sum_n(self._p, n, C.c_void_p(x.ctypes.data), every, first, bin0, nb, C.c_void_p(out.ctypes.data if rows else None))
-        if got < 0:
-            self.api.check()
-            raise SdftHipError("sdft_hip_sdft_lag_sum_n failed")
-        self.api.check()
-        assert got == rows, (got, rows)
-        return out
+        every, first, bin0, nb = _grid_args(self.dftsize, every, first, band, word="band")
+        return self._grid_call("sdft_lag_sum_n", samples, power_sum_rows, every, first, (bin0, nb), None, nb, self.fdx, out)
 
     def isdft(self, dfts, out=None):
         """Synthesise samples from a DFT matrix (n, dftsize) [(channels, n, dftsize)]."""

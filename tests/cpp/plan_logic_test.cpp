@@ -889,6 +889,43 @@ static void test_process_shapes()
   CHECK(r.seg == 32768, "free memory unknown: %zu rows", r.seg);
 }
 
+// grid_segment against the lines the nine grid entry points used to carry inline (written out here), over a small exhaustive table
+static void test_grid_segment()
+{
+  const size_t row_bytes = 3 * 2 * 15 * 8, sample_row_bytes = 3 * 4;      // three channels, a band of 15 complex doubles, float samples
+  int one = 0, two = 0, many = 0;
+  for (size_t n : {(size_t)1, (size_t)7, (size_t)64, (size_t)1000})
+    for (size_t every_asked : {(size_t)1, (size_t)3, (size_t)64, n, n + 1})
+    {
+      const size_t every = std::min(every_asked, n);          // (the entry points clamp every to n)
+      for (size_t first : {(size_t)0, (size_t)5, every, every + 1})
+      {
+        const size_t rows = (n + every - 1) / every + 1;
+        // one segment; two (half the rows, or half the samples where these are what is staged); one row or one hop per segment
+        for (size_t stage_bytes : {(size_t)1 << 30, std::max(rows * row_bytes / 2, n * sample_row_bytes / 2), row_bytes})
+          for (int xd = 0; xd < 2; ++xd)
+            for (int od = 0; od < 2; ++od)
+              for (int whole = 0; whole < 2; ++whole)
+              {
+                size_t seg = n;
+                if (!od) seg = std::min(seg, stage_rows(n, row_bytes, stage_bytes) * every);
+                if (!xd) seg = std::min(seg, std::max<size_t>((size_t)kHopSamples, stage_rows(n, sample_row_bytes, stage_bytes)));
+                if (whole && seg < n && seg > every && first % every == 0) seg -= seg % every;
+                const size_t got = grid_segment(n, every, first, row_bytes, sample_row_bytes, stage_bytes, xd != 0, od != 0, whole != 0);
+                CHECK(got == seg, "grid_segment: n %zu every %zu first %zu stage %zu xd %d od %d whole %d: %zu, the inline lines give %zu", n, every, first, stage_bytes, xd, od, whole, got, seg);
+                CHECK(got >= 1 && got <= n, "a segment is 1 ... n samples: %zu of %zu", got, n);
+                if (xd && od) CHECK(got == n, "device memory on both sides: one segment");
+                if (whole && got < n && got > every && first % every == 0) CHECK(got % every == 0, "whole windows: %zu of %zu", got, every);
+                const size_t segments = (n + got - 1) / got;
+                if (segments == 1) ++one; else if (segments == 2) ++two; else ++many;
+              }
+      }
+    }
+  CHECK(one && two && many, "the table reaches one, two and many segments: %d %d %d", one, two, many);
+  // the lag-product call's rule is this one with the plan's channels for the pairs
+  CHECK(lag_sum_segment(1000, 7, 5, 3, 15, 8, 4, row_bytes, false, false) == grid_segment(1000, 7, 5, row_bytes, sample_row_bytes, row_bytes, false, false, true), "lag_sum_segment");
+}
+
 // nanoseconds per decision over the named shapes (argument "time")
 static void time_routes()
 {
@@ -932,6 +969,7 @@ int main(int argc, char** argv)
   test_host_shapes();
   test_process_routes();
   test_process_shapes();
+  test_grid_segment();
   if (failures) { fprintf(stderr, "%d failure(s)\n", failures); return 1; }
   printf("plan logic: all properties hold\n");
   return 0;
