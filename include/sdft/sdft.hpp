@@ -39,6 +39,8 @@ const char* sdft_hip_last_error(void);
                                        std::size_t bin0, std::size_t nbins, void* sums);                               \
   long sdft_hip_sdft_power_peak_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, \
                                         std::size_t bin0, std::size_t nbins, int hold, void* peaks);                   \
+  long sdft_hip_sdft_power_moments_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, \
+                                           std::size_t bin0, std::size_t nbins, void* moments);                        \
   int sdft_hip_set_filterbank_##SUF(void* plan, std::size_t nbands, const std::size_t* band_bin0, const std::size_t* band_nbins, \
                                     const void* weights);                                                               \
   std::size_t sdft_hip_filterbank_bands_##SUF(const void* plan);                                                       \
@@ -101,6 +103,7 @@ namespace sdft
       static long sdft_power_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_power_n_##SUF(p, n, x, e, f, b, k, d); } \
       static long sdft_power_sum_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_power_sum_n_##SUF(p, n, x, e, f, b, k, d); } \
       static long sdft_power_peak_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, int h, void* d) { return sdft_hip_sdft_power_peak_n_##SUF(p, n, x, e, f, b, k, h, d); } \
+      static long sdft_power_moments_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_power_moments_n_##SUF(p, n, x, e, f, b, k, d); } \
       static int set_filterbank(void* p, std::size_t nb, const std::size_t* b0, const std::size_t* bn, const void* w) { return sdft_hip_set_filterbank_##SUF(p, nb, b0, bn, w); } \
       static std::size_t filterbank_bands(const void* p) { return sdft_hip_filterbank_bands_##SUF(p); } \
       static long sdft_filterbank_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, void* d) { return sdft_hip_sdft_filterbank_n_##SUF(p, n, x, e, f, d); } \
@@ -251,6 +254,27 @@ namespace sdft
       {
         const char* e = sdft_hip_last_error();
         throw std::runtime_error(std::string("sdft_hip_sdft_power_peak_n: ") + (e ? e : "failed"));
+      }
+      return static_cast<std::size_t>(rows);
+    }
+
+    /**
+     * Power-moments analysis (sdft_hip_sdft_power_moments_n): power_sum()'s grid, windows, head row and pointers; out is dense
+     * (rows, nbins, 2) [(channels, rows, nbins, 2)]: per window and bin bin0 <= k < bin0 + nbins the pair (s1, s2), s1 the sum of
+     * power()'s every == 1 values p over the window -- power_sum()'s value bit for bit -- and s2 the sum of fl(p * p).  Sums, not
+     * means; first > 0 makes row 0 the head window [0, first), which completes the previous call's last row (add both
+     * components); the next call's first is sdft_every()'s.  Consecutive sliding-DFT rows overlap in all but one sample, so a
+     * detector built on the two sums is calibrated on the host's own noise.  The plan's state advances over all samples and all
+     * bins.  Returns the number of rows written.
+     **/
+    std::size_t power_moments(const std::size_t nsamples, const T* samples, const std::size_t every, const std::size_t first,
+                              const std::size_t bin0, const std::size_t nbins, F* const out)
+    {
+      const long rows = api::sdft_power_moments_n(plan_, nsamples, samples, every, first, bin0, nbins, out);
+      if (rows < 0)
+      {
+        const char* e = sdft_hip_last_error();
+        throw std::runtime_error(std::string("sdft_hip_sdft_power_moments_n: ") + (e ? e : "failed"));
       }
       return static_cast<std::size_t>(rows);
     }

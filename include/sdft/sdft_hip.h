@@ -255,6 +255,50 @@ long sdft_hip_sdft_power_peak_n(sdft_t* sdft, const sdft_size_t nsamples, const 
                                 const sdft_size_t bin0, const sdft_size_t nbins,
                                 const int hold, sdft_fd_t* peaks) SDFT_HIP_SYMBOL(sdft_power_peak_n);
 
+/* ---- power-moments analysis ------------------------------------------------------------------------
+   The one statistic of the power that no pooled output yields because it is not linear in it: the second moment.  With the sum
+   of the power it gives the variance of the power per bin, the spectral kurtosis (the RFI flagger of radio astronomy, the
+   transient and bearing-fault detector of vibration analysis, a stationarity test on a PSD estimate) and the variance of a Welch
+   estimate -- from ONE recurrence, without storing a power per sample.
+   sdft_hip_sdft_power_moments_n takes its grid, windows, head row, rows = (first > 0 && nsamples > 0 ? 1 : 0) + (rows of
+   sdft_hip_sdft_every_n), the next call's first, the band, every > nsamples and the pointer rules (host or device memory; option
+   "async" applies to device pointers) from sdft_hip_sdft_power_sum_n, unchanged.  moments is [rows][nbins][2] of sdft_fd_t, dense,
+   aligned to sizeof(sdft_fd_t) only; batched plans: samples [channels][nsamples], moments [channels][rows][nbins][2].  The pair of
+   a window and a bin holds s1 at [..][0] and s2 at [..][1]:
+     p  = the value sdft_hip_sdft_power_n stores at every == 1, first == 0:  fl( fl(re*re) + fl(im*im) )
+     q  = fl(p * p)
+     s1 = the sum of p over the window, formed exactly as sdft_hip_sdft_power_sum_n forms it
+     s2 = the sum of q, accumulated in sdft_fd_t in the same order
+   No fused multiply-add anywhere and no floating-point atomics; pieces of a window that a time chunk cuts are added in ascending
+   time order.  Sums are returned, not means; with first > 0, row 0 completes the previous call's last row and the host adds both
+   components.  q overflows in IEEE fashion (FD float: p > 1.8e19) and gives inf; nothing else is done about it.
+   Six things are promised.
+   (1) The same plan, options and input give the same bits on every run.
+   (2) moments[..][0] is sdft_hip_sdft_power_sum_n's output bit for bit, for the same plan, options, samples, grid and band, on
+       every route, as long as both calls cut time into chunks of the same length ("last_chunk_len") and run as one segment: true
+       of device pointers, and of host memory within "stage_bytes".  The call takes that call's chunk choice and none of its own.
+   (3) At every == 1, first == 0, s1 is sdft_hip_sdft_power_n's value and s2 is fl(p * p) of it, bit for bit, wherever sdft_sdft_n
+       is bit-identical to the reference (FD float, FD double with option "carry" = 1, calls shorter than 512 samples) -- for any
+       cut of time into chunks, any host staging and any cut of a stream into calls.  On the other routes they are those
+       expressions on what sdft_hip_sdft_power_n stores on a twin plan that cuts time alike.
+   (4) On the bit-identical routes and for other grids, with L the window's length, u = 2^-24 (float) or 2^-53 (double),
+       gamma_n = n u / (1 - n u), and S1, S2 the exact sums of the sdft_fd_t terms p and q (all of them non-negative):
+       |s1 - S1| <= gamma_(L-1) * S1   and   |s2 - S2| <= gamma_(L-1) * S2.
+   (5) On the other routes sdft_hip_sdft_power_n's term deviation comes on top: with pmax the call's largest power and
+       delta = 2.1e-11 * pmax,  L * delta  for s1 (as the pooled call has it) and  L * delta * (2 * pmax + delta)  for s2
+       (from |p'^2 - p^2| = |p' - p| * |p' + p|).
+   (6) The stream state of every channel is afterwards the one sdft_sdft_n of the same samples leaves -- bins outside the band
+       step every sample too.  Any other entry point may follow.
+   Consecutive rows of a sliding DFT overlap in all but one sample: an estimator built on s1 and s2 (the spectral kurtosis) keeps
+   its mean for Gaussian noise, but not the variance a textbook derives for independent spectra.
+   The call is never resident, pipelined or fused and always runs its own kernel ("last_kernel" = 13).  Returns the number of rows
+   written (0 only for nsamples == 0), or -1 with sdft_hip_last_error() set and the stream state untouched: a NULL plan,
+   every == 0, nbins == 0, bin0 + nbins > dftsize, moments == NULL with rows > 0, or a workspace that cannot be reserved. */
+long sdft_hip_sdft_power_moments_n(sdft_t* sdft, const sdft_size_t nsamples, const sdft_td_t* samples,
+                                   const sdft_size_t every, const sdft_size_t first,
+                                   const sdft_size_t bin0, const sdft_size_t nbins,
+                                   sdft_fd_t* moments) SDFT_HIP_SYMBOL(sdft_power_moments_n);
+
 /* ---- filterbank analysis ---------------------------------------------------------------------------
    Pooling of |X|^2 over frequency: mel, Bark and fractional-octave band energies, or the total power of a row, without storing
    and re-reading the powers.  A filterbank belongs to the plan.  sdft_hip_set_filterbank installs (copies) one; all four pointers
@@ -590,7 +634,7 @@ double sdft_hip_time_hops(sdft_t* sdft, size_t hops, size_t hop, const sdft_td_t
    "relay_flow", "relay_groups", "chain_debug", "inverse_nt", "inverse_nt_skip_mb", "inverse_step", "inverse_ordered", "host_direct", "copy_streams", "prefix_cells", "array_group", "mix_group", "mix_block" (sdft_capi.inc names what each selects);
    get_option "test_hooks" = 1 in that build.
    get_option additionally answers "tiles", "bins_per_lane", "row_slots", "last_chunks",
-   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis, 6 pooled power analysis, 7 filterbank analysis, 8 pooled cross-spectrum analysis, 9 array covariance analysis, 10 channel-mix analysis, 11 peak-hold analysis) or 12 (lag-product analysis), "last_segments", "last_fused",
+   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis, 6 pooled power analysis, 7 filterbank analysis, 8 pooled cross-spectrum analysis, 9 array covariance analysis, 10 channel-mix analysis, 11 peak-hold analysis), 12 (lag-product analysis) or 13 (power-moments analysis), "last_segments", "last_fused",
    "last_filterbank_launches" (forward_filterbank_kernel launches of the last filterbank call, over all of its host segments: more than its carry segments once its pieces exceed the workspace bound),
    "last_chain", "last_fused_exact", "last_fused_fold", "last_process_path" (1 fused kernel, 2 hop pair, 3 two-pass),
    "last_self" (no pre-pass launch), "last_prefix" (long calls: one pre-pass launch, prefix_cells_kernel), "last_inverse_nt" / "last_inverse_skip" (what the last synthesis launch used: non-temporal loads, rows read with ordinary loads),

@@ -104,6 +104,9 @@ long SDFT_FN(sdft_power_sum_n)(void* p, size_t n, const SDFT_TD* x, size_t every
 // peak-hold analysis: the largest or the smallest of those powers over the windows of the grid; see sdft_hip.h
 long SDFT_FN(sdft_power_peak_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, size_t bin0, size_t nbins, int hold, SDFT_FD* peaks)
 { return SDFT_GRID_CALL(sdft_power_peak_n, n, x, every, first, bin0, nbins, hold, peaks); }
+// power-moments analysis: those powers and their squares, each summed over the windows of the grid; see sdft_hip.h
+long SDFT_FN(sdft_power_moments_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, size_t bin0, size_t nbins, SDFT_FD* moments)
+{ return SDFT_GRID_CALL(sdft_power_moments_n, n, x, every, first, bin0, nbins, moments); }
 // filterbank analysis: weighted band sums of those powers on the grid; see sdft_hip.h
 int SDFT_FN(set_filterbank)(void* p, size_t nbands, const size_t* band_bin0, const size_t* band_nbins, const SDFT_FD* weights)
 {

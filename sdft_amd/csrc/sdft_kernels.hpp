@@ -24,6 +24,9 @@
 //   sdft_forward_lag_sum.hpp K1l forward_lag_sum_kernel: the pooled power kernel with the cross-spectrum kernel's term between a row and
 //                          the row before it -- X[t] conj(X[t - 1]) of one channel, the previous row of a chunk's first sample
 //                          demodulated from the chunk's carry-in (sdft_hip_sdft_lag_sum_n)
+//   sdft_forward_power_moments.hpp K1q forward_power_moments_kernel: the pooled power kernel with a second accumulator per bin -- the
+//                          power and its square, each summed in registers over the windows of the grid and stored as a pair
+//                          (sdft_hip_sdft_power_moments_n)
 //   sdft_forward_covariance.hpp K1v forward_covariance_kernel: the cross-spectrum kernel with groups of channels in place of channels --
 //                          all pairs of an array by register blocks of G x G pairs (sdft_hip_sdft_covariance_n)
 //   sdft_forward_mix.hpp   K1m   forward_mix_kernel: forward_power_kernel's grid with the covariance kernel's groups of channels -- per-bin
@@ -66,6 +69,7 @@
 #include "sdft_forward_power_peak.hpp"
 #include "sdft_forward_cross_sum.hpp"
 #include "sdft_forward_lag_sum.hpp"
+#include "sdft_forward_power_moments.hpp"
 #include "sdft_forward_covariance.hpp"
 #include "sdft_forward_mix.hpp"
 #include "sdft_forward_filterbank.hpp"

@@ -205,7 +205,7 @@ class Plan
   long opt_prefix_cells = 1;     // test hook: the prefix-cell route of long calls (logic::ForwardQuery::prefix_cells)
   long last_prefix = 0;          // the last analysis call took it (one pre-pass launch: prefix_cells_kernel)
 
-  long last_kernel = 0;          // 1 = forward_kernel (independent tiles), 2 = forward_rows_kernel, 3 = hop, 4 = forward_every_kernel, 5 = forward_power_kernel, 6 = forward_pooled_power_kernel, 7 = forward_filterbank_kernel, 8 = forward_cross_sum_kernel, 9 = forward_covariance_kernel, 10 = forward_mix_kernel, 11 = forward_power_peak_kernel, 12 = forward_lag_sum_kernel
+  long last_kernel = 0;          // 1 = forward_kernel (independent tiles), 2 = forward_rows_kernel, 3 = hop, 4 = forward_every_kernel, 5 = forward_power_kernel, 6 = forward_pooled_power_kernel, 7 = forward_filterbank_kernel, 8 = forward_cross_sum_kernel, 9 = forward_covariance_kernel, 10 = forward_mix_kernel, 11 = forward_power_peak_kernel, 12 = forward_lag_sum_kernel, 13 = forward_power_moments_kernel
 
   // device-resident stream state
   DevBuf<fdx> d_tw, d_syn, d_wtab;
@@ -602,12 +602,14 @@ class Plan
   // FILTERBANK: filterbank analysis (sdft_filterbank_n) -- forward_filterbank_kernel stores the band sums of the plan's filterbank
   // CROSS_SUM: cross-spectrum analysis (sdft_cross_sum_n) -- forward_cross_sum_kernel sums A conj(B) of the plan's pairs over the grid's windows
   // LAG_SUM: lag-product analysis (sdft_lag_sum_n) -- forward_lag_sum_kernel sums X[t] conj(X[t - 1]) of every channel over those windows; cross has the plan's channels in the pairs' place and no items
+  // POWER_MOMENTS: power-moments analysis (sdft_power_moments_n) -- forward_power_moments_kernel sums the power and its square of every channel over those windows, as (s1, s2) pairs; cross as LAG_SUM's
   // COVARIANCE: covariance analysis (sdft_covariance_n) -- forward_covariance_kernel does that for all pairs of the plan's array, by blocks
   // MIX: channel-mix analysis (sdft_mix_n) -- forward_mix_kernel stores the weighted sums of the plan's mix on the grid
   struct ForwardCall
   {
     enum Kind : int { PLAIN = 0, FUSE = -1, EVERY = logic::FK_EVERY, POWER = logic::FK_POWER, POWER_SUM = logic::FK_POWER_SUM, FILTERBANK = logic::FK_FILTERBANK,
-                      CROSS_SUM = logic::FK_CROSS_SUM, COVARIANCE = logic::FK_COVARIANCE, MIX = logic::FK_MIX, POWER_PEAK = logic::FK_POWER_PEAK, LAG_SUM = logic::FK_LAG_SUM };
+                      CROSS_SUM = logic::FK_CROSS_SUM, COVARIANCE = logic::FK_COVARIANCE, MIX = logic::FK_MIX, POWER_PEAK = logic::FK_POWER_PEAK, LAG_SUM = logic::FK_LAG_SUM,
+                      POWER_MOMENTS = logic::FK_POWER_MOMENTS };
     Kind kind = PLAIN;
     int hold = 0;                                            // POWER_PEAK
     const FuseArgs<TD, FD>* fuse = nullptr;                  // FUSE
@@ -615,7 +617,7 @@ class Plan
     const PowerArgs<FD>* power = nullptr;                    // POWER
     const PowerSumArgs<FD>* psum = nullptr;                  // POWER_SUM, POWER_PEAK
     const FilterbankArgs<FD>* fbk = nullptr;                 // FILTERBANK
-    const CrossSumArgs<FD>* cross = nullptr;                 // CROSS_SUM, LAG_SUM
+    const CrossSumArgs<FD>* cross = nullptr;                 // CROSS_SUM, LAG_SUM, POWER_MOMENTS
     const CovarianceArgs<FD>* cov = nullptr;                 // COVARIANCE
     const MixArgs<FD>* mix = nullptr;                        // MIX
     static ForwardCall of(Kind k) { ForwardCall c; c.kind = k; return c; }
@@ -627,6 +629,7 @@ class Plan
     static ForwardCall filterbank(const FilterbankArgs<FD>& a) { ForwardCall c = of(FILTERBANK); c.fbk = &a; return c; }
     static ForwardCall cross_sum(const CrossSumArgs<FD>& a) { ForwardCall c = of(CROSS_SUM); c.cross = &a; return c; }
     static ForwardCall lag_sum(const CrossSumArgs<FD>& a) { ForwardCall c = of(LAG_SUM); c.cross = &a; return c; }
+    static ForwardCall power_moments(const CrossSumArgs<FD>& a) { ForwardCall c = of(POWER_MOMENTS); c.cross = &a; return c; }
     static ForwardCall covariance(const CovarianceArgs<FD>& a) { ForwardCall c = of(COVARIANCE); c.cov = &a; return c; }
     static ForwardCall channel_mix(const MixArgs<FD>& a) { ForwardCall c = of(MIX); c.mix = &a; return c; }
   };
@@ -678,6 +681,7 @@ class Plan
     q.filterbank = c.kind == ForwardCall::FILTERBANK;
     q.cross_sum = c.kind == ForwardCall::CROSS_SUM;
     q.lag_sum = c.kind == ForwardCall::LAG_SUM;
+    q.power_moments = c.kind == ForwardCall::POWER_MOMENTS;
     q.covariance = c.kind == ForwardCall::COVARIANCE;
     q.mix = c.kind == ForwardCall::MIX;
     q.power_every = q.power ? (size_t)c.power->every : q.filterbank ? (size_t)c.fbk->every : q.mix ? (size_t)c.mix->every : 1;
@@ -891,7 +895,7 @@ class Plan
     const FuseArgs<TD, FD>* const fuse = c.fuse;
     const size_t nb = nbins;
     const long chunks = r.chunks, segments = r.segments;
-    // cross-spectrum and lag-product analysis: the workspace of the windows a chunk boundary cuts (grown on demand, kept by the
+    // cross-spectrum, lag-product and power-moments analysis: the workspace of the windows a chunk boundary cuts (grown on demand, kept by the
     // plan); the work items take the channels' place in the launch
     CrossSumArgs<FD> cs{};
     if (c.cross)
@@ -1001,6 +1005,7 @@ class Plan
         }
         break;
       case K::LAG_SUM: if (!grid_fits(blocks)) return false; launch_forward_lag_sum(fa, cs, (unsigned)blocks); break;
+      case K::POWER_MOMENTS: if (!grid_fits(blocks)) return false; launch_forward_power_moments(fa, cs, (unsigned)blocks); break;
       case K::CROSS_SUM: if (!grid_fits(blocks)) return false; launch_forward_cross_sum(fa, cs, (unsigned)blocks); break;
       case K::COVARIANCE: if (!grid_fits(blocks)) return false; if (!launch_forward_covariance(fa, cv, (unsigned)blocks)) return false; break;
       case K::MIX: if (!grid_fits(blocks)) return false; if (!launch_forward_mix(fa, *c.mix, (unsigned)blocks)) return false; break;
@@ -1013,8 +1018,8 @@ class Plan
     }
     SDFT_TRY(hipGetLastError());
     // the rows a chunk boundary cut, from the workspace: per channel for the pooled power and the peak-hold call (which holds instead
-    // of adding); per pair for the cross-spectrum, the lag-product (its pairs are the plan's channels) and the covariance call,
-    // whose complex sums over nbins_out bins are real sums over 2 * nbins_out numbers -- the pooled power call's adder
+    // of adding); per pair for the cross-spectrum, the lag-product, the power-moments (their pairs are the plan's channels) and the covariance call,
+    // whose complex sums (or pairs of sums) over nbins_out bins are real sums over 2 * nbins_out numbers -- the pooled power call's adder
     if (chunks > 1 && (c.psum || c.cross || c.cov))
     {
       const PowerSumArgs<FD> pieces = c.psum ? ps

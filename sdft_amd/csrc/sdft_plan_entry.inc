@@ -106,14 +106,14 @@
     return true;
   }
 
-  // ---- grid analysis calls: sdft_every_n and its eight siblings -----------------------------------------------------------------
-  // What the nine share.  The stream state after a call is the one sdft_n leaves on the same samples.  A call is never resident,
+  // ---- grid analysis calls: sdft_every_n and its nine siblings -----------------------------------------------------------------
+  // What the ten share.  The stream state after a call is the one sdft_n leaves on the same samples.  A call is never resident,
   // pipelined or fused: whatever is in flight is retired / joined first, then one forward call on the plan's stream with the
   // call's own kernel (ForwardCall).  `rows` receives the row count.  Device samples and a device output take that one call; host
   // memory goes through device scratch in time segments of at most logic::grid_segment samples, each segment a call of its own
   // under the streaming contract, with its own first.
   // The every-grid calls (every, power, filterbank, mix) keep the rows of the samples first, first + every, ... < n; a segment
-  // keeps the rows of the grid that fall into it.  The pooled calls (power_sum, power_peak, cross_sum, lag_sum, covariance) write
+  // keeps the rows of the grid that fall into it.  The pooled calls (power_sum, power_peak, power_moments, cross_sum, lag_sum, covariance) write
   // one row per window the grid cuts the call into (logic::power_sum_window), row 0 the head window [0, first) when first > 0; a
   // segment that starts inside a window has a head row of its own, which is kept apart (the call's head buffer) and joined into
   // the row the segment before it ended with -- on the host for a host buffer, by a small kernel for a device buffer.
@@ -431,6 +431,21 @@
       const CrossSumArgs<FD> g{row0, row0_stride, rest, rest_stride, nullptr, nullptr, (unsigned)channels, (unsigned)channels,
                                p.grid.every, p.grid.first, (unsigned)bin0, (unsigned)nbins_out};
       return forward_device(p.m, p.td, p.td_stride, nullptr, 0, nullptr, ForwardCall::lag_sum(g));
+    });
+  }
+
+  // power-moments analysis (sdft_hip_sdft_power_moments_n): per channel the pairs (sum of the power, sum of its square) over the
+  // windows of the grid, dense [channels][rows][nbins_out][2] real numbers.  The lag-product call's host side -- the cross-spectrum
+  // call's arguments with the plan's channels in the pairs' place, its workspace, head and stage buffers, the pooled adders over
+  // 2 * nbins_out numbers -- and forward_power_moments_kernel on the pooled power call's route and chunk choice.
+  bool sdft_power_moments_n(size_t n, const TD* x, size_t every, size_t first, size_t bin0, size_t nbins_out, FD* moments, size_t& rows)
+  {
+    if (!grid_args("sdft_hip_sdft_power_moments_n", n, every, first, true, bin0, nbins_out, nullptr, true, moments, "moments", rows)) return false;
+    return pooled_grid_call(n, x, every, first, moments, rows, channels, 2 * nbins_out, d_cross_head, &d_cross_stage, kJoinAdd, grid_ready,
+                            [&](const GridPiece& p, FD* row0, size_t row0_stride, FD* rest, size_t rest_stride) {
+      const CrossSumArgs<FD> g{row0, row0_stride, rest, rest_stride, nullptr, nullptr, (unsigned)channels, (unsigned)channels,
+                               p.grid.every, p.grid.first, (unsigned)bin0, (unsigned)nbins_out};
+      return forward_device(p.m, p.td, p.td_stride, nullptr, 0, nullptr, ForwardCall::power_moments(g));
     });
   }
 

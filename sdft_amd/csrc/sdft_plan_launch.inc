@@ -395,6 +395,19 @@
       default:           hipLaunchKernelGGL((forward_lag_sum_kernel<FD, BPL, WIN_BOXCAR>), gr, b, 0, stream, fa, g); break;
     }
   }
+  // (g: likewise; a row of nbins_out (s1, s2) pairs in the place of a row of complex sums)
+  void launch_forward_power_moments(const ForwardArgs<FD>& fa, const CrossSumArgs<FD>& g, unsigned blocks)
+  {
+    constexpr int BPL = sizeof(fdx) == 16 ? 1 : 2;
+    const dim3 gr(blocks), b(kBlock);
+    switch (window)
+    {
+      case WIN_HANN:     hipLaunchKernelGGL((forward_power_moments_kernel<FD, BPL, WIN_HANN>), gr, b, 0, stream, fa, g); break;
+      case WIN_HAMMING:  hipLaunchKernelGGL((forward_power_moments_kernel<FD, BPL, WIN_HAMMING>), gr, b, 0, stream, fa, g); break;
+      case WIN_BLACKMAN: hipLaunchKernelGGL((forward_power_moments_kernel<FD, BPL, WIN_BLACKMAN>), gr, b, 0, stream, fa, g); break;
+      default:           hipLaunchKernelGGL((forward_power_moments_kernel<FD, BPL, WIN_BOXCAR>), gr, b, 0, stream, fa, g); break;
+    }
+  }
   // channels per group of a covariance call: the build's choice per FD type, or (test hook) a candidate of scripts/covariance_rates.py
   int array_group() const
   {

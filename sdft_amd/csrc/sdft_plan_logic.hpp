@@ -372,6 +372,17 @@ inline size_t lag_sum_slot(size_t channel, size_t chunks, size_t chunk, int slot
 inline size_t lag_channel_stride(size_t rows, size_t nbins_out) { return cross_pair_stride(rows, nbins_out); }
 // (the time segments of a call on host memory: lag_sum_segment, beside stage_rows)
 
+// ---- power-moments analysis (sdft_hip_sdft_power_moments_n) ---------------------------------------------------------------------
+// Row r of a channel holds, per bin of the band, the pair (s1, s2): the sum over the r-th window of the pooled power call's grid of
+// that call's term p, and the sum of q = fl(p * p).  A row of nbins_out pairs has the shape of the cross-spectrum call's row of
+// nbins_out complex sums, so rows, workspace and strides are that call's with the plan's channels in the pairs' place, as the
+// lag-product call has them -- on the pooled power call's route with ITS chunk choice (choose_power_sum_chunks, nothing of this
+// call's own): [..][0] has the pooled call's bits only while both calls cut time alike.
+inline size_t power_moments_workspace(size_t channels, size_t chunks, size_t nbins_out) { return cross_sum_workspace(std::max<size_t>(channels, 1), chunks, nbins_out); }
+inline size_t power_moments_slot(size_t channel, size_t chunks, size_t chunk, int slot, size_t nbins_out) { return cross_sum_slot(channel, chunks, chunk, slot, nbins_out); }
+inline size_t power_moments_channel_stride(size_t rows, size_t nbins_out) { return cross_pair_stride(rows, nbins_out); }
+// (the time segments of a call on host memory: power_moments_segment, beside stage_rows)
+
 // ---- array covariance analysis (sdft_hip_sdft_covariance_n) ------------------------------------------------------------------------
 // The array is an ordered list of nch distinct channels of the plan (sdft_hip_set_array); the call returns the cross-spectrum
 // call's sums for ALL pairs of its elements: the upper triangle in row-major order, element (i <= j) -- the pair of the channels
@@ -948,6 +959,7 @@ struct ForwardQuery
   bool power_sum = false;                 // pooled power analysis (forward_pooled_power_kernel)
   bool power_peak = false;                // peak-hold analysis (forward_power_peak_kernel): the pooled power call's route (never with power_sum)
   bool lag_sum = false;                   // lag-product analysis (forward_lag_sum_kernel): the pooled power call's route (never with power_sum or power_peak)
+  bool power_moments = false;             // power-moments analysis (forward_power_moments_kernel): the pooled power call's route and chunk choice (never with power_sum, power_peak or lag_sum)
   bool filterbank = false;                // filterbank analysis (forward_filterbank_kernel) on the grid of power_every
   bool cross_sum = false;                 // pooled cross-spectrum analysis (forward_cross_sum_kernel) of ...
   size_t cross_items = 0;                 // ... this many work items (logic::cross_items), which take the channels' place in the launch
@@ -963,7 +975,7 @@ struct ForwardQuery
        chain_L = 0, relay_flow = 1, segments = 0, xcd_map = 1, rows_f32 = 1, pipeline = 1;
   long prefix_cells = 1;                  // test hook: 0 = never the prefix-cell route, 1 = calls beyond kSelfMax, 2 = whatever the length
 };
-enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6, FK_FILTERBANK = 7, FK_CROSS_SUM = 8, FK_COVARIANCE = 9, FK_MIX = 10, FK_POWER_PEAK = 11, FK_LAG_SUM = 12 };     // = get_option "last_kernel"
+enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6, FK_FILTERBANK = 7, FK_CROSS_SUM = 8, FK_COVARIANCE = 9, FK_MIX = 10, FK_POWER_PEAK = 11, FK_LAG_SUM = 12, FK_POWER_MOMENTS = 13 };     // = get_option "last_kernel"
 // carries: the single chunk's are the stream state (delta_kernel copies it); pre-pass partial sums + scan (carries from the
 // closed-form table); the serial exact pass (carry_exact_kernel); the relay form of the exact pass (carry_relay_kernel)
 enum CarryForm : int { CARRY_STATE = 0, CARRY_SUMS = 1, CARRY_SERIAL = 2, CARRY_RELAY = 3 };
@@ -1011,8 +1023,8 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   ForwardRoute r;
   const size_t nb = q.nbins, span = 2 * nb, n = q.n, ch = std::max<size_t>(q.channels, 1);
   const bool pow2 = (span & (span - 1)) == 0;
-  // the decimated, the power-spectrogram, the pooled power, the peak-hold, the lag-product, the filterbank, the cross-spectrum, the covariance and the mix analysis have the tile form only
-  const bool grid = q.every || q.power || q.power_sum || q.power_peak || q.lag_sum || q.filterbank || q.cross_sum || q.covariance || q.mix;
+  // the decimated, the power-spectrogram, the pooled power, the peak-hold, the lag-product, the power-moments, the filterbank, the cross-spectrum, the covariance and the mix analysis have the tile form only
+  const bool grid = q.every || q.power || q.power_sum || q.power_peak || q.lag_sum || q.power_moments || q.filterbank || q.cross_sum || q.covariance || q.mix;
   // (channel, chunk) groups of a tile launch per chunk: the cross-spectrum, the covariance and the mix call's are their work items
   const size_t lanes = (q.cross_sum || q.covariance || q.mix) ? std::max<size_t>(q.cross_items, 1) : ch;
   const bool rows = !grid && rows_kernel_ok(nb, q.fdx_bytes, q.row_pointers, q.rows_kernel != 0, q.row_slots_max);
@@ -1040,12 +1052,12 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   {
     EveryQuery e;
     e.n = n; e.channels = lanes; e.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); e.exact = q.exact; e.forced_chunk = q.chunk; e.compute_units = q.compute_units;
-    c = (q.power_sum || q.power_peak || q.lag_sum || q.cross_sum || q.covariance) ? choose_power_sum_chunks(e) : (q.power || q.filterbank || q.mix) ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
+    c = (q.power_sum || q.power_peak || q.lag_sum || q.power_moments || q.cross_sum || q.covariance) ? choose_power_sum_chunks(e) : (q.power || q.filterbank || q.mix) ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
   }
   else c = choose_chunks(chunk_query(q, rows, r.pipelined));
   r.chunks = c.chunks; r.len = c.len;
   r.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); r.interior = interior_lanes(q.window, q.fdx_bytes, q.interior);
-  r.kernel = q.mix ? FK_MIX : q.covariance ? FK_COVARIANCE : q.cross_sum ? FK_CROSS_SUM : q.filterbank ? FK_FILTERBANK : q.lag_sum ? FK_LAG_SUM : q.power_peak ? FK_POWER_PEAK : q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
+  r.kernel = q.mix ? FK_MIX : q.covariance ? FK_COVARIANCE : q.cross_sum ? FK_CROSS_SUM : q.filterbank ? FK_FILTERBANK : q.power_moments ? FK_POWER_MOMENTS : q.lag_sum ? FK_LAG_SUM : q.power_peak ? FK_POWER_PEAK : q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
   if (r.chunks == 1 && q.hop_kernel && nb >= 2 && !q.fuse && !grid) { r.kernel = FK_HOP; return r; }
 
   // self-carried chunks: every workgroup derives its carry-in from the raw samples (fold + one FFT in LDS) and forms
@@ -1291,7 +1303,7 @@ inline size_t stage_rows(size_t n, size_t row_bytes, size_t stage_bytes)
   const size_t seg = std::max<size_t>(1, stage_bytes / std::max<size_t>(row_bytes, 1));
   return std::min(seg, std::max<size_t>(n, 1));
 }
-// A grid analysis call (sdft_every_n and its eight siblings) on host memory goes in time segments of at most this many samples:
+// A grid analysis call (sdft_every_n and its nine siblings) on host memory goes in time segments of at most this many samples:
 // the rows a segment writes (row_bytes each, all channels / pairs / outputs of a row together; one row per `every` samples) and
 // the samples it reads (sample_row_bytes per time step) stay within stage_bytes -- but a segment of host samples is never shorter
 // than a hop.  whole_windows (the pooled calls): where the grid allows it a segment is made of whole windows, so that no row is
@@ -1311,6 +1323,13 @@ inline size_t lag_sum_segment(size_t n, size_t every, size_t first, size_t chann
 {
   const size_t ch = std::max<size_t>(channels, 1);
   return grid_segment(n, every, first, ch * 2 * nbins_out * fd_bytes, ch * td_bytes, stage_bytes, samples_on_device, sums_on_device, true);
+}
+// the power-moments call's: the same bounds -- a row is channels * nbins_out pairs, twice the pooled call's bytes
+inline size_t power_moments_segment(size_t n, size_t every, size_t first, size_t channels, size_t nbins_out, size_t fd_bytes, size_t td_bytes,
+                                    size_t stage_bytes, bool samples_on_device, bool moments_on_device)
+{
+  const size_t ch = std::max<size_t>(channels, 1);
+  return grid_segment(n, every, first, ch * 2 * nbins_out * fd_bytes, ch * td_bytes, stage_bytes, samples_on_device, moments_on_device, true);
 }
 
 // ---- host memory: the route of an analysis or a synthesis call (Plan::sdft_n / isdft_n run it) -----------------------------

@@ -473,6 +473,30 @@ class SDFT:
             raise ValueError(f"hold must be 'max' (0) or 'min' (1), got {hold!r}")
         return self._grid_call("sdft_power_peak_n", x, power_sum_rows, every, first, (bin0, nb, HOLDS[hold]), None, nb, self.fd, out)
 
+    def power_moments(self, x, every: int = 1, first: int = 0, bins=None, out=None):
+        """Power-moments analysis (``sdft_hip_sdft_power_moments_n``): :meth:`power_sum`'s grid, windows, head row and pointers,
+        with two sums per window and bin -> real array of shape (rows, nbins, 2) [(channels, rows, nbins, 2) if batched] in the FD
+        dtype, numpy for numpy input, a device tensor for a device tensor.  ``[..., 0]`` is ``s1``, the sum of :meth:`power`'s
+        ``every = 1`` values ``p`` over the window -- :meth:`power_sum`'s value bit for bit --, ``[..., 1]`` is ``s2``, the sum of
+        ``p * p`` (rounded once, no fused multiply-add).  Sums, not means; with ``first > 0`` row 0 is the head window
+        ``[0, first)`` and completes the previous call's last row (add both components); the next call's ``first`` is
+        :func:`every_next_first`.  :func:`power_sum_lengths` gives the windows' lengths, :func:`power_variance` and
+        :func:`spectral_kurtosis` turn the sums into statistics.  Consecutive sliding-DFT rows overlap in all but one sample: the
+        kurtosis estimator keeps its unit mean for Gaussian noise, but not the variance a textbook derives for independent
+        spectra, so detection thresholds have to be calibrated on the host's own noise.  The plan's state advances over all n
+        samples and all bins, as with :meth:`sdft`."""
+        self.api.clear()
+        every, first, bin0, nb = _grid_args(self.dftsize, every, first, bins)
+        flat = None
+        if out is not None:
+            if tuple(out.shape[-2:]) != (nb, 2):
+                raise ValueError(f"out must end in the shape ({nb}, 2), got {tuple(out.shape)}")
+            if not (out.is_contiguous() if _is_tensor(out) else out.flags.c_contiguous):
+                raise ValueError("out must be contiguous")
+            flat = out.reshape(tuple(out.shape[:-2]) + (2 * nb,))
+        flat = self._grid_call("sdft_power_moments_n", x, power_sum_rows, every, first, (bin0, nb), None, 2 * nb, self.fd, flat)
+        return out if out is not None else flat.reshape(tuple(flat.shape[:-1]) + (nb, 2))
+
     def lag_sum(self, samples, every: int, first: int = 0, band=None, out=None):
         """Lag-product analysis (``sdft_hip_sdft_lag_sum_n``): the sum of ``X[t] * conj(X[t - 1])`` over the windows
         :meth:`power_sum` cuts the n samples into, for the bins ``band = (bin0, nbins)`` (``None``: all) -> complex array of shape
@@ -603,6 +627,54 @@ def power_sum_rows(n: int, every: int, first: int) -> int:
     """Rows a pooled power analysis call of n samples writes (sdft_hip_sdft_power_sum_n): the head window, if any, and one row per
     grid point."""
     return (1 if first > 0 and n > 0 else 0) + every_rows(n, every, first)
+
+
+def power_sum_lengths(n: int, every: int, first: int):
+    """The window lengths of the rows a pooled call of n samples writes (:meth:`SDFT.power_sum`, :meth:`SDFT.power_moments` and
+    their siblings), as an int64 array of ``power_sum_rows(n, every, first)`` entries: the head window ``[0, first)`` if
+    ``first > 0``, then one window of at most ``every`` samples per grid point, the last one ending with the call."""
+    n, every, first = int(n), int(every), int(first)
+    if every < 1 or first < 0 or n < 0:
+        raise ValueError(f"every must be >= 1, first >= 0 and n >= 0, got n={n}, every={every}, first={first}")
+    head = [min(first, n)] if first > 0 and n > 0 else []
+    starts = np.arange(first, n, every, dtype=np.int64) if first < n else np.zeros(0, dtype=np.int64)
+    return np.concatenate([np.asarray(head, dtype=np.int64), np.minimum(starts + every, n) - starts])
+
+
+def _moments(moments, lengths):
+    """(s1, s2, L) of :meth:`SDFT.power_moments`' output in float64, L shaped to broadcast against (..., rows, nbins)."""
+    if _is_tensor(moments):
+        moments = moments.detach().cpu().numpy()
+    m = np.asarray(moments).astype(np.float64)
+    if m.ndim < 3 or m.shape[-1] != 2:
+        raise ValueError(f"moments must be (..., rows, nbins, 2), got {m.shape}")
+    length = np.asarray(lengths, dtype=np.float64)
+    if length.ndim <= 1:
+        length = length.reshape(-1, 1)                       # one length per row (or one for all): over bins and channels
+    return m[..., 0], m[..., 1], length
+
+
+def power_variance(moments, lengths):
+    """The variance of the power per window and bin from :meth:`SDFT.power_moments`' sums: ``s2 / L - (s1 / L)**2``, in float64
+    (numpy; a device tensor is copied).  ``lengths`` holds one window length per row (:func:`power_sum_lengths`) and broadcasts
+    over bins and channels; rows that a stream cut are added by the caller first."""
+    s1, s2, length = _moments(moments, lengths)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = s1 / length
+        return s2 / length - mean * mean
+
+
+def spectral_kurtosis(moments, lengths):
+    """The spectral kurtosis estimator per window and bin from :meth:`SDFT.power_moments`' sums:
+    ``(L + 1) / (L - 1) * (L * s2 / s1**2 - 1)``, in float64 (numpy; a device tensor is copied); NaN where ``L < 2`` or
+    ``s1 == 0``.  ``lengths`` holds one window length per row (:func:`power_sum_lengths`) and broadcasts over bins and channels;
+    rows that a stream cut are added by the caller first.  Its mean is 1 for Gaussian noise.  Consecutive sliding-DFT rows
+    overlap in all but one sample, so the estimator's textbook variance, which assumes independent spectra, does NOT hold:
+    calibrate detection thresholds on the host's own noise."""
+    s1, s2, length = _moments(moments, lengths)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sk = (length + 1.0) / (length - 1.0) * (length * s2 / (s1 * s1) - 1.0)
+    return np.where((length < 2) | (s1 == 0), np.nan, sk)
 
 
 HOLDS = {"max": 0, "min": 1, 0: 0, 1: 1}                     # SDFT.power_peak's hold -> enum sdft_hip_hold
