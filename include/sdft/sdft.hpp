@@ -45,6 +45,7 @@ const char* sdft_hip_last_error(void);
                                     const void* weights);                                                               \
   std::size_t sdft_hip_filterbank_bands_##SUF(const void* plan);                                                       \
   long sdft_hip_sdft_filterbank_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, void* out); \
+  long sdft_hip_sdft_band_peak_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, void* peaks); \
   int sdft_hip_set_pairs_##SUF(void* plan, std::size_t npairs, const std::size_t* pair_a, const std::size_t* pair_b);    \
   std::size_t sdft_hip_pairs_##SUF(const void* plan);                                                                  \
   long sdft_hip_sdft_cross_sum_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, \
@@ -107,6 +108,7 @@ namespace sdft
       static int set_filterbank(void* p, std::size_t nb, const std::size_t* b0, const std::size_t* bn, const void* w) { return sdft_hip_set_filterbank_##SUF(p, nb, b0, bn, w); } \
       static std::size_t filterbank_bands(const void* p) { return sdft_hip_filterbank_bands_##SUF(p); } \
       static long sdft_filterbank_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, void* d) { return sdft_hip_sdft_filterbank_n_##SUF(p, n, x, e, f, d); } \
+      static long sdft_band_peak_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, void* d) { return sdft_hip_sdft_band_peak_n_##SUF(p, n, x, e, f, d); } \
       static int set_pairs(void* p, std::size_t np, const std::size_t* a, const std::size_t* b) { return sdft_hip_set_pairs_##SUF(p, np, a, b); } \
       static std::size_t pairs(const void* p) { return sdft_hip_pairs_##SUF(p); } \
       static long sdft_cross_sum_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_cross_sum_n_##SUF(p, n, x, e, f, b, k, d); } \
@@ -307,6 +309,24 @@ namespace sdft
       {
         const char* e = sdft_hip_last_error();
         throw std::runtime_error(std::string("sdft_hip_sdft_filterbank_n: ") + (e ? e : "failed"));
+      }
+      return static_cast<std::size_t>(rows);
+    }
+
+    /**
+     * Band-peak analysis (sdft_hip_sdft_band_peak_n): per band of the installed filterbank the largest weight * power over the
+     * band's bins and the bin that attains it, for the rows filterbank() would write; out is dense (rows, filterbank_bands(), 2):
+     * [..][0] the value, [..][1] the absolute bin as an exactly representable integer of F.  Among the rounded products v of a
+     * band in ascending bin order the pair is (v[i], i) with i the lowest bin of the largest value, or the lowest NaN bin if there
+     * is one (numpy's argmax).  The plan's state advances over all samples and all bins.  Returns the number of rows written.
+     **/
+    std::size_t band_peak(const std::size_t nsamples, const T* samples, const std::size_t every, const std::size_t first, F* const out)
+    {
+      const long rows = api::sdft_band_peak_n(plan_, nsamples, samples, every, first, out);
+      if (rows < 0)
+      {
+        const char* e = sdft_hip_last_error();
+        throw std::runtime_error(std::string("sdft_hip_sdft_band_peak_n: ") + (e ? e : "failed"));
       }
       return static_cast<std::size_t>(rows);
     }

@@ -341,6 +341,48 @@ long sdft_hip_sdft_filterbank_n(sdft_t* sdft, const sdft_size_t nsamples, const 
                                 const sdft_size_t every, const sdft_size_t first,
                                 sdft_fd_t* out) SDFT_HIP_SYMBOL(sdft_filterbank_n);
 
+/* ---- band-peak analysis ----------------------------------------------------------------------------
+   The question a sliding DFT is most often run for: which bin is the peak, in each band, at each row, and how large is it --
+   pitch and tone tracking, DTMF and FSK detection, dominant-frequency tracking, peak picking for sinusoidal modelling -- without
+   storing and re-reading a power per bin.  sdft_hip_sdft_band_peak_n uses the plan's installed filterbank
+   (sdft_hip_set_filterbank) and takes its grid, rows, streaming rule, the next call's first, every > nsamples and the pointer
+   rules (host or device memory; option "async" applies to device pointers; peaks may be NULL when the call keeps no row) from
+   sdft_hip_sdft_filterbank_n, unchanged.  peaks is [rows][nbands][2] of sdft_fd_t, dense, aligned to sizeof(sdft_fd_t) only;
+   batched plans: samples [channels][nsamples], peaks [channels][rows][nbands][2].  [..][0] is the value, [..][1] the absolute bin
+   index, stored as an exactly representable integer of sdft_fd_t; the call is refused when dftsize > 2^24 on an FD float plan.
+   The value, exactly.  Let p_k be what sdft_hip_sdft_power_n stores for the row and bin k, w_k the band's weight for that bin and
+   v_k = fl(w_k * p_k): one rounded product, no fused multiply-add.  The band's bins are scanned in ascending order:
+     (m, i) = (v_first, first bin)
+     for each later k:  if (v_k > m) || (v_k != v_k && m == m)  then (m, i) = (v_k, k)
+   That is the lowest bin that attains the largest value, the lowest NaN bin if any value is NaN, and the first bin's bits among
+   equal zeros of either sign: in numpy, i = np.argmax(v) and m = v[i].  The pieces of a band that a tile boundary of the plan's
+   geometry cuts are combined in ascending tile order by the same rule, the lower piece the held pair and the higher piece the
+   candidate; the rule is strict, so a tie across a tile boundary keeps the lower bin.
+   Six things are promised.
+   (1) The same plan, options and input give the same bits on every run: no atomics.
+   (2) A row's pair depends only on the plan, the filterbank and that row's powers -- not on nsamples, every, first, the time
+       chunking, the host staging, or where a stream was cut into calls.
+   (3) Wherever sdft_sdft_n is bit-identical to the reference (FD float, FD double with option "carry" = 1, calls shorter than 512
+       samples), value and bin are exactly the numpy expression on the reference's powers.  The value matches bit for bit; a
+       NaN's payload is unspecified.
+   (4) On the other routes value and bin are exactly that expression on what sdft_hip_sdft_power_n stores on a twin plan that cuts
+       time into chunks of the same length ("last_chunk_len").  With pmax the largest power of the call's grid the value lies
+       within 2.1e-11 * pmax * max|w| of the reference's (|max a - max b| <= max |a - b| and the power call's term deviation), and
+       the bin can differ from the reference's only among bins whose reference values lie within twice that of the maximum.
+   (5) A filterbank of dftsize one-bin bands of weight 1 returns sdft_hip_sdft_power_n's value bit for bit, with bin k, on every
+       route.
+   (6) The stream state of every channel is afterwards the one sdft_sdft_n of the same samples leaves.  Any other entry point may
+       follow.
+   Split bands pass through the filterbank call's plan-owned workspace with a pair per piece; a call whose workspace would exceed
+   64 MiB runs its time chunks in row segments (several launches that reuse the workspace), with the same bits and the same state.
+   The call is never resident, pipelined or fused and always runs its own kernel ("last_kernel" = 14).  Returns the number of rows
+   written (0 for nsamples == 0), or -1 with sdft_hip_last_error() set and the stream state untouched: a NULL plan, no filterbank
+   installed, every == 0, peaks == NULL with rows > 0, dftsize > 2^24 on an FD float plan, or a workspace that cannot be
+   reserved. */
+long sdft_hip_sdft_band_peak_n(sdft_t* sdft, const sdft_size_t nsamples, const sdft_td_t* samples,
+                               const sdft_size_t every, const sdft_size_t first,
+                               sdft_fd_t* peaks) SDFT_HIP_SYMBOL(sdft_band_peak_n);
+
 /* ---- pooled cross-spectrum analysis ----------------------------------------------------------------
    What relates the channels of a batched plan (sdft_hip_alloc_batch): the cross power spectral density
      S_ab[k] = sum over the samples t of a window of X_a[t][k] * conj(X_b[t][k])
@@ -634,8 +676,9 @@ double sdft_hip_time_hops(sdft_t* sdft, size_t hops, size_t hop, const sdft_td_t
    "relay_flow", "relay_groups", "chain_debug", "inverse_nt", "inverse_nt_skip_mb", "inverse_step", "inverse_ordered", "host_direct", "copy_streams", "prefix_cells", "array_group", "mix_group", "mix_block" (sdft_capi.inc names what each selects);
    get_option "test_hooks" = 1 in that build.
    get_option additionally answers "tiles", "bins_per_lane", "row_slots", "last_chunks",
-   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis, 6 pooled power analysis, 7 filterbank analysis, 8 pooled cross-spectrum analysis, 9 array covariance analysis, 10 channel-mix analysis, 11 peak-hold analysis), 12 (lag-product analysis) or 13 (power-moments analysis), "last_segments", "last_fused",
+   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis, 6 pooled power analysis, 7 filterbank analysis, 8 pooled cross-spectrum analysis, 9 array covariance analysis, 10 channel-mix analysis, 11 peak-hold analysis), 12 (lag-product analysis), 13 (power-moments analysis) or 14 (band-peak analysis), "last_segments", "last_fused",
    "last_filterbank_launches" (forward_filterbank_kernel launches of the last filterbank call, over all of its host segments: more than its carry segments once its pieces exceed the workspace bound),
+   "last_band_peak_launches" (its twin: forward_band_peak_kernel launches of the last band-peak call),
    "last_chain", "last_fused_exact", "last_fused_fold", "last_process_path" (1 fused kernel, 2 hop pair, 3 two-pass),
    "last_self" (no pre-pass launch), "last_prefix" (long calls: one pre-pass launch, prefix_cells_kernel), "last_inverse_nt" / "last_inverse_skip" (what the last synthesis launch used: non-temporal loads, rows read with ordinary loads),
    "array_group" (channels per group of a register block of sdft_hip_sdft_covariance_n),

@@ -62,6 +62,7 @@ def typed_signatures(combo: str):
         "set_filterbank": (C.c_int, [vp, sz, vp, vp, vp]),
         "filterbank_bands": (sz, [vp]),
         "sdft_filterbank_n": (C.c_long, [vp, sz, vp, sz, sz, vp]),
+        "sdft_band_peak_n": (C.c_long, [vp, sz, vp, sz, sz, vp]),
         "set_pairs": (C.c_int, [vp, sz, vp, vp]),
         "pairs": (sz, [vp]),
         "sdft_cross_sum_n": (C.c_long, [vp, sz, vp, sz, sz, sz, sz, vp]),

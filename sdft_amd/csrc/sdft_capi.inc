@@ -116,6 +116,9 @@ int SDFT_FN(set_filterbank)(void* p, size_t nbands, const size_t* band_bin0, con
 size_t SDFT_FN(filterbank_bands)(const void* p) { return p ? P(p)->filterbank_bands() : 0; }
 long SDFT_FN(sdft_filterbank_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, SDFT_FD* out)
 { return SDFT_GRID_CALL(sdft_filterbank_n, n, x, every, first, out); }
+// band-peak analysis: per band of that filterbank the largest weighted power and its bin on the grid; see sdft_hip.h
+long SDFT_FN(sdft_band_peak_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, SDFT_FD* peaks)
+{ return SDFT_GRID_CALL(sdft_band_peak_n, n, x, every, first, peaks); }
 // pooled cross-spectrum analysis: A conj(B) of the plan's channel pairs summed over the windows of the grid; see sdft_hip.h
 int SDFT_FN(set_pairs)(void* p, size_t npairs, const size_t* pair_a, const size_t* pair_b)
 {
@@ -270,6 +273,7 @@ long SDFT_FN(get_option)(const void* p, const char* key)
   if (!strcmp(key, "last_fused")) return q->last_fused;
   if (!strcmp(key, "last_segments")) return q->last_segments;
   if (!strcmp(key, "last_filterbank_launches")) return q->last_filterbank_launches;
+  if (!strcmp(key, "last_band_peak_launches")) return q->last_band_peak_launches;
   if (!strcmp(key, "row_slots")) return q->row_slots();
   if (!strcmp(key, "device")) return q->device;
   if (!strcmp(key, "last_chain")) return q->last_chain;

@@ -34,6 +34,9 @@
 //   sdft_forward_filterbank.hpp K1f forward_filterbank_kernel: the powers of a kept row go to a wave-private strip of LDS and the lanes
 //                          form the weighted sums of the pieces of the plan's bands that lie in the tile; filterbank_rows_kernel adds
 //                          the pieces of the bands a tile boundary cuts (sdft_hip_sdft_filterbank_n)
+//   sdft_forward_band_peak.hpp K1b forward_band_peak_kernel: the filterbank kernel with numpy's argmax rule in the place of the sum --
+//                          per piece the largest rounded product and its bin, as a pair; band_peak_rows_kernel joins the pieces of
+//                          the bands a tile boundary cuts in ascending tile order by the same rule (sdft_hip_sdft_band_peak_n)
 //   sdft_forward_hop.hpp   K1h   calls of one time chunk: forward_hop_kernel, forward_hop2_kernel (two waves per tile)
 //   sdft_ops.hpp           spectral operations of the fused call, the synthesis term (sdft.h:641-651), user_rows_kernel
 //   sdft_forward_rows.hpp  K1    forward_rows_kernel: one workgroup per (chunk, row), LDS edge exchange, lockstep row
@@ -73,6 +76,7 @@
 #include "sdft_forward_covariance.hpp"
 #include "sdft_forward_mix.hpp"
 #include "sdft_forward_filterbank.hpp"
+#include "sdft_forward_band_peak.hpp"
 #include "sdft_forward_hop.hpp"
 #include "sdft_ops.hpp"
 #include "sdft_forward_rows.hpp"

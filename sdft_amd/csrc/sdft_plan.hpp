@@ -205,7 +205,7 @@ class Plan
   long opt_prefix_cells = 1;     // test hook: the prefix-cell route of long calls (logic::ForwardQuery::prefix_cells)
   long last_prefix = 0;          // the last analysis call took it (one pre-pass launch: prefix_cells_kernel)
 
-  long last_kernel = 0;          // 1 = forward_kernel (independent tiles), 2 = forward_rows_kernel, 3 = hop, 4 = forward_every_kernel, 5 = forward_power_kernel, 6 = forward_pooled_power_kernel, 7 = forward_filterbank_kernel, 8 = forward_cross_sum_kernel, 9 = forward_covariance_kernel, 10 = forward_mix_kernel, 11 = forward_power_peak_kernel, 12 = forward_lag_sum_kernel, 13 = forward_power_moments_kernel
+  long last_kernel = 0;          // 1 = forward_kernel (independent tiles), 2 = forward_rows_kernel, 3 = hop, 4 = forward_every_kernel, 5 = forward_power_kernel, 6 = forward_pooled_power_kernel, 7 = forward_filterbank_kernel, 8 = forward_cross_sum_kernel, 9 = forward_covariance_kernel, 10 = forward_mix_kernel, 11 = forward_power_peak_kernel, 12 = forward_lag_sum_kernel, 13 = forward_power_moments_kernel, 14 = forward_band_peak_kernel
 
   // device-resident stream state
   DevBuf<fdx> d_tw, d_syn, d_wtab;
@@ -312,6 +312,7 @@ class Plan
   // last launch geometry (introspection for tests / bench)
   long last_chunks = 0, last_chunk_len = 0, last_tiles = 0, last_interior = 0, last_pipelined = 0;
   long last_filterbank_launches = 0;                         // forward_filterbank_kernel launches of the last filterbank call
+  long last_band_peak_launches = 0;                          // forward_band_peak_kernel launches of the last band-peak call
 
   bool create(size_t dftsize, int win, double lat, size_t nch)
   {
@@ -600,6 +601,7 @@ class Plan
   // POWER_SUM: pooled power analysis (sdft_power_sum_n) -- forward_pooled_power_kernel sums it over the grid's windows
   // POWER_PEAK: peak-hold analysis (sdft_power_peak_n) -- forward_power_peak_kernel holds its largest (hold 0) or smallest (hold 1) over those windows; psum as POWER_SUM's
   // FILTERBANK: filterbank analysis (sdft_filterbank_n) -- forward_filterbank_kernel stores the band sums of the plan's filterbank
+  // BAND_PEAK: band-peak analysis (sdft_band_peak_n) -- forward_band_peak_kernel stores per band of that filterbank the largest weighted power and its bin, as a pair; fbk as FILTERBANK's, a pair for a number
   // CROSS_SUM: cross-spectrum analysis (sdft_cross_sum_n) -- forward_cross_sum_kernel sums A conj(B) of the plan's pairs over the grid's windows
   // LAG_SUM: lag-product analysis (sdft_lag_sum_n) -- forward_lag_sum_kernel sums X[t] conj(X[t - 1]) of every channel over those windows; cross has the plan's channels in the pairs' place and no items
   // POWER_MOMENTS: power-moments analysis (sdft_power_moments_n) -- forward_power_moments_kernel sums the power and its square of every channel over those windows, as (s1, s2) pairs; cross as LAG_SUM's
@@ -609,14 +611,14 @@ class Plan
   {
     enum Kind : int { PLAIN = 0, FUSE = -1, EVERY = logic::FK_EVERY, POWER = logic::FK_POWER, POWER_SUM = logic::FK_POWER_SUM, FILTERBANK = logic::FK_FILTERBANK,
                       CROSS_SUM = logic::FK_CROSS_SUM, COVARIANCE = logic::FK_COVARIANCE, MIX = logic::FK_MIX, POWER_PEAK = logic::FK_POWER_PEAK, LAG_SUM = logic::FK_LAG_SUM,
-                      POWER_MOMENTS = logic::FK_POWER_MOMENTS };
+                      POWER_MOMENTS = logic::FK_POWER_MOMENTS, BAND_PEAK = logic::FK_BAND_PEAK };
     Kind kind = PLAIN;
     int hold = 0;                                            // POWER_PEAK
     const FuseArgs<TD, FD>* fuse = nullptr;                  // FUSE
     const EveryGrid* every = nullptr;                        // EVERY
     const PowerArgs<FD>* power = nullptr;                    // POWER
     const PowerSumArgs<FD>* psum = nullptr;                  // POWER_SUM, POWER_PEAK
-    const FilterbankArgs<FD>* fbk = nullptr;                 // FILTERBANK
+    const FilterbankArgs<FD>* fbk = nullptr;                 // FILTERBANK, BAND_PEAK
     const CrossSumArgs<FD>* cross = nullptr;                 // CROSS_SUM, LAG_SUM, POWER_MOMENTS
     const CovarianceArgs<FD>* cov = nullptr;                 // COVARIANCE
     const MixArgs<FD>* mix = nullptr;                        // MIX
@@ -627,6 +629,7 @@ class Plan
     static ForwardCall power_sum(const PowerSumArgs<FD>& a) { ForwardCall c = of(POWER_SUM); c.psum = &a; return c; }
     static ForwardCall power_peak(const PowerSumArgs<FD>& a, int hold) { ForwardCall c = of(POWER_PEAK); c.psum = &a; c.hold = hold; return c; }
     static ForwardCall filterbank(const FilterbankArgs<FD>& a) { ForwardCall c = of(FILTERBANK); c.fbk = &a; return c; }
+    static ForwardCall band_peak(const FilterbankArgs<FD>& a) { ForwardCall c = of(BAND_PEAK); c.fbk = &a; return c; }
     static ForwardCall cross_sum(const CrossSumArgs<FD>& a) { ForwardCall c = of(CROSS_SUM); c.cross = &a; return c; }
     static ForwardCall lag_sum(const CrossSumArgs<FD>& a) { ForwardCall c = of(LAG_SUM); c.cross = &a; return c; }
     static ForwardCall power_moments(const CrossSumArgs<FD>& a) { ForwardCall c = of(POWER_MOMENTS); c.cross = &a; return c; }
@@ -679,12 +682,13 @@ class Plan
     q.power_sum = c.kind == ForwardCall::POWER_SUM;
     q.power_peak = c.kind == ForwardCall::POWER_PEAK;
     q.filterbank = c.kind == ForwardCall::FILTERBANK;
+    q.band_peak = c.kind == ForwardCall::BAND_PEAK;
     q.cross_sum = c.kind == ForwardCall::CROSS_SUM;
     q.lag_sum = c.kind == ForwardCall::LAG_SUM;
     q.power_moments = c.kind == ForwardCall::POWER_MOMENTS;
     q.covariance = c.kind == ForwardCall::COVARIANCE;
     q.mix = c.kind == ForwardCall::MIX;
-    q.power_every = q.power ? (size_t)c.power->every : q.filterbank ? (size_t)c.fbk->every : q.mix ? (size_t)c.mix->every : 1;
+    q.power_every = q.power ? (size_t)c.power->every : (q.filterbank || q.band_peak) ? (size_t)c.fbk->every : q.mix ? (size_t)c.mix->every : 1;
     q.cross_items = c.cross ? c.cross->nitems : q.covariance ? c.cov->nitems : q.mix ? c.mix->nitems : 0;
     q.row_pointers = rows != nullptr;
     q.out = reinterpret_cast<uintptr_t>(out);
@@ -921,11 +925,12 @@ class Plan
       if (!d_psum_ws.reserve(logic::power_sum_workspace(channels, (size_t)chunks, ps.nbins_out))) return false;
       ps.ws = chunks > 1 ? d_psum_ws.p : nullptr;
     }
-    // filterbank analysis: the workspace of the bands a tile boundary cuts, [channels][rows of a launch][slots] (likewise); the
-    // chunks go in launches whose rows keep it within its bound (logic::filterbank_next_span)
+    // filterbank and band-peak analysis: the workspace of the bands a tile boundary cuts, [channels][rows of a launch][slots]
+    // (likewise) of numbers or of pairs; the chunks go in launches whose rows keep it within its bound (logic::filterbank_next_span)
     FilterbankArgs<FD> fb{};
     const FilterbankArgs<FD>* const fbk = c.fbk;
-    const size_t fb_rows = fbk ? logic::filterbank_segment_rows(channels, fbk->nslots, sizeof(FD)) : 0;
+    const bool peak = c.kind == K::BAND_PEAK;
+    const size_t fb_rows = !fbk ? 0 : peak ? logic::band_peak_segment_rows(channels, fbk->nslots, sizeof(FD)) : logic::filterbank_segment_rows(channels, fbk->nslots, sizeof(FD));
     if (fbk)
     {
       fb = *fbk;
@@ -936,7 +941,7 @@ class Plan
           const logic::FilterbankSpan sp = logic::filterbank_next_span(ja, j1, r.len, r.shift, n, (size_t)fb.every, (size_t)fb.first, fb_rows);
           most = std::max(most, sp.rows); ja = sp.jb;
         }
-      if (!d_fb_ws.reserve(logic::filterbank_workspace(channels, most, fb.nslots))) return false;
+      if (!d_fb_ws.reserve(peak ? logic::band_peak_workspace(channels, most, fb.nslots) : logic::filterbank_workspace(channels, most, fb.nslots))) return false;
       fb.ws = d_fb_ws.p;
     }
     if (!prof_begin(ST_FORWARD)) return false;
@@ -987,6 +992,7 @@ class Plan
         else launch_forward(fa, (unsigned)blocks);
         break;
       case K::FILTERBANK:
+      case K::BAND_PEAK:
         for (long ja = j0; ja < j1;)
         {
           const logic::FilterbankSpan sp = logic::filterbank_next_span(ja, j1, r.len, r.shift, n, (size_t)fb.every, (size_t)fb.first, fb_rows);
@@ -997,10 +1003,10 @@ class Plan
           const unsigned long long span_blocks = (fa.total_waves + kWavesPerBlock - 1) / kWavesPerBlock;
           if (!grid_fits(span_blocks)) return false;
           fb.ws_row0 = sp.row0; fb.ws_rows = sp.rows;
-          launch_forward_filterbank(fa, fb, (unsigned)span_blocks);
+          if (peak) launch_forward_band_peak(fa, fb, (unsigned)span_blocks); else launch_forward_filterbank(fa, fb, (unsigned)span_blocks);
           SDFT_TRY(hipGetLastError());
-          ++last_filterbank_launches;
-          if (fb.nsplits && sp.rows && !launch_filterbank_rows(fb)) return false;   // the split bands of these rows, before the next launch reuses the workspace
+          ++(peak ? last_band_peak_launches : last_filterbank_launches);
+          if (fb.nsplits && sp.rows && !(peak ? launch_band_peak_rows(fb) : launch_filterbank_rows(fb))) return false;   // the split bands of these rows, before the next launch reuses the workspace
           ja = sp.jb;
         }
         break;

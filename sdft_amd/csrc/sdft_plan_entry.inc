@@ -106,13 +106,13 @@
     return true;
   }
 
-  // ---- grid analysis calls: sdft_every_n and its nine siblings -----------------------------------------------------------------
-  // What the ten share.  The stream state after a call is the one sdft_n leaves on the same samples.  A call is never resident,
+  // ---- grid analysis calls: sdft_every_n and its ten siblings ------------------------------------------------------------------
+  // What the eleven share.  The stream state after a call is the one sdft_n leaves on the same samples.  A call is never resident,
   // pipelined or fused: whatever is in flight is retired / joined first, then one forward call on the plan's stream with the
   // call's own kernel (ForwardCall).  `rows` receives the row count.  Device samples and a device output take that one call; host
   // memory goes through device scratch in time segments of at most logic::grid_segment samples, each segment a call of its own
   // under the streaming contract, with its own first.
-  // The every-grid calls (every, power, filterbank, mix) keep the rows of the samples first, first + every, ... < n; a segment
+  // The every-grid calls (every, power, filterbank, band_peak, mix) keep the rows of the samples first, first + every, ... < n; a segment
   // keeps the rows of the grid that fall into it.  The pooled calls (power_sum, power_peak, power_moments, cross_sum, lag_sum, covariance) write
   // one row per window the grid cuts the call into (logic::power_sum_window), row 0 the head window [0, first) when first > 0; a
   // segment that starts inside a window has a head row of its own, which is kept apart (the call's head buffer) and joined into
@@ -327,6 +327,33 @@
       const FilterbankArgs<FD> g{at, at_rows * nbands, nullptr, 0, 0, p.grid.every, p.grid.first, d_fb_pieces.p, d_fb_tile0.p,
                                  d_fb_weights.p, d_fb_splits.p, (unsigned)nbands, (unsigned)l.nslots, (unsigned)l.splits.size()};
       return forward_device(p.m, p.td, p.td_stride, nullptr, 0, nullptr, ForwardCall::filterbank(g));
+    });
+  }
+
+  // band-peak analysis (sdft_hip_sdft_band_peak_n): per band of the installed filterbank the largest fl(weight * power) over the
+  // band's bins and the bin that attains it, of the rows of the grid, dense [channels][rows][nbands][2] real numbers --
+  // forward_band_peak_kernel, then band_peak_rows_kernel for the bands a tile boundary cuts, in the filterbank call's launches by
+  // rows with a pair per workspace slot (forward_rows_stage).  A unit row of every_grid_call is the 2 * nbands numbers of a row.
+  bool sdft_band_peak_n(size_t n, const TD* x, size_t every, size_t first, FD* peaks, size_t& rows)
+  {
+    static const char* fn = "sdft_hip_sdft_band_peak_n";
+    rows = 0;
+    const size_t nbands = filterbank_bands();
+    if (nbands == 0) { set_error(fn, "no filterbank is installed (sdft_hip_set_filterbank)"); return false; }
+    const char* const refused = logic::band_peak_bins_exact(nbins, sizeof(FD)) ? nullptr : "dftsize is beyond 2^24: a bin would not be an exact number of sdft_fd_t";
+    if (!grid_args(fn, n, every, first, false, 0, 0, refused, false, peaks, "peaks", rows)) return false;
+    last_band_peak_launches = 0;                             // (forward_rows_stage counts, over all host segments of the call)
+    auto ready = [&] {                                       // (option "interior" changed the tiles: the pieces are cut again)
+      if (fbank.interior == interior_lanes() || upload_filterbank(fbank)) return true;
+      fbank.interior = -1;
+      return false;
+    };
+    const size_t unit_row = logic::kBandPeakPair * nbands;
+    return every_grid_call(n, x, every, first, peaks, rows, channels, unit_row, ready, [&](const GridPiece& p, FD* at, size_t at_rows) {
+      const logic::FilterbankLayout& l = fbank.layout;
+      const FilterbankArgs<FD> g{at, at_rows * unit_row, nullptr, 0, 0, p.grid.every, p.grid.first, d_fb_pieces.p, d_fb_tile0.p,
+                                 d_fb_weights.p, d_fb_splits.p, (unsigned)nbands, (unsigned)l.nslots, (unsigned)l.splits.size()};
+      return forward_device(p.m, p.td, p.td_stride, nullptr, 0, nullptr, ForwardCall::band_peak(g));
     });
   }
 

@@ -370,6 +370,28 @@
     hipLaunchKernelGGL((filterbank_rows_kernel<FD>), dim3((unsigned)blocks), dim3(kBlock), 0, stream, g, (unsigned)channels);
     return true;
   }
+  // (g: the filterbank call's arguments, read with a pair where that call has a number: sdft_forward_band_peak.hpp)
+  void launch_forward_band_peak(const ForwardArgs<FD>& fa, const FilterbankArgs<FD>& g, unsigned blocks)
+  {
+    constexpr int BPL = sizeof(fdx) == 16 ? 1 : 2;
+    const dim3 gr(blocks), b(kBlock);
+    switch (window)
+    {
+      case WIN_HANN:     hipLaunchKernelGGL((forward_band_peak_kernel<FD, BPL, WIN_HANN>), gr, b, 0, stream, fa, g); break;
+      case WIN_HAMMING:  hipLaunchKernelGGL((forward_band_peak_kernel<FD, BPL, WIN_HAMMING>), gr, b, 0, stream, fa, g); break;
+      case WIN_BLACKMAN: hipLaunchKernelGGL((forward_band_peak_kernel<FD, BPL, WIN_BLACKMAN>), gr, b, 0, stream, fa, g); break;
+      default:           hipLaunchKernelGGL((forward_band_peak_kernel<FD, BPL, WIN_BOXCAR>), gr, b, 0, stream, fa, g); break;
+    }
+  }
+  // the bands a tile boundary cuts, joined from their pieces' pairs by the rule: one thread per (channel, row of the launch, split band)
+  bool launch_band_peak_rows(const FilterbankArgs<FD>& g)
+  {
+    const unsigned long long threads = (unsigned long long)channels * (unsigned long long)g.ws_rows * g.nsplits;
+    const unsigned long long blocks = (threads + kBlock - 1) / kBlock;
+    if (!grid_fits(blocks)) return false;
+    hipLaunchKernelGGL((band_peak_rows_kernel<FD>), dim3((unsigned)blocks), dim3(kBlock), 0, stream, g, (unsigned)channels);
+    return true;
+  }
   void launch_forward_cross_sum(const ForwardArgs<FD>& fa, const CrossSumArgs<FD>& g, unsigned blocks)
   {
     constexpr int BPL = sizeof(fdx) == 16 ? 1 : 2;

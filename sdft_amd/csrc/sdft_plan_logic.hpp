@@ -611,6 +611,23 @@ inline FilterbankSpan filterbank_next_span(long ja, long j1, long len, long shif
   return s;
 }
 
+// ---- band-peak analysis (sdft_hip_sdft_band_peak_n) -----------------------------------------------------------------------------
+// Per band of the installed filterbank and row of the filterbank call's grid the pair (m, i): with v_k = fl(w_k * p_k) over the
+// band's bins in ascending order, i = np.argmax(v) and m = v[i] -- the lowest bin of the largest value, the lowest NaN bin if any
+// value is NaN, the first bin's bits among equal zeros.  The pieces, the tile order, the slots and the launches by rows are the
+// filterbank call's (filterbank_layout, filterbank_next_span); a slot holds a pair, so the workspace bound takes two numbers per slot.
+// The rule is associative for ordered concatenation: the pieces of a split band, joined in ascending tile order with the lower
+// piece held and the higher the candidate, give the bits of one walk over the whole band, for every cut of bins into tiles.
+// The host's restatement of the rule (the kernels' band_peak_take; the tests hold it against np.argmax): is the candidate v, at a
+// higher bin than the held m, taken?
+template <typename T> inline bool band_peak_take(T m, T v) { return (v > m) || (v != v && m == m); }
+constexpr size_t kBandPeakPair = 2;                         // numbers per band of a row, and per workspace slot: value, bin
+inline size_t band_peak_segment_rows(size_t channels, size_t nslots, size_t fd_bytes, size_t bound_bytes = kFilterbankWorkspaceBytes)
+{ return filterbank_segment_rows(channels, nslots, kBandPeakPair * fd_bytes, bound_bytes); }
+inline size_t band_peak_workspace(size_t channels, size_t rows, size_t nslots) { return kBandPeakPair * filterbank_workspace(channels, rows, nslots); }
+// the bin is stored as a number of FD: every bin of the plan must be one exactly (FD float: dftsize <= 2^24)
+inline bool band_peak_bins_exact(size_t nbins, size_t fd_bytes) { return fd_bytes >= 8 ? nbins <= ((size_t)1 << 53) : nbins <= ((size_t)1 << 24); }
+
 // ---- exact carries, relay form: block length = seed distance -----------------------------------------------------------
 // divides 2N and the chunk length; L products live in L registers per lane (128 at FD float, 64 register pairs at FD double);
 // the seed table (fid at every L-th cursor) stays below 256 MiB.  0: no block length fits (serial pass).
@@ -961,6 +978,7 @@ struct ForwardQuery
   bool lag_sum = false;                   // lag-product analysis (forward_lag_sum_kernel): the pooled power call's route (never with power_sum or power_peak)
   bool power_moments = false;             // power-moments analysis (forward_power_moments_kernel): the pooled power call's route and chunk choice (never with power_sum, power_peak or lag_sum)
   bool filterbank = false;                // filterbank analysis (forward_filterbank_kernel) on the grid of power_every
+  bool band_peak = false;                 // band-peak analysis (forward_band_peak_kernel) on the grid of power_every: the filterbank call's route and chunk choice (never with filterbank)
   bool cross_sum = false;                 // pooled cross-spectrum analysis (forward_cross_sum_kernel) of ...
   size_t cross_items = 0;                 // ... this many work items (logic::cross_items), which take the channels' place in the launch
   bool covariance = false;                // array covariance analysis (forward_covariance_kernel): cross_items counts its block items (logic::covariance_items)
@@ -975,7 +993,7 @@ struct ForwardQuery
        chain_L = 0, relay_flow = 1, segments = 0, xcd_map = 1, rows_f32 = 1, pipeline = 1;
   long prefix_cells = 1;                  // test hook: 0 = never the prefix-cell route, 1 = calls beyond kSelfMax, 2 = whatever the length
 };
-enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6, FK_FILTERBANK = 7, FK_CROSS_SUM = 8, FK_COVARIANCE = 9, FK_MIX = 10, FK_POWER_PEAK = 11, FK_LAG_SUM = 12, FK_POWER_MOMENTS = 13 };     // = get_option "last_kernel"
+enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6, FK_FILTERBANK = 7, FK_CROSS_SUM = 8, FK_COVARIANCE = 9, FK_MIX = 10, FK_POWER_PEAK = 11, FK_LAG_SUM = 12, FK_POWER_MOMENTS = 13, FK_BAND_PEAK = 14 };     // = get_option "last_kernel"
 // carries: the single chunk's are the stream state (delta_kernel copies it); pre-pass partial sums + scan (carries from the
 // closed-form table); the serial exact pass (carry_exact_kernel); the relay form of the exact pass (carry_relay_kernel)
 enum CarryForm : int { CARRY_STATE = 0, CARRY_SUMS = 1, CARRY_SERIAL = 2, CARRY_RELAY = 3 };
@@ -1023,8 +1041,8 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   ForwardRoute r;
   const size_t nb = q.nbins, span = 2 * nb, n = q.n, ch = std::max<size_t>(q.channels, 1);
   const bool pow2 = (span & (span - 1)) == 0;
-  // the decimated, the power-spectrogram, the pooled power, the peak-hold, the lag-product, the power-moments, the filterbank, the cross-spectrum, the covariance and the mix analysis have the tile form only
-  const bool grid = q.every || q.power || q.power_sum || q.power_peak || q.lag_sum || q.power_moments || q.filterbank || q.cross_sum || q.covariance || q.mix;
+  // the decimated, the power-spectrogram, the pooled power, the peak-hold, the lag-product, the power-moments, the filterbank, the band-peak, the cross-spectrum, the covariance and the mix analysis have the tile form only
+  const bool grid = q.every || q.power || q.power_sum || q.power_peak || q.lag_sum || q.power_moments || q.filterbank || q.band_peak || q.cross_sum || q.covariance || q.mix;
   // (channel, chunk) groups of a tile launch per chunk: the cross-spectrum, the covariance and the mix call's are their work items
   const size_t lanes = (q.cross_sum || q.covariance || q.mix) ? std::max<size_t>(q.cross_items, 1) : ch;
   const bool rows = !grid && rows_kernel_ok(nb, q.fdx_bytes, q.row_pointers, q.rows_kernel != 0, q.row_slots_max);
@@ -1052,12 +1070,12 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   {
     EveryQuery e;
     e.n = n; e.channels = lanes; e.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); e.exact = q.exact; e.forced_chunk = q.chunk; e.compute_units = q.compute_units;
-    c = (q.power_sum || q.power_peak || q.lag_sum || q.power_moments || q.cross_sum || q.covariance) ? choose_power_sum_chunks(e) : (q.power || q.filterbank || q.mix) ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
+    c = (q.power_sum || q.power_peak || q.lag_sum || q.power_moments || q.cross_sum || q.covariance) ? choose_power_sum_chunks(e) : (q.power || q.filterbank || q.band_peak || q.mix) ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
   }
   else c = choose_chunks(chunk_query(q, rows, r.pipelined));
   r.chunks = c.chunks; r.len = c.len;
   r.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); r.interior = interior_lanes(q.window, q.fdx_bytes, q.interior);
-  r.kernel = q.mix ? FK_MIX : q.covariance ? FK_COVARIANCE : q.cross_sum ? FK_CROSS_SUM : q.filterbank ? FK_FILTERBANK : q.power_moments ? FK_POWER_MOMENTS : q.lag_sum ? FK_LAG_SUM : q.power_peak ? FK_POWER_PEAK : q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
+  r.kernel = q.mix ? FK_MIX : q.covariance ? FK_COVARIANCE : q.cross_sum ? FK_CROSS_SUM : q.filterbank ? FK_FILTERBANK : q.band_peak ? FK_BAND_PEAK : q.power_moments ? FK_POWER_MOMENTS : q.lag_sum ? FK_LAG_SUM : q.power_peak ? FK_POWER_PEAK : q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
   if (r.chunks == 1 && q.hop_kernel && nb >= 2 && !q.fuse && !grid) { r.kernel = FK_HOP; return r; }
 
   // self-carried chunks: every workgroup derives its carry-in from the raw samples (fold + one FFT in LDS) and forms
@@ -1303,7 +1321,7 @@ inline size_t stage_rows(size_t n, size_t row_bytes, size_t stage_bytes)
   const size_t seg = std::max<size_t>(1, stage_bytes / std::max<size_t>(row_bytes, 1));
   return std::min(seg, std::max<size_t>(n, 1));
 }
-// A grid analysis call (sdft_every_n and its nine siblings) on host memory goes in time segments of at most this many samples:
+// A grid analysis call (sdft_every_n and its ten siblings) on host memory goes in time segments of at most this many samples:
 // the rows a segment writes (row_bytes each, all channels / pairs / outputs of a row together; one row per `every` samples) and
 // the samples it reads (sample_row_bytes per time step) stay within stage_bytes -- but a segment of host samples is never shorter
 // than a hop.  whole_windows (the pooled calls): where the grid allows it a segment is made of whole windows, so that no row is

@@ -76,6 +76,24 @@ def fractional_octave(dftsize: int, samplerate: float, fraction: int = 3, fmin: 
     return _pack(bands)
 
 
+def flat(bin0, nbins):
+    """Bands of weight 1: band b covers the bins ``bin0[b] <= k < bin0[b] + nbins[b]`` -- what a peak search over bin ranges
+    (:meth:`sdft_amd.SDFT.band_peak`) installs.  Scalars give one band.  Bands without bins are dropped, as by the other builders."""
+    b0 = np.atleast_1d(np.asarray(bin0, dtype=np.int64))
+    nb = np.atleast_1d(np.asarray(nbins, dtype=np.int64))
+    if b0.shape != nb.shape or b0.ndim != 1:
+        raise ValueError("bin0 and nbins must have one entry per band")
+    if (b0 < 0).any() or (nb < 0).any():
+        raise ValueError("bin0 and nbins must not be negative")
+    return _pack([(int(k0), np.ones(int(n), dtype=np.float64)) for k0, n in zip(b0, nb)])
+
+
+def peak_frequency(bins, dftsize: int, samplerate: float) -> np.ndarray:
+    """The frequency of the bins :func:`sdft_amd.sdft.band_peak_split` returns, by the rule of :func:`bin_frequencies`:
+    ``bins * samplerate / (2 * dftsize)``, in the unit of ``samplerate``."""
+    return np.asarray(bins, dtype=np.float64) * (float(samplerate) / (2.0 * int(dftsize)))
+
+
 def dense(dftsize: int, bin0, nbins, weights) -> np.ndarray:
     """The filterbank as a dense (nbands, dftsize) matrix W, so that ``W @ power_row`` is what the filterbank analysis computes
     (bands that repeat stay separate rows)."""

@@ -321,6 +321,32 @@ class SDFT:
             raise ValueError("no filterbank is installed: call set_filterbank first")
         return self._grid_call("sdft_filterbank_n", x, every_rows, every, first, (), None, nb, self.fd, out)
 
+    def band_peak(self, x, every: int = 1, first: int = 0, out=None):
+        """Band-peak analysis (``sdft_hip_sdft_band_peak_n``): per band of the installed filterbank (:meth:`set_filterbank`) the
+        largest ``weight * power`` over the band's bins and the bin that attains it, of the rows :meth:`power` would return for the
+        samples ``first``, ``first + every``, ... < n -> real array of shape (rows, nbands, 2) [(channels, rows, nbands, 2) if
+        batched], numpy for numpy input, a device tensor for a device tensor: ``[..., 0]`` the value, ``[..., 1]`` the absolute bin
+        as a number of the plan's real type (:func:`band_peak_split` gives integers).  With ``v`` the rounded products of a band in
+        ascending bin order the pair is ``v[i], i = np.argmax(v)``: the lowest bin of the largest value, the lowest NaN bin if
+        there is one.  Neither the complex rows nor the powers are stored.  State and grid as with :meth:`filterbank`."""
+        self.api.clear()
+        every, first, _, _ = _grid_args(self.dftsize, every, first, banded=False)
+        nb = self.filterbank_bands
+        if nb == 0:
+            raise ValueError("no filterbank is installed: call set_filterbank first")
+        flat = None
+        if out is not None:
+            if _is_tensor(out) != _is_tensor(x):
+                raise ValueError("out must be of the samples' kind: a device tensor for a device tensor, a numpy array for numpy input")
+            shape = tuple(out.shape)
+            if len(shape) < 2 or shape[-2:] != (nb, 2):
+                raise ValueError(f"out must end in (nbands, 2) = ({nb}, 2), got shape {shape}")
+            if not (out.is_contiguous() if _is_tensor(out) else out.flags.c_contiguous):
+                raise ValueError("out must be contiguous")       # (a reshape would copy, and the call would write the copy)
+            flat = out.reshape(shape[:-2] + (2 * nb,))
+        got = self._grid_call("sdft_band_peak_n", x, every_rows, every, first, (), None, 2 * nb, self.fd, flat)
+        return out if out is not None else got.reshape(tuple(got.shape[:-1]) + (nb, 2))
+
     def set_pairs(self, a, b):
         """Installs a list of channel pairs in the plan (``sdft_hip_set_pairs``; the arrays are copied): pair p is the channels
         ``(a[p], b[p])``.  Pairs may repeat, come in any order and have ``a == b`` (the auto-spectrum).  No pairs removes the list."""
@@ -743,6 +769,15 @@ def mvdr_weights(mat, steering, loading: float = 0.0):
     den = np.einsum("kc,kc->k", np.conj(d), rid)                          # d^H R^-1 d
     w = rid / den[:, None]
     return np.ascontiguousarray(np.conj(w).T[None])
+
+
+def band_peak_split(peaks):
+    """``(values, bins)`` of :meth:`SDFT.band_peak`'s array: ``peaks[..., 0]`` as it is and ``peaks[..., 1]`` as int64 (the bins are
+    stored as exactly representable integers of the plan's real type).  numpy in, numpy out; device tensors likewise."""
+    if _is_tensor(peaks):
+        return peaks[..., 0], peaks[..., 1].to(_torch().int64)
+    peaks = np.asarray(peaks)
+    return peaks[..., 0], peaks[..., 1].astype(np.int64)
 
 
 def every_next_first(n: int, every: int, first: int) -> int:
