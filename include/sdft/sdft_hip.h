@@ -255,6 +255,58 @@ long sdft_hip_sdft_power_peak_n(sdft_t* sdft, const sdft_size_t nsamples, const 
                                 const sdft_size_t bin0, const sdft_size_t nbins,
                                 const int hold, sdft_fd_t* peaks) SDFT_HIP_SYMBOL(sdft_power_peak_n);
 
+/* ---- smoothed power analysis -----------------------------------------------------------------------
+   The third detector of a spectrum analyser, beside the linear average (sdft_hip_sdft_power_sum_n) and the peak hold
+   (sdft_hip_sdft_power_peak_n): the exponential average, the recursive periodogram of noise trackers (minimum statistics takes its
+   minimum over this estimate), decision-directed SNR estimators, AGC and VAD front ends and spectrograms with a time constant,
+     s[t][k] = a * s[t-1][k] + (1 - a) * |X[t][k]|^2
+   advanced at EVERY sample of the call -- a sliding DFT has a spectrum at every sample -- and kept on a row grid, without storing
+   a power per sample.  sdft_hip_sdft_power_smooth_n takes its grid (sampled: no head row, no windows), rows and the next call's
+   first from sdft_hip_sdft_every_n and every > nsamples, the band and the pointer rules (host or device memory, each pointer on its
+   own; option "async" applies to device pointers; smooth may be NULL when the call keeps no row) from sdft_hip_sdft_power_n,
+   unchanged.  smooth is [rows][nbins], dense, aligned to sizeof(sdft_fd_t) only; batched plans: samples [channels][nsamples],
+   smooth [channels][rows][nbins].
+   The value, exactly.  Let p[t][k] be what sdft_hip_sdft_power_n stores at every == 1, first == 0.  In sdft_fd_t, with no fused
+   multiply-add:
+     a = (sdft_fd_t)decay     b = (sdft_fd_t)1 - a     s[-1] = state (zero if state == NULL)
+     s[t] = fl( fl(a * s[t-1]) + fl(b * p[t]) )
+   Row r is s at sample first + r * every, after that sample's update.  state is [channels][nbins] (the bins of the band only),
+   read and written: on entry s before the call's first sample, on return s after its last.  It may be host or device memory
+   whatever the other pointers are.  NULL: the call starts from zero and drops the end value.  A call that keeps no row still
+   advances state.  A stream cut into calls passes state and sdft_hip_sdft_every_n's next first along.  exp(-1 / tau) is the decay of
+   a time constant of tau samples.  A NaN or infinite power stays in s from then on.
+   A call on host memory beyond option "stage_bytes" goes in time segments, calls in sequence with state passed along on the
+   device; "last_segments" then answers their number.
+   A long call cuts time into chunks ("last_chunks"); every chunk but the first runs the recursion from +0, and two small ordered
+   kernels carry s across the chunks (the recursion is linear in s): a scan of the chunks' end values in ascending order, then
+   smooth = fl(smooth + fl(P[j] * S)) for the rows of the later chunks, P[j] = fl(a^j) and S the value before the row's chunk.
+   Six things are promised.
+   (1) The same plan, options and input give the same bits on every run: no atomics.
+   (2) A call of one time chunk ("last_chunks" = 1; every call shorter than 512 samples is one) is bit for bit the sequential
+       expression above, evaluated on the reference's powers, wherever sdft_sdft_n is bit-identical to the reference (FD float, FD
+       double with option "carry" = 1, calls shorter than 512 samples) -- for any every, first, band, pointer placement and staging.
+   (3) A stream cut into one-chunk calls that pass state and the next first along has the bits of that sequential loop over the
+       whole signal, wherever it is cut.
+   (4) decay == 0 gives sdft_hip_sdft_power_n's values bit for bit for finite powers, on every route and any chunking (b == 1,
+       P[j >= 1] == 0, and adding +0 changes nothing): those of the reference on the bit-identical routes, elsewhere what
+       sdft_hip_sdft_power_n stores when it cuts time into chunks of the same length ("last_chunk_len"; at every == 1 it does).
+   (5) Calls of several chunks: with u = 2^-24 (float) or 2^-53 (double), s the exact recursion on the sdft_fd_t terms and the
+       rounded coefficients and M the largest of the incoming state and s[tau], tau <= t, barring underflow
+         |smooth - s| <= 8 u M / (1 - a)
+       (to first order 2 for the recursion itself, 3 for the scan, 3 (1 - a) for the last step; DESIGN.md has the derivation), and
+       likewise the returned state.  On the routes that are not bit-identical the power call's term deviation comes on top: 2.1e-11
+       of the largest power, with no factor 1 / (1 - a) because b / (1 - a) = 1.
+   (6) The stream state of every channel is afterwards the one sdft_sdft_n of the same samples leaves -- bins outside the band
+       step every sample too -- so any other entry point may follow.
+   The call is never resident, pipelined or fused and always runs its own kernel ("last_kernel" = 15).  Returns the number of rows
+   written (0 for nsamples == 0), or -1 with sdft_hip_last_error() set, the stream state and *state untouched: a NULL plan,
+   every == 0, nbins == 0, bin0 + nbins > dftsize, a decay that is NaN, negative or not below 1 after rounding to sdft_fd_t (a == 1
+   never forgets), smooth == NULL with rows > 0, or a workspace that cannot be reserved. */
+long sdft_hip_sdft_power_smooth_n(sdft_t* sdft, const sdft_size_t nsamples, const sdft_td_t* samples,
+                                  const sdft_size_t every, const sdft_size_t first,
+                                  const sdft_size_t bin0, const sdft_size_t nbins,
+                                  const double decay, sdft_fd_t* state, sdft_fd_t* smooth) SDFT_HIP_SYMBOL(sdft_power_smooth_n);
+
 /* ---- power-moments analysis ------------------------------------------------------------------------
    The one statistic of the power that no pooled output yields because it is not linear in it: the second moment.  With the sum
    of the power it gives the variance of the power per bin, the spectral kurtosis (the RFI flagger of radio astronomy, the
@@ -676,7 +728,7 @@ double sdft_hip_time_hops(sdft_t* sdft, size_t hops, size_t hop, const sdft_td_t
    "relay_flow", "relay_groups", "chain_debug", "inverse_nt", "inverse_nt_skip_mb", "inverse_step", "inverse_ordered", "host_direct", "copy_streams", "prefix_cells", "array_group", "mix_group", "mix_block" (sdft_capi.inc names what each selects);
    get_option "test_hooks" = 1 in that build.
    get_option additionally answers "tiles", "bins_per_lane", "row_slots", "last_chunks",
-   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis, 6 pooled power analysis, 7 filterbank analysis, 8 pooled cross-spectrum analysis, 9 array covariance analysis, 10 channel-mix analysis, 11 peak-hold analysis), 12 (lag-product analysis), 13 (power-moments analysis) or 14 (band-peak analysis), "last_segments", "last_fused",
+   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis, 6 pooled power analysis, 7 filterbank analysis, 8 pooled cross-spectrum analysis, 9 array covariance analysis, 10 channel-mix analysis, 11 peak-hold analysis), 12 (lag-product analysis), 13 (power-moments analysis), 14 (band-peak analysis) or 15 (smoothed power analysis), "last_segments", "last_fused",
    "last_filterbank_launches" (forward_filterbank_kernel launches of the last filterbank call, over all of its host segments: more than its carry segments once its pieces exceed the workspace bound),
    "last_band_peak_launches" (its twin: forward_band_peak_kernel launches of the last band-peak call),
    "last_chain", "last_fused_exact", "last_fused_fold", "last_process_path" (1 fused kernel, 2 hop pair, 3 two-pass),

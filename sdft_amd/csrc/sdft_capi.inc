@@ -107,6 +107,10 @@ long SDFT_FN(sdft_power_peak_n)(void* p, size_t n, const SDFT_TD* x, size_t ever
 // power-moments analysis: those powers and their squares, each summed over the windows of the grid; see sdft_hip.h
 long SDFT_FN(sdft_power_moments_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, size_t bin0, size_t nbins, SDFT_FD* moments)
 { return SDFT_GRID_CALL(sdft_power_moments_n, n, x, every, first, bin0, nbins, moments); }
+// smoothed power analysis: the one-pole average of those powers, advanced at every sample and kept on the grid; see sdft_hip.h
+long SDFT_FN(sdft_power_smooth_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, size_t bin0, size_t nbins, double decay,
+                                  SDFT_FD* state, SDFT_FD* smooth)
+{ return SDFT_GRID_CALL(sdft_power_smooth_n, n, x, every, first, bin0, nbins, decay, state, smooth); }
 // filterbank analysis: weighted band sums of those powers on the grid; see sdft_hip.h
 int SDFT_FN(set_filterbank)(void* p, size_t nbands, const size_t* band_bin0, const size_t* band_nbins, const SDFT_FD* weights)
 {

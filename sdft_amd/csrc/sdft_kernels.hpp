@@ -19,6 +19,10 @@
 //   sdft_forward_power_peak.hpp K1k forward_power_peak_kernel: the pooled power kernel with the other statistic -- the largest or the
 //                          smallest of those powers over each window, kept in registers by one rule (peak_hold); peak_rows_kernel
 //                          combines the pieces of the windows a chunk boundary cuts (sdft_hip_sdft_power_peak_n)
+//   sdft_forward_power_smooth.hpp K1o forward_power_smooth_kernel: the pooled power kernel with a recursion for the sum -- the one-pole
+//                          average s = a s + b p of those powers, advanced at every sample, stored on the grid and never cleared;
+//                          smooth_scan_kernel carries it across the time chunks in ascending order, smooth_fix_kernel adds what the
+//                          later chunks left out of their rows (sdft_hip_sdft_power_smooth_n)
 //   sdft_forward_cross_sum.hpp K1x forward_cross_sum_kernel: the pooled power kernel with a second channel -- A conj(B) of the windowed
 //                          bins of two channels of a plan, summed in registers over the windows of the grid (sdft_hip_sdft_cross_sum_n)
 //   sdft_forward_lag_sum.hpp K1l forward_lag_sum_kernel: the pooled power kernel with the cross-spectrum kernel's term between a row and
@@ -70,6 +74,7 @@
 #include "sdft_forward_power.hpp"
 #include "sdft_forward_power_sum.hpp"
 #include "sdft_forward_power_peak.hpp"
+#include "sdft_forward_power_smooth.hpp"
 #include "sdft_forward_cross_sum.hpp"
 #include "sdft_forward_lag_sum.hpp"
 #include "sdft_forward_power_moments.hpp"

@@ -205,7 +205,7 @@ class Plan
   long opt_prefix_cells = 1;     // test hook: the prefix-cell route of long calls (logic::ForwardQuery::prefix_cells)
   long last_prefix = 0;          // the last analysis call took it (one pre-pass launch: prefix_cells_kernel)
 
-  long last_kernel = 0;          // 1 = forward_kernel (independent tiles), 2 = forward_rows_kernel, 3 = hop, 4 = forward_every_kernel, 5 = forward_power_kernel, 6 = forward_pooled_power_kernel, 7 = forward_filterbank_kernel, 8 = forward_cross_sum_kernel, 9 = forward_covariance_kernel, 10 = forward_mix_kernel, 11 = forward_power_peak_kernel, 12 = forward_lag_sum_kernel, 13 = forward_power_moments_kernel, 14 = forward_band_peak_kernel
+  long last_kernel = 0;          // 1 = forward_kernel (independent tiles), 2 = forward_rows_kernel, 3 = hop, 4 = forward_every_kernel, 5 = forward_power_kernel, 6 = forward_pooled_power_kernel, 7 = forward_filterbank_kernel, 8 = forward_cross_sum_kernel, 9 = forward_covariance_kernel, 10 = forward_mix_kernel, 11 = forward_power_peak_kernel, 12 = forward_lag_sum_kernel, 13 = forward_power_moments_kernel, 14 = forward_band_peak_kernel, 15 = forward_power_smooth_kernel
 
   // device-resident stream state
   DevBuf<fdx> d_tw, d_syn, d_wtab;
@@ -251,6 +251,11 @@ class Plan
   DevBuf<fdx> d_stage_fdx;
   DevBuf<fdx*> d_rowptr;
   DevBuf<FD> d_psum_ws, d_psum_head;                       // pooled power analysis: pieces of cut windows [channels][chunks][2][band]; a segment's head row
+  // smoothed power analysis: the chunks' end values [channels][chunks][band]; s between the caller's state and the kernels (and
+  // between the segments of a call) [channels][band]; P[j] = fl(a^j), j = 0 ... chunk length, rebuilt when (a, length) changes
+  DevBuf<FD> d_smooth_ws, d_smooth_state, d_smooth_pw;
+  FD smooth_pw_a = (FD)-1;                                   // (no decay is negative: nothing is cached yet)
+  size_t smooth_pw_len = 0;
   // filterbank analysis: the installed filterbank (sdft_hip_set_filterbank) as the host gave it, its decomposition for the plan's
   // tiles (logic::filterbank_layout), the device copies the kernels read, and the workspace of split bands [channels][rows][slots]
   struct Filterbank
@@ -353,6 +358,7 @@ class Plan
     d_delta.release(); d_carry.release(); d_seed.release(); d_prefix.release();
     d_stage_td.release(); d_stage_fdx.release(); d_rowptr.release(); d_fseed.release();
     d_psum_ws.release(); d_psum_head.release();
+    d_smooth_ws.release(); d_smooth_state.release(); d_smooth_pw.release();
     d_fb_pieces.release(); d_fb_tile0.release(); d_fb_splits.release(); d_fb_weights.release(); d_fb_ws.release();
     d_cross_items.release(); d_cross_ws.release(); d_cross_head.release(); d_cross_stage.release();
     d_cov_items.release(); d_cov_chan.release(); d_cov_ws.release(); d_cov_head.release(); d_cov_stage.release();
@@ -600,6 +606,7 @@ class Plan
   // POWER: power-spectrogram analysis (sdft_power_n) -- forward_power_kernel stores |X|^2 of its band on its grid
   // POWER_SUM: pooled power analysis (sdft_power_sum_n) -- forward_pooled_power_kernel sums it over the grid's windows
   // POWER_PEAK: peak-hold analysis (sdft_power_peak_n) -- forward_power_peak_kernel holds its largest (hold 0) or smallest (hold 1) over those windows; psum as POWER_SUM's
+  // POWER_SMOOTH: smoothed power analysis (sdft_power_smooth_n) -- forward_power_smooth_kernel runs its one-pole average at every sample and stores it on the grid
   // FILTERBANK: filterbank analysis (sdft_filterbank_n) -- forward_filterbank_kernel stores the band sums of the plan's filterbank
   // BAND_PEAK: band-peak analysis (sdft_band_peak_n) -- forward_band_peak_kernel stores per band of that filterbank the largest weighted power and its bin, as a pair; fbk as FILTERBANK's, a pair for a number
   // CROSS_SUM: cross-spectrum analysis (sdft_cross_sum_n) -- forward_cross_sum_kernel sums A conj(B) of the plan's pairs over the grid's windows
@@ -611,9 +618,10 @@ class Plan
   {
     enum Kind : int { PLAIN = 0, FUSE = -1, EVERY = logic::FK_EVERY, POWER = logic::FK_POWER, POWER_SUM = logic::FK_POWER_SUM, FILTERBANK = logic::FK_FILTERBANK,
                       CROSS_SUM = logic::FK_CROSS_SUM, COVARIANCE = logic::FK_COVARIANCE, MIX = logic::FK_MIX, POWER_PEAK = logic::FK_POWER_PEAK, LAG_SUM = logic::FK_LAG_SUM,
-                      POWER_MOMENTS = logic::FK_POWER_MOMENTS, BAND_PEAK = logic::FK_BAND_PEAK };
+                      POWER_MOMENTS = logic::FK_POWER_MOMENTS, BAND_PEAK = logic::FK_BAND_PEAK, POWER_SMOOTH = logic::FK_POWER_SMOOTH };
     Kind kind = PLAIN;
     int hold = 0;                                            // POWER_PEAK
+    const PowerSmoothArgs<FD>* smooth = nullptr;             // POWER_SMOOTH
     const FuseArgs<TD, FD>* fuse = nullptr;                  // FUSE
     const EveryGrid* every = nullptr;                        // EVERY
     const PowerArgs<FD>* power = nullptr;                    // POWER
@@ -628,6 +636,7 @@ class Plan
     static ForwardCall band_power(const PowerArgs<FD>& a) { ForwardCall c = of(POWER); c.power = &a; return c; }
     static ForwardCall power_sum(const PowerSumArgs<FD>& a) { ForwardCall c = of(POWER_SUM); c.psum = &a; return c; }
     static ForwardCall power_peak(const PowerSumArgs<FD>& a, int hold) { ForwardCall c = of(POWER_PEAK); c.psum = &a; c.hold = hold; return c; }
+    static ForwardCall power_smooth(const PowerSmoothArgs<FD>& a) { ForwardCall c = of(POWER_SMOOTH); c.smooth = &a; return c; }
     static ForwardCall filterbank(const FilterbankArgs<FD>& a) { ForwardCall c = of(FILTERBANK); c.fbk = &a; return c; }
     static ForwardCall band_peak(const FilterbankArgs<FD>& a) { ForwardCall c = of(BAND_PEAK); c.fbk = &a; return c; }
     static ForwardCall cross_sum(const CrossSumArgs<FD>& a) { ForwardCall c = of(CROSS_SUM); c.cross = &a; return c; }
@@ -681,6 +690,7 @@ class Plan
     q.power = c.kind == ForwardCall::POWER;
     q.power_sum = c.kind == ForwardCall::POWER_SUM;
     q.power_peak = c.kind == ForwardCall::POWER_PEAK;
+    q.power_smooth = c.kind == ForwardCall::POWER_SMOOTH;
     q.filterbank = c.kind == ForwardCall::FILTERBANK;
     q.band_peak = c.kind == ForwardCall::BAND_PEAK;
     q.cross_sum = c.kind == ForwardCall::CROSS_SUM;
@@ -925,6 +935,25 @@ class Plan
       if (!d_psum_ws.reserve(logic::power_sum_workspace(channels, (size_t)chunks, ps.nbins_out))) return false;
       ps.ws = chunks > 1 ? d_psum_ws.p : nullptr;
     }
+    // smoothed power analysis: the workspace of the chunks' end values and the table of the decay's powers (likewise; a call of one
+    // chunk needs neither)
+    PowerSmoothArgs<FD> sm{};
+    if (c.smooth)
+    {
+      sm = *c.smooth;
+      if (chunks > 1)
+      {
+        if (!d_smooth_ws.reserve(logic::power_smooth_workspace(channels, (size_t)chunks, sm.nbins_out))) return false;
+        if (smooth_pw_a != sm.a || smooth_pw_len != (size_t)r.len)
+        {
+          const std::vector<FD> table = logic::power_smooth_table<FD>(sm.a, (size_t)r.len);
+          smooth_pw_a = (FD)-1;                              // (a failure leaves no half-written table behind as a valid one)
+          if (!d_smooth_pw.reserve(table.size()) || !to_device(d_smooth_pw.p, table.data(), table.size() * sizeof(FD))) return false;
+          smooth_pw_a = sm.a; smooth_pw_len = (size_t)r.len;
+        }
+        sm.ends = d_smooth_ws.p; sm.pw = d_smooth_pw.p;
+      }
+    }
     // filterbank and band-peak analysis: the workspace of the bands a tile boundary cuts, [channels][rows of a launch][slots]
     // (likewise) of numbers or of pairs; the chunks go in launches whose rows keep it within its bound (logic::filterbank_next_span)
     FilterbankArgs<FD> fb{};
@@ -1017,6 +1046,7 @@ class Plan
       case K::MIX: if (!grid_fits(blocks)) return false; if (!launch_forward_mix(fa, *c.mix, (unsigned)blocks)) return false; break;
       case K::POWER_PEAK: if (!grid_fits(blocks)) return false; launch_forward_power_peak(fa, ps, (unsigned)blocks, c.hold); break;
       case K::POWER_SUM: if (!grid_fits(blocks)) return false; launch_forward_power_sum(fa, ps, (unsigned)blocks); break;
+      case K::POWER_SMOOTH: if (!grid_fits(blocks)) return false; launch_forward_power_smooth(fa, sm, (unsigned)blocks); break;
       case K::POWER: if (!grid_fits(blocks)) return false; launch_forward_power(fa, *c.power, (unsigned)blocks); break;
       case K::EVERY: if (!grid_fits(blocks)) return false; launch_forward_every(fa, *c.every, (unsigned)blocks); break;
       }
@@ -1033,6 +1063,14 @@ class Plan
                                               : PowerSumArgs<FD>{cv.row0, cv.row0_stride, cv.rest, cv.rest_stride, cv.ws, cv.every, cv.first, cv.bin0, 2u * cv.nbins_out};
       const size_t units = c.psum ? channels : c.cross ? cs.npairs : cv.npairs;
       if (!(c.kind == K::POWER_PEAK ? launch_peak_rows(pieces, n, chunks, r.len, r.shift, units, c.hold) : launch_power_sum_rows(pieces, n, chunks, r.len, r.shift, units))) return false;
+      SDFT_TRY(hipGetLastError());
+    }
+    // the smoothed power call's carry across chunks: the scan of the end values, then what the chunks c >= 1 left out of their rows
+    if (chunks > 1 && c.smooth)
+    {
+      if (!launch_smooth_scan(sm, n, chunks, r.len, r.shift)) return false;
+      const size_t kept = logic::every_rows(n, (size_t)sm.every, (size_t)sm.first);
+      if (kept && !launch_smooth_fix(sm, kept, chunks, r.len, r.shift)) return false;
       SDFT_TRY(hipGetLastError());
     }
     if (r.flow) SDFT_TRY(hipStreamWaitEvent(stream, seg_events[0], 0));          // the call ends when both launches have

@@ -106,13 +106,13 @@
     return true;
   }
 
-  // ---- grid analysis calls: sdft_every_n and its ten siblings ------------------------------------------------------------------
-  // What the eleven share.  The stream state after a call is the one sdft_n leaves on the same samples.  A call is never resident,
+  // ---- grid analysis calls: sdft_every_n and its eleven siblings ---------------------------------------------------------------
+  // What the twelve share.  The stream state after a call is the one sdft_n leaves on the same samples.  A call is never resident,
   // pipelined or fused: whatever is in flight is retired / joined first, then one forward call on the plan's stream with the
   // call's own kernel (ForwardCall).  `rows` receives the row count.  Device samples and a device output take that one call; host
   // memory goes through device scratch in time segments of at most logic::grid_segment samples, each segment a call of its own
   // under the streaming contract, with its own first.
-  // The every-grid calls (every, power, filterbank, band_peak, mix) keep the rows of the samples first, first + every, ... < n; a segment
+  // The every-grid calls (every, power, power_smooth, filterbank, band_peak, mix) keep the rows of the samples first, first + every, ... < n; a segment
   // keeps the rows of the grid that fall into it.  The pooled calls (power_sum, power_peak, power_moments, cross_sum, lag_sum, covariance) write
   // one row per window the grid cuts the call into (logic::power_sum_window), row 0 the head window [0, first) when first > 0; a
   // segment that starts inside a window has a head row of its own, which is kept apart (the call's head buffer) and joined into
@@ -255,6 +255,46 @@
       const PowerArgs<FD> g{at, logic::power_channel_stride(at_rows, nbins_out), p.grid.every, p.grid.first, (unsigned)bin0, (unsigned)nbins_out};
       return forward_device(p.m, p.td, p.td_stride, nullptr, 0, nullptr, ForwardCall::band_power(g));
     });
+  }
+
+  // smoothed power analysis (sdft_hip_sdft_power_smooth_n): s[t] = fl(fl(a * s[t - 1]) + fl(b * p[t])) of sdft_power_n's every == 1
+  // powers, advanced at every sample and kept on the grid, dense [channels][rows][nbins_out] real numbers --
+  // forward_power_smooth_kernel, then, in a call of more than one chunk, smooth_scan_kernel and smooth_fix_kernel.  sdft_power_n's
+  // path with one addition: s travels from the caller's state [channels][nbins_out] (host or device memory; nullptr: from zero,
+  // and the end value is dropped) through the two halves of d_smooth_state -- a launch reads one and writes the other, the next
+  // segment of a call on host memory goes on from there -- and back to the caller once the whole call has succeeded.  A call in
+  // several segments reports their number as "last_segments".
+  bool sdft_power_smooth_n(size_t n, const TD* x, size_t every, size_t first, size_t bin0, size_t nbins_out, double decay, FD* state, FD* smooth,
+                           size_t& rows)
+  {
+    const char* const refused = logic::power_smooth_decay_ok<FD>(decay) ? nullptr : "decay must be at least 0 and less than 1 after rounding to sdft_fd_t";
+    if (!grid_args("sdft_hip_sdft_power_smooth_n", n, every, first, true, bin0, nbins_out, refused, false, smooth, "smooth", rows)) return false;
+    if (n == 0 || nbins == 0) return true;
+    const FD a = (FD)decay, b = (FD)1 - a;
+    const size_t count = channels * nbins_out;
+    bool state_device = false;
+    int cur = 0;                                             // the half of d_smooth_state that holds s
+    long pieces = 0;                                         // forward calls: more than one when host memory goes in segments
+    auto ready = [&] {
+      if (!d_smooth_state.reserve(2 * count)) return false;
+      state_device = state && on_device(state);
+      if (!state) SDFT_TRY(hipMemsetAsync(d_smooth_state.p, 0, count * sizeof(FD), stream));
+      else if (state_device) SDFT_TRY(hipMemcpyAsync(d_smooth_state.p, state, count * sizeof(FD), hipMemcpyDeviceToDevice, stream));
+      else if (!to_device(d_smooth_state.p, state, count * sizeof(FD))) return false;
+      return true;
+    };
+    if (!every_grid_call(n, x, every, first, smooth, rows, channels, nbins_out, ready, [&](const GridPiece& p, FD* at, size_t at_rows) {
+          const PowerSmoothArgs<FD> g{at, logic::power_channel_stride(at_rows, nbins_out), d_smooth_state.p + cur * count, d_smooth_state.p + (cur ^ 1) * count,
+                                      nullptr, nullptr, a, b, p.grid.every, p.grid.first, (unsigned)bin0, (unsigned)nbins_out};
+          if (!forward_device(p.m, p.td, p.td_stride, nullptr, 0, nullptr, ForwardCall::power_smooth(g))) return false;
+          cur ^= 1; ++pieces;
+          return true;
+        })) return false;
+    if (pieces > 1) last_segments = pieces;                  // ("last_segments": the call went in that many time segments, each a call with its own carries)
+    if (!state) return true;
+    if (!state_device) return to_host(state, d_smooth_state.p + cur * count, count * sizeof(FD));
+    SDFT_TRY(hipMemcpyAsync(state, d_smooth_state.p + cur * count, count * sizeof(FD), hipMemcpyDeviceToDevice, stream));
+    return async || synchronize();
   }
 
   // ---- filterbank analysis ---------------------------------------------------------------------------------------------

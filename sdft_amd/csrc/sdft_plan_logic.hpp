@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 namespace sdfthip {
@@ -309,6 +310,40 @@ inline bool peak_hold_ok(int hold) { return hold == kHoldMax || hold == kHoldMin
 template <typename T> inline T peak_hold(T m, T p, int hold)
 {
   return hold == kHoldMin ? ((p < m || p != p) ? p : m) : ((p > m || p != p) ? p : m);
+}
+
+// ---- smoothed power analysis (sdft_hip_sdft_power_smooth_n) ----------------------------------------------------------------------
+// The one-pole average of the power call's every == 1 term p, s[t] = fl(fl(a * s[t - 1]) + fl(b * p[t])) in FD, a = (FD)decay,
+// b = fl(1 - a), advanced at EVERY sample of the call and kept on the power call's grid (rows: every_rows; the row of a grid point
+// holds s after that sample's step).  It is the first statistic with memory across windows: s before a call's first sample comes
+// from the caller's state [channels][nbins_out] and s after its last goes back there.  The pooled power call's route and chunk
+// choice (choose_power_sum_chunks).  Chunk 0 starts from the state, every later chunk from +0 and so leaves a^(j + 1) * S_c out of
+// its j-th sample, S_c the true s before the chunk.  Each chunk leaves the value it ends with, E_c, in the workspace
+// [channels][chunks][nbins_out]; smooth_scan_kernel walks S_1 = E_0, S_{c + 1} = fl(fl(P[len_c] * S_c) + E_c) in ascending order,
+// puts S_c in E_c's place and the last value into the state; smooth_fix_kernel adds fl(P[j + 1] * S_c) to the kept rows of the
+// chunks c >= 1.  P[j] = fl(a^j) (power_smooth_table).  A call of one chunk needs none of this and is the sequential loop bit for bit.
+// The decay a call may take: after rounding to FD neither NaN nor negative nor 1 or more (a == 1 never forgets: b == 0)
+template <typename T> inline bool power_smooth_decay_ok(double decay)
+{
+  const T a = (T)decay;
+  return a >= (T)0 && a < (T)1;                              // (false for NaN)
+}
+inline size_t power_smooth_slot(size_t channel, size_t chunks, size_t chunk, size_t nbins_out) { return (channel * chunks + chunk) * nbins_out; }
+inline size_t power_smooth_workspace(size_t channels, size_t chunks, size_t nbins_out) { return chunks > 1 ? channels * chunks * nbins_out : 0; }
+// P[j] = a^j for j = 0 ... len, formed from the rounded a in long double and rounded once to T (P[0] = 1 also at a == 0)
+template <typename T> inline std::vector<T> power_smooth_table(T a, size_t len)
+{
+  std::vector<T> p(len + 1);
+  for (size_t j = 0; j <= len; ++j) p[j] = (T)std::pow((long double)a, (long double)j);
+  return p;
+}
+// what smooth_fix_kernel does with the row of sample t: its chunk and, in a chunk c >= 1, the entry of P that scales S_c -- the
+// number of steps from the chunk's first sample up to and including t
+struct PowerSmoothFix { long chunk; size_t power; };
+inline PowerSmoothFix power_smooth_fix(size_t t, long len, long shift)
+{
+  const long c = chunk_of(t, len, shift);
+  return {c, t - chunk_begin(c, len, shift) + 1};
 }
 
 // ---- pooled cross-spectrum analysis (sdft_hip_sdft_cross_sum_n) ------------------------------------------------------------------
@@ -977,6 +1012,7 @@ struct ForwardQuery
   bool power_peak = false;                // peak-hold analysis (forward_power_peak_kernel): the pooled power call's route (never with power_sum)
   bool lag_sum = false;                   // lag-product analysis (forward_lag_sum_kernel): the pooled power call's route (never with power_sum or power_peak)
   bool power_moments = false;             // power-moments analysis (forward_power_moments_kernel): the pooled power call's route and chunk choice (never with power_sum, power_peak or lag_sum)
+  bool power_smooth = false;              // smoothed power analysis (forward_power_smooth_kernel): the pooled power call's route and chunk choice (never with another of these)
   bool filterbank = false;                // filterbank analysis (forward_filterbank_kernel) on the grid of power_every
   bool band_peak = false;                 // band-peak analysis (forward_band_peak_kernel) on the grid of power_every: the filterbank call's route and chunk choice (never with filterbank)
   bool cross_sum = false;                 // pooled cross-spectrum analysis (forward_cross_sum_kernel) of ...
@@ -993,7 +1029,7 @@ struct ForwardQuery
        chain_L = 0, relay_flow = 1, segments = 0, xcd_map = 1, rows_f32 = 1, pipeline = 1;
   long prefix_cells = 1;                  // test hook: 0 = never the prefix-cell route, 1 = calls beyond kSelfMax, 2 = whatever the length
 };
-enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6, FK_FILTERBANK = 7, FK_CROSS_SUM = 8, FK_COVARIANCE = 9, FK_MIX = 10, FK_POWER_PEAK = 11, FK_LAG_SUM = 12, FK_POWER_MOMENTS = 13, FK_BAND_PEAK = 14 };     // = get_option "last_kernel"
+enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6, FK_FILTERBANK = 7, FK_CROSS_SUM = 8, FK_COVARIANCE = 9, FK_MIX = 10, FK_POWER_PEAK = 11, FK_LAG_SUM = 12, FK_POWER_MOMENTS = 13, FK_BAND_PEAK = 14, FK_POWER_SMOOTH = 15 };     // = get_option "last_kernel"
 // carries: the single chunk's are the stream state (delta_kernel copies it); pre-pass partial sums + scan (carries from the
 // closed-form table); the serial exact pass (carry_exact_kernel); the relay form of the exact pass (carry_relay_kernel)
 enum CarryForm : int { CARRY_STATE = 0, CARRY_SUMS = 1, CARRY_SERIAL = 2, CARRY_RELAY = 3 };
@@ -1041,8 +1077,8 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   ForwardRoute r;
   const size_t nb = q.nbins, span = 2 * nb, n = q.n, ch = std::max<size_t>(q.channels, 1);
   const bool pow2 = (span & (span - 1)) == 0;
-  // the decimated, the power-spectrogram, the pooled power, the peak-hold, the lag-product, the power-moments, the filterbank, the band-peak, the cross-spectrum, the covariance and the mix analysis have the tile form only
-  const bool grid = q.every || q.power || q.power_sum || q.power_peak || q.lag_sum || q.power_moments || q.filterbank || q.band_peak || q.cross_sum || q.covariance || q.mix;
+  // the decimated, the power-spectrogram, the pooled power, the peak-hold, the lag-product, the power-moments, the smoothed power, the filterbank, the band-peak, the cross-spectrum, the covariance and the mix analysis have the tile form only
+  const bool grid = q.every || q.power || q.power_sum || q.power_peak || q.lag_sum || q.power_moments || q.power_smooth || q.filterbank || q.band_peak || q.cross_sum || q.covariance || q.mix;
   // (channel, chunk) groups of a tile launch per chunk: the cross-spectrum, the covariance and the mix call's are their work items
   const size_t lanes = (q.cross_sum || q.covariance || q.mix) ? std::max<size_t>(q.cross_items, 1) : ch;
   const bool rows = !grid && rows_kernel_ok(nb, q.fdx_bytes, q.row_pointers, q.rows_kernel != 0, q.row_slots_max);
@@ -1070,12 +1106,12 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   {
     EveryQuery e;
     e.n = n; e.channels = lanes; e.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); e.exact = q.exact; e.forced_chunk = q.chunk; e.compute_units = q.compute_units;
-    c = (q.power_sum || q.power_peak || q.lag_sum || q.power_moments || q.cross_sum || q.covariance) ? choose_power_sum_chunks(e) : (q.power || q.filterbank || q.band_peak || q.mix) ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
+    c = (q.power_sum || q.power_peak || q.lag_sum || q.power_moments || q.power_smooth || q.cross_sum || q.covariance) ? choose_power_sum_chunks(e) : (q.power || q.filterbank || q.band_peak || q.mix) ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
   }
   else c = choose_chunks(chunk_query(q, rows, r.pipelined));
   r.chunks = c.chunks; r.len = c.len;
   r.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); r.interior = interior_lanes(q.window, q.fdx_bytes, q.interior);
-  r.kernel = q.mix ? FK_MIX : q.covariance ? FK_COVARIANCE : q.cross_sum ? FK_CROSS_SUM : q.filterbank ? FK_FILTERBANK : q.band_peak ? FK_BAND_PEAK : q.power_moments ? FK_POWER_MOMENTS : q.lag_sum ? FK_LAG_SUM : q.power_peak ? FK_POWER_PEAK : q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
+  r.kernel = q.mix ? FK_MIX : q.covariance ? FK_COVARIANCE : q.cross_sum ? FK_CROSS_SUM : q.filterbank ? FK_FILTERBANK : q.band_peak ? FK_BAND_PEAK : q.power_smooth ? FK_POWER_SMOOTH : q.power_moments ? FK_POWER_MOMENTS : q.lag_sum ? FK_LAG_SUM : q.power_peak ? FK_POWER_PEAK : q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
   if (r.chunks == 1 && q.hop_kernel && nb >= 2 && !q.fuse && !grid) { r.kernel = FK_HOP; return r; }
 
   // self-carried chunks: every workgroup derives its carry-in from the raw samples (fold + one FFT in LDS) and forms
@@ -1321,7 +1357,7 @@ inline size_t stage_rows(size_t n, size_t row_bytes, size_t stage_bytes)
   const size_t seg = std::max<size_t>(1, stage_bytes / std::max<size_t>(row_bytes, 1));
   return std::min(seg, std::max<size_t>(n, 1));
 }
-// A grid analysis call (sdft_every_n and its ten siblings) on host memory goes in time segments of at most this many samples:
+// A grid analysis call (sdft_every_n and its eleven siblings) on host memory goes in time segments of at most this many samples:
 // the rows a segment writes (row_bytes each, all channels / pairs / outputs of a row together; one row per `every` samples) and
 // the samples it reads (sample_row_bytes per time step) stay within stage_bytes -- but a segment of host samples is never shorter
 // than a hop.  whole_windows (the pooled calls): where the grid allows it a segment is made of whole windows, so that no row is

@@ -499,6 +499,33 @@ class SDFT:
             raise ValueError(f"hold must be 'max' (0) or 'min' (1), got {hold!r}")
         return self._grid_call("sdft_power_peak_n", x, power_sum_rows, every, first, (bin0, nb, HOLDS[hold]), None, nb, self.fd, out)
 
+    def power_smooth(self, x, decay: float, every: int = 1, first: int = 0, bins=None, state=None, out=None):
+        """Smoothed power analysis (``sdft_hip_sdft_power_smooth_n``): the one-pole average ``s = a * s + b * p`` of :meth:`power`'s
+        ``every = 1`` values ``p``, ``(a, b) = smooth_coefficients(decay, dtype)``, advanced at every sample and kept on
+        :meth:`power`'s grid -> real array of shape (rows, nbins) [(channels, rows, nbins) if batched], numpy for numpy input, a
+        device tensor for a device tensor: row r is the average after the sample ``first + r * every``.  ``state`` is a numpy array
+        or a device tensor (whatever ``x`` is) of shape (nbins,) [(channels, nbins)] in the FD dtype, updated in place: the average
+        before the first sample on entry, after the last on return; ``None`` starts from zero and drops the end value.  A stream
+        passes ``state`` and :func:`every_next_first` from call to call.  :func:`smooth_decay` turns a time constant into
+        ``decay``.  The plan's state advances over all n samples and all bins, as with :meth:`sdft`."""
+        self.api.clear()
+        every, first, bin0, nb = _grid_args(self.dftsize, every, first, bins)
+        smooth_coefficients(decay, self.fd)                  # (raises for a decay the library would refuse)
+        sp = None
+        if state is not None:
+            batched = (x.dim() if _is_tensor(x) else np.ndim(x)) == 2
+            shape = (self.channels, nb) if batched else (nb,)
+            if _is_tensor(state):
+                self._check_tensor(state, "state", self.fd, shape)
+                sp = state.data_ptr()
+            else:
+                if not isinstance(state, np.ndarray) or state.dtype != self.fd or not state.flags.c_contiguous or not state.flags.writeable:
+                    raise ValueError(f"state must be a writable C-contiguous numpy array of dtype {np.dtype(self.fd).name} (it is updated in place) or a device tensor")
+                if state.shape != shape:
+                    raise ValueError(f"state must have shape {shape}, got {state.shape}")
+                sp = state.ctypes.data
+        return self._grid_call("sdft_power_smooth_n", x, every_rows, every, first, (bin0, nb, float(decay), C.c_void_p(sp)), None, nb, self.fd, out)
+
     def power_moments(self, x, every: int = 1, first: int = 0, bins=None, out=None):
         """Power-moments analysis (``sdft_hip_sdft_power_moments_n``): :meth:`power_sum`'s grid, windows, head row and pointers,
         with two sums per window and bin -> real array of shape (rows, nbins, 2) [(channels, rows, nbins, 2) if batched] in the FD
@@ -701,6 +728,24 @@ def spectral_kurtosis(moments, lengths):
     with np.errstate(divide="ignore", invalid="ignore"):
         sk = (length + 1.0) / (length - 1.0) * (length * s2 / (s1 * s1) - 1.0)
     return np.where((length < 2) | (s1 == 0), np.nan, sk)
+
+
+def smooth_coefficients(decay: float, dtype):
+    """``(a, b)`` of :meth:`SDFT.power_smooth` as numbers of ``dtype`` (the plan's real type): ``a = dtype(decay)`` and
+    ``b = dtype(1) - a``.  Raises ValueError for a decay the library refuses: NaN, negative, or 1 or more after rounding."""
+    t = np.dtype(dtype).type
+    a = t(decay)
+    if not (a >= t(0) and a < t(1)):
+        raise ValueError(f"decay must be at least 0 and less than 1 after rounding to {np.dtype(dtype).name}, got {decay!r}")
+    return a, t(1) - a
+
+
+def smooth_decay(time_constant_samples: float) -> float:
+    """The decay of a time constant of that many samples: ``exp(-1 / tau)`` (after tau samples a step has reached 1 - 1/e)."""
+    tau = float(time_constant_samples)
+    if not tau > 0:
+        raise ValueError(f"the time constant must be positive, got {time_constant_samples!r}")
+    return float(np.exp(-1.0 / tau))
 
 
 HOLDS = {"max": 0, "min": 1, 0: 0, 1: 1}                     # SDFT.power_peak's hold -> enum sdft_hip_hold
