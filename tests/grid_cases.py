@@ -1,5 +1,5 @@
-"""The cases of the seeded sweep over the six grid analysis calls (tests/test_gpu_fuzz_grid.py).  TEST HELPER (plain numpy: no
-HIP, no torch; imported like guarded and exact_sdft).
+"""The cases of the seeded sweep over the twelve grid analysis calls (tests/test_gpu_fuzz_grid.py), in two slates of six.  TEST
+HELPER (plain numpy: no HIP, no torch; imported like guarded and exact_sdft).
 
 cases(seed) draws the seven cases of a seed, one per kind in the order of SLOTS: the six grid entry points and `mixed`, a second
 draw of one of the six on a batched plan.  The draw is deterministic: np.random.default_rng(BASE + seed + SDFT_FUZZ_OFFSET), the
@@ -28,7 +28,18 @@ live (device, stage_bytes in opts, out = residue of a guarded output or None) an
 
 The geometry is restated from logic::interior_lanes and logic::bins_per_lane (sdft_plan_logic.hpp); the GPU test asserts it
 against the plan's own answers.  chunk_cuts() restates where a forced chunk length cuts time (logic::choose_grid_chunks,
-logic::relay_block, logic::chunk_begin / chunk_end) for the coverage conditions of tests/test_grid_cases_cpu.py."""
+logic::relay_block, logic::chunk_begin / chunk_end) for the coverage conditions of tests/test_grid_cases_cpu.py.
+
+cases2(seed) is the second slate: the six newer calls (KINDS2: mix, power_peak, lag_sum, power_moments, band_peak, power_smooth) and
+`mixed`, drawn from np.random.default_rng(BASE2 + seed + SDFT_FUZZ_OFFSET) by the same rule and through the same draws of the plan,
+the options, the warm-up, the grid and the placement, so that a stratum means the same in both slates.  The first slate's draws
+do not move: what a new kind draws, it draws on branches the old kinds never take (tests/test_grid_cases_cpu.py pins the digest).
+A case of the second slate has, by kind: the mix (nout, chan, wseed: test_gpu_mix.weights_for(fdx, nout, len(chan), m, wseed);
+mix_group / mix_block on hooks plans), hold, the smoothing (decay, tau where smooth_decay(tau) gave it, state in none / host /
+device, sseed: test_gpu_power_smooth.some_state), the bank of band_peak (as the filterbank's; one_bin: one_bin_bands(m); keep: the
+first `keep` of random_bands' 3 m bands), and split: None, or the sample at which the call under test is cut into two calls (in
+the strata that pin several chunks the cut leaves them to the first call).  Where fid_scale is set, the second slate scales
+channel c's fid by 2.0 ** c, which is exact in either FD type and passes through the demodulation and the window exactly."""
 
 from __future__ import annotations
 
@@ -37,6 +48,7 @@ import os
 import numpy as np
 
 BASE = 52000
+BASE2 = 137000                                               # the second slate's
 OFFSET = int(os.environ.get("SDFT_FUZZ_OFFSET", "0"))
 COMBOS = ("f32f64", "f32f32", "f64f64", "f64f32")           # oracle.COMBOS (asserted by the tests)
 WINDOWS = ("boxcar", "hann", "hamming", "blackman")
@@ -44,9 +56,13 @@ KINDS = ("every", "power", "power_sum", "filterbank", "cross_sum", "covariance")
 SLOTS = KINDS + ("mixed",)
 STRATA = ("default", "one_chunk", "relay", "serial", "sums", "segments", "installed")
 STRATIFIED = 28                                              # seeds below this are stratified: 4 type pairs x 7 strata
-KERNEL = {"every": 4, "power": 5, "power_sum": 6, "filterbank": 7, "cross_sum": 8, "covariance": 9}    # logic::ForwardKernel
-POOLED = ("power_sum", "cross_sum", "covariance")            # the kinds that sum over windows (and have a head row)
-BANDED = ("power", "power_sum", "cross_sum", "covariance")   # the kinds that take a band of bins
+KINDS2 = ("mix", "power_peak", "lag_sum", "power_moments", "band_peak", "power_smooth")
+SLOTS2 = KINDS2 + ("mixed",)
+KERNEL = {"every": 4, "power": 5, "power_sum": 6, "filterbank": 7, "cross_sum": 8, "covariance": 9,
+          "mix": 10, "power_peak": 11, "lag_sum": 12, "power_moments": 13, "band_peak": 14, "power_smooth": 15}    # logic::ForwardKernel
+POOLED = ("power_sum", "cross_sum", "covariance", "power_peak", "lag_sum", "power_moments")      # the kinds that pool windows (and have a head row)
+BANDED = ("power", "power_sum", "cross_sum", "covariance", "mix", "power_peak", "lag_sum", "power_moments", "power_smooth")      # ... that take a band of bins
+COMPLEX = ("every", "cross_sum", "covariance", "mix", "lag_sum")                                   # ... whose output elements are (re, im)
 
 STRUCTURAL = (8, 9, 31, 63, 64, 65, 127, 128, 129, 500, 1000, 1023, 1024, 1025, 1100, 2047, 2048, 2049, 2500, 4096, 4100)   # tests/test_gpu_fuzz.py
 CHUNKS = (0, 8, 64, 96, 100, 200, 512, 1000, 1 << 30)
@@ -54,6 +70,10 @@ BUDGET = 3_000_000                                           # m * n * channels 
 HOP = 512                                                    # logic::kHopSamples: shorter calls are one chunk unless option "chunk" cuts them
 CLOSING = 60                                                 # samples of the closing sdft call
 PAIR_WORK = 6_000_000                                        # pairs * n1 * band bins the reference of a pair case may cost
+ONE_BIN_WORK = 2_000_000                                     # m * rows * channels up to which band_peak may get one_bin_bands(m)
+BANK_BANDS = 600                                             # bands of random_bands(m) a band_peak case keeps (the reference is a loop over bands)
+DECAYS = (0.0, 0.5, 0.9, 1.0 - 2.0 ** -10)                   # tests/test_gpu_power_smooth.py
+MIX_NOUTS, MIX_GROUPS, MIX_BLOCKS = (1, 2, 3, 5), (2, 4, 8), (1, 2, 4)      # tests/test_gpu_mix.py
 
 # the pair lists and arrays of the suites (the GPU test asserts that they are the suites' own)
 PAIRS = [(0, 1), (1, 0), (2, 2), (0, 0), (0, 2), (0, 1)]     # tests/test_gpu_cross_sum.py
@@ -267,8 +287,57 @@ def cut_to(pairs, channels):
     return [(a, b) for a, b in pairs if a < channels and b < channels] or [(0, 0)]
 
 
+def draw_kind2(rng, case, several, length):
+    """what only a kind of the second slate draws"""
+    kind, ch, n1, stratum = case["kind"], case["channels"], case["n1"], case["stratum"]
+    if kind == "mix":
+        case["nout"] = int(pick(rng, MIX_NOUTS))
+        form = int(rng.integers(0, 3))
+        if form == 0:
+            chan = list(range(ch))                           # all channels, in plan order
+        elif form == 1:
+            chan = [int(c) for c in rng.permutation(ch)[:int(rng.integers(1, ch))]]      # a proper subset: some channel only advances
+            if len(chan) > 1 and chan == sorted(chan):
+                chan.reverse()
+        else:
+            chan = [int(rng.integers(0, ch))]
+        case["chan"], case["wseed"] = chan, int(rng.integers(0, 1 << 16))
+        if case["hooks"]:
+            maybe(rng, case, "mix_group", MIX_GROUPS, 0.3)
+            maybe(rng, case, "mix_block", MIX_BLOCKS, 0.3)
+    if kind == "power_peak":
+        case["hold"] = str(pick(rng, ("max", "min")))
+    if kind == "power_smooth":
+        case["tau"] = float(rng.uniform(2.0, 2000.0))
+        case["decay"] = float(pick(rng, DECAYS + (float(np.exp(-1.0 / case["tau"])),)))      # (smooth_decay(tau))
+        case["state"] = str(pick(rng, ("none", "host", "device")))
+        case["sseed"] = int(rng.integers(0, 1 << 16))
+    # the call under test as two calls: the first keeps what the stratum pins
+    low = (3 * length + 1) if stratum == "segments" else ((length + 1) if case["opts"].get("chunk", 0) > 0 else HOP) if several else 1
+    take = rng.random() < 0.25
+    case["split"] = None
+    if take and n1 >= 2 and low < n1 and "stage_bytes" not in case["opts"] and case["out"] is None:
+        case["split"] = int(rng.integers(low, n1))
+
+
+def next_first(n, every, first):
+    """sdft_amd.sdft.every_next_first"""
+    rows = (n - first + every - 1) // every if first < n else 0
+    return first + rows * every - n if rows else first - n
+
+
+def parts(case):
+    """the calls the call under test is made as: [case] or, for a split case, the two cases of its parts"""
+    cut = case.get("split")
+    if not cut:
+        return [case]
+    a = dict(case, n1=cut, split=None)
+    b = dict(case, n0=case["n0"] + cut, n1=case["n1"] - cut, first=next_first(cut, case["every"], case["first"]), split=None)
+    return [a, b]
+
+
 def draw_case(rng, seed, slot, kind, combo, stratum, index):
-    batched = slot == "mixed" or kind in ("cross_sum", "covariance") or rng.random() < 1 / 3
+    batched = slot == "mixed" or kind in ("cross_sum", "covariance", "mix") or (kind == "lag_sum" and stratum == "installed") or rng.random() < 1 / 3
     channels = int(rng.integers(2, 6)) if batched else 1
     window = WINDOWS[int(rng.integers(0, 4))]
     hooks = bool(rng.random() < 0.4)
@@ -306,6 +375,8 @@ def draw_case(rng, seed, slot, kind, combo, stratum, index):
     if stratum == "relay":
         n0s = [v for v in n0s if v % 8] or [min(room, 2 * m - 1) | 1]
     case["n0"] = int(pick(rng, n0s))
+    if kind == "lag_sum" and stratum not in ("relay", "installed") and rng.random() < 0.15:
+        case["n0"] = 0                                       # (the zero previous row)
     case["warm"] = str(pick(rng, ("sdft", "every", "power", "power_sum", kind)))
     if stratum == "relay":
         assert case["n0"] % 8 and m % 4 == 0
@@ -326,6 +397,8 @@ def draw_case(rng, seed, slot, kind, combo, stratum, index):
         first = n1 + int(rng.integers(0, 3))                 # no grid rows; a pooled call has its head row only
     if kind == "every" and (every, first) == (1, 0):
         first = 1                                            # (every == 1, first == 0 is sdft_n itself: tests/test_gpu_fuzz.py)
+    if kind in ("lag_sum", "power_moments") and rng.random() < 0.3:
+        every, first = 1, 0                                  # a row is its term: the bit-for-bit check
     case["every"], case["first"] = every, first
 
     # what the call reads its bins, bands and channels from
@@ -333,15 +406,18 @@ def draw_case(rng, seed, slot, kind, combo, stratum, index):
     if kind in BANDED:
         case["band"] = draw_band(rng, m, per)
         nb = case["band"][1]
-    if kind == "filterbank":
+    if kind in ("filterbank", "band_peak"):
         extra, t = [], tiles_of(m, per) // 2
-        bank = int(rng.integers(0, 3))                       # random_bands(m), plus a band ending on / beginning on a tile boundary
+        bank = int(rng.integers(0, 3 if kind == "filterbank" else 4))      # random_bands(m), plus a band ending on / beginning on a tile boundary
         if bank == 1 and t >= 1:
             b0 = int(rng.integers(0, t * per))
             extra = [(b0, t * per - b0)]
         if bank == 2 and t >= 1:
             extra = [(t * per, int(rng.integers(1, m - t * per + 1)))]
         case["bank"] = dict(seed=int(rng.integers(0, 1 << 16)), extra=extra)
+        if kind == "band_peak":
+            rows = (n1 - first + every - 1) // every if first < n1 else 0
+            case["bank"].update(one_bin=bool(bank == 3 and m * rows * channels <= ONE_BIN_WORK), keep=min(3 * m, BANK_BANDS))
     if kind == "cross_sum":
         lists = [("PAIRS", PAIRS), ("PAIR_LISTS[0]", PAIR_LISTS[0]), ("PAIR_LISTS[1]", PAIR_LISTS[1])] + list(WRITER_LISTS.items())
         lists = [(name, cut_to(p, channels)) for name, p in lists]
@@ -359,8 +435,10 @@ def draw_case(rng, seed, slot, kind, combo, stratum, index):
         opts["stage_bytes"] = int(pick(rng, (700 * channels * (8 if combo.startswith("f64") else 4), 4096, 65536)))
     case["out"] = None
     if guarded:
-        size = (8 if fd_double(combo) else 4) * (2 if kind in ("every", "cross_sum", "covariance") else 1)
+        size = (8 if fd_double(combo) else 4) * (2 if kind in COMPLEX else 1)
         case["out"] = pick(rng, [(r, 16) for r in range(size, 16, size)] + [(16, 128)])
+    if kind in KINDS2:
+        draw_kind2(rng, case, several, length)
     case["fid_scale"] = bool(stratum == "installed" and channels > 1 and (seed // 2) % 2 == 1)
     case["xseed"] = int(rng.integers(0, 1 << 20))
     return case
@@ -375,5 +453,18 @@ def cases(seed, offset=None):
     out = []
     for i, slot in enumerate(SLOTS):
         kind = KINDS[int(rng.integers(0, 6))] if slot == "mixed" else slot
+        out.append(draw_case(rng, seed, slot, kind, combo, stratum, seed + i + offset // 1000))
+    return out
+
+
+def cases2(seed, offset=None):
+    """the seven cases of a seed of the second slate, in the order of SLOTS2"""
+    seed, offset = int(seed), OFFSET if offset is None else int(offset)
+    rng = np.random.default_rng(BASE2 + seed + offset)
+    combo = COMBOS[seed % 4]
+    stratum = STRATA[(seed // 4) % 7] if seed < STRATIFIED else "free"
+    out = []
+    for i, slot in enumerate(SLOTS2):
+        kind = KINDS2[int(rng.integers(0, 6))] if slot == "mixed" else slot
         out.append(draw_case(rng, seed, slot, kind, combo, stratum, seed + i + offset // 1000))
     return out

@@ -85,8 +85,9 @@ def check_terms(got, X, prev, band, what, skip=0):
             assert np.all(g[:skip] == 0), (what, name, "the term against the zero row is not zero")
 
 
-def check_sums(got, X, prev, n, every, first, band, exact, what):
-    """any grid: promise 3 per component, with promise 4 on top where the route is not bit-identical"""
+def check_sums(got, X, prev, n, every, first, band, exact, what, scale=1.0):
+    """any grid: promise 3 per component, with promise 4 on top where the route is not bit-identical (scale: what its BAR is
+    multiplied by on a route whose rows are held to another bar)"""
     got = numpy_of(got)
     s = slice(band[0], band[0] + band[1])
     re, im = terms_of(X[:n, s], None if prev is None else prev[s])
@@ -105,7 +106,7 @@ def check_sums(got, X, prev, n, every, first, band, exact, what):
         T = np.add.reduceat(np.abs(t).astype(hi), starts, axis=0)
         bar = (L - 1) * u / (1 - (L - 1) * u) * T + L * uw * T
         if not exact:
-            bar = bar + L * hi(BAR) * xmax
+            bar = bar + L * hi(BAR * scale) * xmax
         err = np.abs(g.astype(hi) - S)
         bad = err > bar
         assert not bad.any(), (what, name, int(bad.sum()), float((err / np.maximum(bar, np.finfo(hi).tiny)).max()))

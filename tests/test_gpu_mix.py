@@ -94,7 +94,8 @@ def mix_ref(X, chan, w, every, first, band):
     return re, im, bar_w, bar_r
 
 
-def check_mix(got, X, chan, w, every, first, band, exact, what):
+def check_mix(got, X, chan, w, every, first, band, exact, what, scale=1.0):
+    """scale: what the row deviation E_ROW is multiplied by on a route whose rows are held to another bar"""
     got = numpy_of(got)
     re, im, bar_w, bar_r = mix_ref(X, chan, w, every, first, band)
     assert got.shape == re.shape and got.dtype == X.dtype, (what, got.shape, re.shape, got.dtype)
@@ -106,7 +107,7 @@ def check_mix(got, X, chan, w, every, first, band, exact, what):
         return
     u = float(np.finfo(X.real.dtype).eps) / 2
     k = len(chan) + 1
-    bar = E_ROW * bar_w + (k * u / (1 - k * u)) * bar_r
+    bar = E_ROW * scale * bar_w + (k * u / (1 - k * u)) * bar_r
     worst = max(float((np.abs(gr.astype(np.float64) - re) - bar).max()), float((np.abs(gi.astype(np.float64) - im) - bar).max()))
     print(what, "largest deviation over its bar:", float(np.maximum(np.abs(gr - re), np.abs(gi - im)).max()), "/", float(bar.min()))
     assert worst <= 0, (what, worst)

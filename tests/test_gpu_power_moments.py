@@ -87,16 +87,17 @@ def usable(q, what):
     assert float(q.max()) > float(np.finfo(q.dtype).tiny), (what, float(q.max()))
 
 
-def bar2(pmax):
-    """what check() takes for pmax so that its L * BAR * pmax is promise (5)'s L * delta * (2 pmax + delta)"""
-    return pmax * (2.0 * pmax + BAR * pmax)
+def bar2(pmax, scale=1.0):
+    """what check() takes for pmax so that its L * BAR * pmax is promise (5)'s L * delta * (2 pmax + delta), delta = BAR * scale *
+    pmax (scale: what BAR is multiplied by on a route whose rows are held to another bar; it enters delta once)"""
+    return scale * pmax * (2.0 * pmax + BAR * scale * pmax)
 
 
-def check_pair(got, want1, want2, lens, exact, pmax, what):
+def check_pair(got, want1, want2, lens, exact, pmax, what, scale=1.0):
     got = numpy_of(got)
     assert got.ndim == 3 and got.shape[-1] == 2 and got.shape[:2] == want1.shape == want2.shape, (what, got.shape, want1.shape)
-    check(np.ascontiguousarray(got[..., 0]), want1, lens, exact, pmax, (what, "s1"))
-    check(np.ascontiguousarray(got[..., 1]), want2, lens, exact, bar2(pmax), (what, "s2"))
+    check(np.ascontiguousarray(got[..., 0]), want1, lens, exact, scale * pmax, (what, "s1"))
+    check(np.ascontiguousarray(got[..., 1]), want2, lens, exact, bar2(pmax, scale), (what, "s2"))
 
 
 def check_band(got, combo, window, m, n, every, first, band, exact, what):
