@@ -52,6 +52,8 @@ const char* sdft_hip_last_error(void);
   std::size_t sdft_hip_pairs_##SUF(const void* plan);                                                                  \
   long sdft_hip_sdft_cross_sum_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, \
                                        std::size_t bin0, std::size_t nbins, void* sums);                               \
+  long sdft_hip_sdft_cross_smooth_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, \
+                                          std::size_t bin0, std::size_t nbins, double decay, void* state, void* smooth); \
   long sdft_hip_sdft_lag_sum_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, \
                                      std::size_t bin0, std::size_t nbins, void* sums);                                 \
   int sdft_hip_set_array_##SUF(void* plan, std::size_t nch, const std::size_t* chan);                                  \
@@ -115,6 +117,7 @@ namespace sdft
       static int set_pairs(void* p, std::size_t np, const std::size_t* a, const std::size_t* b) { return sdft_hip_set_pairs_##SUF(p, np, a, b); } \
       static std::size_t pairs(const void* p) { return sdft_hip_pairs_##SUF(p); } \
       static long sdft_cross_sum_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_cross_sum_n_##SUF(p, n, x, e, f, b, k, d); } \
+      static long sdft_cross_smooth_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, double a, void* s, void* d) { return sdft_hip_sdft_cross_smooth_n_##SUF(p, n, x, e, f, b, k, a, s, d); } \
       static long sdft_lag_sum_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_lag_sum_n_##SUF(p, n, x, e, f, b, k, d); } \
       static int set_array(void* p, std::size_t nc, const std::size_t* c) { return sdft_hip_set_array_##SUF(p, nc, c); } \
       static std::size_t array_channels(const void* p) { return sdft_hip_array_channels_##SUF(p); } \
@@ -385,6 +388,28 @@ namespace sdft
       {
         const char* e = sdft_hip_last_error();
         throw std::runtime_error(std::string("sdft_hip_sdft_cross_sum_n: ") + (e ? e : "failed"));
+      }
+      return static_cast<std::size_t>(rows);
+    }
+
+    /**
+     * Smoothed cross-spectrum analysis (sdft_hip_sdft_cross_smooth_n): per pair (a, b) of the installed list the one-pole average
+     * s = a * s + (1 - a) * X_a conj(X_b) of cross_sum()'s every == 1 term, each component on its own, a = F(decay), advanced at
+     * every sample and kept on power()'s grid; samples is (channels, nsamples), out is dense (pairs(), rows, nbins), row r the
+     * average after the sample first + r * every.  state is (pairs(), nbins) complex numbers of the band, read on entry and
+     * written on return (nullptr: from zero, the end value is dropped); a stream passes it from call to call with the next first.
+     * out may be nullptr when no row is kept.  The state of every channel advances over all samples and all bins.  Returns the
+     * number of rows kept.
+     **/
+    std::size_t cross_smooth(const std::size_t nsamples, const T* samples, const std::size_t every, const std::size_t first,
+                             const std::size_t bin0, const std::size_t nbins, const double decay, std::complex<F>* const state,
+                             std::complex<F>* const out)
+    {
+      const long rows = api::sdft_cross_smooth_n(plan_, nsamples, samples, every, first, bin0, nbins, decay, state, out);
+      if (rows < 0)
+      {
+        const char* e = sdft_hip_last_error();
+        throw std::runtime_error(std::string("sdft_hip_sdft_cross_smooth_n: ") + (e ? e : "failed"));
       }
       return static_cast<std::size_t>(rows);
     }

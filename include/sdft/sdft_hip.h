@@ -485,6 +485,57 @@ long sdft_hip_sdft_cross_sum_n(sdft_t* sdft, const sdft_size_t nsamples, const s
                                const sdft_size_t bin0, const sdft_size_t nbins,
                                sdft_fdx_t* sums) SDFT_HIP_SYMBOL(sdft_cross_sum_n);
 
+/* ---- smoothed cross-spectrum analysis ---------------------------------------------------------------
+   The estimator an online multichannel host runs: the recursive cross-spectrum
+     S_ab[t][k] = a * S_ab[t-1][k] + (1 - a) * X_a[t][k] conj(X_b[t][k])
+   advanced at EVERY sample and kept on a row grid.  With S_aa and S_bb from the same call (the pairs (a, a) and (b, b)) it gives
+   time-varying coherence, transfer functions and GCC-PHAT tracking; it is the forgetting-factor covariance of an online MVDR / GEV
+   beamformer.  sdft_hip_sdft_cross_smooth_n uses the pair list of sdft_hip_set_pairs (repeats and a == b allowed, as for
+   sdft_hip_sdft_cross_sum_n) and takes grid, rows, the next call's first, every > nsamples, the band and the pointer rules (host or
+   device memory, each pointer on its own; option "async" applies to device pointers; smooth may be NULL when the call keeps no
+   row) from sdft_hip_sdft_power_smooth_n, unchanged.  samples is [channels][nsamples]; smooth is [npairs][rows][nbins] complex
+   (re, im), dense, aligned to sizeof(sdft_fd_t) only.
+   The value, exactly.  With (re, im) the term of sdft_hip_sdft_cross_sum_n at sample t, A and B the windowed bins,
+     re = fl( fl(A.re * B.re) + fl(A.im * B.im) )     im = fl( fl(A.im * B.re) - fl(A.re * B.im) )
+     a = (sdft_fd_t)decay     b = (sdft_fd_t)1 - a
+   each component separately runs s = fl( fl(a * s) + fl(b * term) ) in sdft_fd_t, no fused multiply-add.  Row r is s after the
+   update of sample first + r * every.  state is [npairs][nbins] complex (the bins of the band only), read on entry and written on
+   return, host or device memory whatever the other pointers are; NULL starts from zero and drops the end value.  It is written
+   only after the whole call has succeeded.  A call that keeps no row still advances state.  A call on host memory beyond option
+   "stage_bytes" goes in time segments with state passed along on the device; "last_segments" then answers their number.  A long
+   call cuts time into chunks and carries s across them with the two ordered kernels of sdft_hip_sdft_power_smooth_n, which see a
+   pair's row as 2 * nbins real numbers.
+   Seven things are promised.
+   (1) The same plan, options and input give the same bits on every run: no atomics.
+   (2) A call of one time chunk ("last_chunks" = 1; every call shorter than 512 samples is one) is bit for bit the sequential
+       expression above on the reference's rows, wherever sdft_sdft_n is bit-identical to the reference (FD float, FD double with
+       option "carry" = 1, calls shorter than 512 samples) -- for any every, first, band, pointer placement and staging.
+   (3) A stream cut into one-chunk calls that pass state and the next first along has the bits of that sequential loop over the
+       whole signal, wherever it is cut.
+   (4) Pair (a, a): re is sdft_hip_sdft_power_smooth_n's value for channel a bit for bit, given the same decay, the same grid and
+       the re half of the state, on every route where both calls cut time alike ("last_chunk_len" equal); im stays +0 from a +0
+       state.  Pair (b, a) equals the conjugate of pair (a, b) as numbers (zeros may differ in sign).  A repeated pair gives
+       identical bits.
+   (5) decay == 0 gives the every == 1 term of sdft_hip_sdft_cross_sum_n at the grid's samples, equal as numbers (a -0 term may
+       come out as +0), on every route and any chunking.
+   (6) Calls of several chunks: with u = 2^-24 (float) or 2^-53 (double), s the exact recursion on the sdft_fd_t terms and the
+       rounded coefficients and M the running largest of the majorant m[t] = a * m[t-1] + b * |term[t]|, m[-1] = |state|, per
+       component and barring underflow
+         |smooth - s| <= 8 u M / (1 - a)
+       (DESIGN.md has the derivation: that of sdft_hip_sdft_power_smooth_n with |s| <= m in the place of s >= 0), and likewise
+       the returned state.  On the routes that are not bit-identical the cross-spectrum call's term deviation comes on top:
+       2.1e-11 * max|X_a| * max|X_b|, with no factor 1 / (1 - a).
+   (7) The stream state afterwards is the one sdft_sdft_n of the same samples leaves for EVERY channel of the plan, whether it
+       appears in no pair, in one or in many.  Any other entry point may follow.
+   The call is never resident, pipelined or fused and always runs its own kernel ("last_kernel" = 16).  Returns the number of rows
+   written (0 for nsamples == 0), or -1 with sdft_hip_last_error() set, the stream state and *state untouched: a NULL plan, no
+   pairs installed, every == 0, nbins == 0, bin0 + nbins > dftsize, a decay that is NaN, negative or not below 1 after rounding to
+   sdft_fd_t, smooth == NULL with rows > 0, or a workspace that cannot be reserved. */
+long sdft_hip_sdft_cross_smooth_n(sdft_t* sdft, const sdft_size_t nsamples, const sdft_td_t* samples,
+                                  const sdft_size_t every, const sdft_size_t first,
+                                  const sdft_size_t bin0, const sdft_size_t nbins,
+                                  const double decay, sdft_fdx_t* state, sdft_fdx_t* smooth) SDFT_HIP_SYMBOL(sdft_cross_smooth_n);
+
 /* ---- lag-product analysis --------------------------------------------------------------------------
    What a sliding DFT has over a hopped STFT is a row per sample, and the first thing a phase vocoder, a sinusoidal tracker, a
    reassignment or a Doppler (pulse-pair) estimator does with a row per sample is the phase advance of every bin from one sample to
@@ -728,7 +779,7 @@ double sdft_hip_time_hops(sdft_t* sdft, size_t hops, size_t hop, const sdft_td_t
    "relay_flow", "relay_groups", "chain_debug", "inverse_nt", "inverse_nt_skip_mb", "inverse_step", "inverse_ordered", "host_direct", "copy_streams", "prefix_cells", "array_group", "mix_group", "mix_block" (sdft_capi.inc names what each selects);
    get_option "test_hooks" = 1 in that build.
    get_option additionally answers "tiles", "bins_per_lane", "row_slots", "last_chunks",
-   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis, 6 pooled power analysis, 7 filterbank analysis, 8 pooled cross-spectrum analysis, 9 array covariance analysis, 10 channel-mix analysis, 11 peak-hold analysis), 12 (lag-product analysis), 13 (power-moments analysis), 14 (band-peak analysis) or 15 (smoothed power analysis), "last_segments", "last_fused",
+   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis, 6 pooled power analysis, 7 filterbank analysis, 8 pooled cross-spectrum analysis, 9 array covariance analysis, 10 channel-mix analysis, 11 peak-hold analysis), 12 (lag-product analysis), 13 (power-moments analysis), 14 (band-peak analysis), 15 (smoothed power analysis) or 16 (smoothed cross-spectrum analysis), "last_segments", "last_fused",
    "last_filterbank_launches" (forward_filterbank_kernel launches of the last filterbank call, over all of its host segments: more than its carry segments once its pieces exceed the workspace bound),
    "last_band_peak_launches" (its twin: forward_band_peak_kernel launches of the last band-peak call),
    "last_chain", "last_fused_exact", "last_fused_fold", "last_process_path" (1 fused kernel, 2 hop pair, 3 two-pass),

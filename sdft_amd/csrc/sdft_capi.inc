@@ -132,6 +132,10 @@ int SDFT_FN(set_pairs)(void* p, size_t npairs, const size_t* pair_a, const size_
 size_t SDFT_FN(pairs)(const void* p) { return p ? P(p)->pairs_count() : 0; }
 long SDFT_FN(sdft_cross_sum_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, size_t bin0, size_t nbins, SDFT_FD* sums)
 { return SDFT_GRID_CALL(sdft_cross_sum_n, n, x, every, first, bin0, nbins, sums); }
+// smoothed cross-spectrum analysis: the one-pole average of A conj(B) of those pairs, advanced at every sample and kept on the grid; see sdft_hip.h
+long SDFT_FN(sdft_cross_smooth_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, size_t bin0, size_t nbins, double decay,
+                                  SDFT_FD* state, SDFT_FD* smooth)
+{ return SDFT_GRID_CALL(sdft_cross_smooth_n, n, x, every, first, bin0, nbins, decay, state, smooth); }
 // lag-product analysis: X[t] conj(X[t - 1]) of every channel summed over those windows; see sdft_hip.h
 long SDFT_FN(sdft_lag_sum_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, size_t bin0, size_t nbins, SDFT_FD* sums)
 { return SDFT_GRID_CALL(sdft_lag_sum_n, n, x, every, first, bin0, nbins, sums); }

@@ -25,6 +25,10 @@
 //                          later chunks left out of their rows (sdft_hip_sdft_power_smooth_n)
 //   sdft_forward_cross_sum.hpp K1x forward_cross_sum_kernel: the pooled power kernel with a second channel -- A conj(B) of the windowed
 //                          bins of two channels of a plan, summed in registers over the windows of the grid (sdft_hip_sdft_cross_sum_n)
+//   sdft_forward_cross_smooth.hpp K1xs forward_cross_smooth_kernel: the cross-spectrum kernel with the smoothed power kernel's recursion
+//                          for the sums -- the one-pole average of A conj(B) per component, advanced at every sample and stored on the
+//                          grid; smooth_scan_kernel and smooth_fix_kernel carry it across the time chunks as 2 * nbins real numbers
+//                          per pair (sdft_hip_sdft_cross_smooth_n)
 //   sdft_forward_lag_sum.hpp K1l forward_lag_sum_kernel: the pooled power kernel with the cross-spectrum kernel's term between a row and
 //                          the row before it -- X[t] conj(X[t - 1]) of one channel, the previous row of a chunk's first sample
 //                          demodulated from the chunk's carry-in (sdft_hip_sdft_lag_sum_n)
@@ -76,6 +80,7 @@
 #include "sdft_forward_power_peak.hpp"
 #include "sdft_forward_power_smooth.hpp"
 #include "sdft_forward_cross_sum.hpp"
+#include "sdft_forward_cross_smooth.hpp"
 #include "sdft_forward_lag_sum.hpp"
 #include "sdft_forward_power_moments.hpp"
 #include "sdft_forward_covariance.hpp"

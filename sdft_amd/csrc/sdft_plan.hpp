@@ -205,7 +205,7 @@ class Plan
   long opt_prefix_cells = 1;     // test hook: the prefix-cell route of long calls (logic::ForwardQuery::prefix_cells)
   long last_prefix = 0;          // the last analysis call took it (one pre-pass launch: prefix_cells_kernel)
 
-  long last_kernel = 0;          // 1 = forward_kernel (independent tiles), 2 = forward_rows_kernel, 3 = hop, 4 = forward_every_kernel, 5 = forward_power_kernel, 6 = forward_pooled_power_kernel, 7 = forward_filterbank_kernel, 8 = forward_cross_sum_kernel, 9 = forward_covariance_kernel, 10 = forward_mix_kernel, 11 = forward_power_peak_kernel, 12 = forward_lag_sum_kernel, 13 = forward_power_moments_kernel, 14 = forward_band_peak_kernel, 15 = forward_power_smooth_kernel
+  long last_kernel = 0;          // 1 = forward_kernel (independent tiles), 2 = forward_rows_kernel, 3 = hop, 4 = forward_every_kernel, 5 = forward_power_kernel, 6 = forward_pooled_power_kernel, 7 = forward_filterbank_kernel, 8 = forward_cross_sum_kernel, 9 = forward_covariance_kernel, 10 = forward_mix_kernel, 11 = forward_power_peak_kernel, 12 = forward_lag_sum_kernel, 13 = forward_power_moments_kernel, 14 = forward_band_peak_kernel, 15 = forward_power_smooth_kernel, 16 = forward_cross_smooth_kernel
 
   // device-resident stream state
   DevBuf<fdx> d_tw, d_syn, d_wtab;
@@ -256,6 +256,9 @@ class Plan
   DevBuf<FD> d_smooth_ws, d_smooth_state, d_smooth_pw;
   FD smooth_pw_a = (FD)-1;                                   // (no decay is negative: nothing is cached yet)
   size_t smooth_pw_len = 0;
+  // smoothed cross-spectrum analysis: d_smooth_ws and d_smooth_pw above serve it with pairs for channels and (re, im) rows of twice
+  // the band; its s between the caller's state and the kernels [pairs][band] complex, and a segment's rows on their way to a host buffer
+  DevBuf<FD> d_cross_smooth_state, d_cross_smooth_stage;
   // filterbank analysis: the installed filterbank (sdft_hip_set_filterbank) as the host gave it, its decomposition for the plan's
   // tiles (logic::filterbank_layout), the device copies the kernels read, and the workspace of split bands [channels][rows][slots]
   struct Filterbank
@@ -358,7 +361,7 @@ class Plan
     d_delta.release(); d_carry.release(); d_seed.release(); d_prefix.release();
     d_stage_td.release(); d_stage_fdx.release(); d_rowptr.release(); d_fseed.release();
     d_psum_ws.release(); d_psum_head.release();
-    d_smooth_ws.release(); d_smooth_state.release(); d_smooth_pw.release();
+    d_smooth_ws.release(); d_smooth_state.release(); d_smooth_pw.release(); d_cross_smooth_state.release(); d_cross_smooth_stage.release();
     d_fb_pieces.release(); d_fb_tile0.release(); d_fb_splits.release(); d_fb_weights.release(); d_fb_ws.release();
     d_cross_items.release(); d_cross_ws.release(); d_cross_head.release(); d_cross_stage.release();
     d_cov_items.release(); d_cov_chan.release(); d_cov_ws.release(); d_cov_head.release(); d_cov_stage.release();
@@ -610,6 +613,7 @@ class Plan
   // FILTERBANK: filterbank analysis (sdft_filterbank_n) -- forward_filterbank_kernel stores the band sums of the plan's filterbank
   // BAND_PEAK: band-peak analysis (sdft_band_peak_n) -- forward_band_peak_kernel stores per band of that filterbank the largest weighted power and its bin, as a pair; fbk as FILTERBANK's, a pair for a number
   // CROSS_SUM: cross-spectrum analysis (sdft_cross_sum_n) -- forward_cross_sum_kernel sums A conj(B) of the plan's pairs over the grid's windows
+  // CROSS_SMOOTH: smoothed cross-spectrum analysis (sdft_cross_smooth_n) -- forward_cross_smooth_kernel runs the one-pole average of that term at every sample and stores it on the grid; the carry across chunks is POWER_SMOOTH's over 2 * band numbers per pair
   // LAG_SUM: lag-product analysis (sdft_lag_sum_n) -- forward_lag_sum_kernel sums X[t] conj(X[t - 1]) of every channel over those windows; cross has the plan's channels in the pairs' place and no items
   // POWER_MOMENTS: power-moments analysis (sdft_power_moments_n) -- forward_power_moments_kernel sums the power and its square of every channel over those windows, as (s1, s2) pairs; cross as LAG_SUM's
   // COVARIANCE: covariance analysis (sdft_covariance_n) -- forward_covariance_kernel does that for all pairs of the plan's array, by blocks
@@ -618,7 +622,7 @@ class Plan
   {
     enum Kind : int { PLAIN = 0, FUSE = -1, EVERY = logic::FK_EVERY, POWER = logic::FK_POWER, POWER_SUM = logic::FK_POWER_SUM, FILTERBANK = logic::FK_FILTERBANK,
                       CROSS_SUM = logic::FK_CROSS_SUM, COVARIANCE = logic::FK_COVARIANCE, MIX = logic::FK_MIX, POWER_PEAK = logic::FK_POWER_PEAK, LAG_SUM = logic::FK_LAG_SUM,
-                      POWER_MOMENTS = logic::FK_POWER_MOMENTS, BAND_PEAK = logic::FK_BAND_PEAK, POWER_SMOOTH = logic::FK_POWER_SMOOTH };
+                      POWER_MOMENTS = logic::FK_POWER_MOMENTS, BAND_PEAK = logic::FK_BAND_PEAK, POWER_SMOOTH = logic::FK_POWER_SMOOTH, CROSS_SMOOTH = logic::FK_CROSS_SMOOTH };
     Kind kind = PLAIN;
     int hold = 0;                                            // POWER_PEAK
     const PowerSmoothArgs<FD>* smooth = nullptr;             // POWER_SMOOTH
@@ -628,6 +632,7 @@ class Plan
     const PowerSumArgs<FD>* psum = nullptr;                  // POWER_SUM, POWER_PEAK
     const FilterbankArgs<FD>* fbk = nullptr;                 // FILTERBANK, BAND_PEAK
     const CrossSumArgs<FD>* cross = nullptr;                 // CROSS_SUM, LAG_SUM, POWER_MOMENTS
+    const CrossSmoothArgs<FD>* xsmooth = nullptr;            // CROSS_SMOOTH
     const CovarianceArgs<FD>* cov = nullptr;                 // COVARIANCE
     const MixArgs<FD>* mix = nullptr;                        // MIX
     static ForwardCall of(Kind k) { ForwardCall c; c.kind = k; return c; }
@@ -640,6 +645,7 @@ class Plan
     static ForwardCall filterbank(const FilterbankArgs<FD>& a) { ForwardCall c = of(FILTERBANK); c.fbk = &a; return c; }
     static ForwardCall band_peak(const FilterbankArgs<FD>& a) { ForwardCall c = of(BAND_PEAK); c.fbk = &a; return c; }
     static ForwardCall cross_sum(const CrossSumArgs<FD>& a) { ForwardCall c = of(CROSS_SUM); c.cross = &a; return c; }
+    static ForwardCall cross_smooth(const CrossSmoothArgs<FD>& a) { ForwardCall c = of(CROSS_SMOOTH); c.xsmooth = &a; return c; }
     static ForwardCall lag_sum(const CrossSumArgs<FD>& a) { ForwardCall c = of(LAG_SUM); c.cross = &a; return c; }
     static ForwardCall power_moments(const CrossSumArgs<FD>& a) { ForwardCall c = of(POWER_MOMENTS); c.cross = &a; return c; }
     static ForwardCall covariance(const CovarianceArgs<FD>& a) { ForwardCall c = of(COVARIANCE); c.cov = &a; return c; }
@@ -694,12 +700,13 @@ class Plan
     q.filterbank = c.kind == ForwardCall::FILTERBANK;
     q.band_peak = c.kind == ForwardCall::BAND_PEAK;
     q.cross_sum = c.kind == ForwardCall::CROSS_SUM;
+    q.cross_smooth = c.kind == ForwardCall::CROSS_SMOOTH;
     q.lag_sum = c.kind == ForwardCall::LAG_SUM;
     q.power_moments = c.kind == ForwardCall::POWER_MOMENTS;
     q.covariance = c.kind == ForwardCall::COVARIANCE;
     q.mix = c.kind == ForwardCall::MIX;
     q.power_every = q.power ? (size_t)c.power->every : (q.filterbank || q.band_peak) ? (size_t)c.fbk->every : q.mix ? (size_t)c.mix->every : 1;
-    q.cross_items = c.cross ? c.cross->nitems : q.covariance ? c.cov->nitems : q.mix ? c.mix->nitems : 0;
+    q.cross_items = c.cross ? c.cross->nitems : c.xsmooth ? c.xsmooth->nitems : q.covariance ? c.cov->nitems : q.mix ? c.mix->nitems : 0;
     q.row_pointers = rows != nullptr;
     q.out = reinterpret_cast<uintptr_t>(out);
     q.out_stride = out_stride;
@@ -926,7 +933,7 @@ class Plan
       if (!d_cov_ws.reserve(logic::covariance_workspace(cv.nch, (size_t)chunks, cv.nbins_out))) return false;
       cv.ws = chunks > 1 ? d_cov_ws.p : nullptr;
     }
-    const size_t launch_channels = c.cross ? cs.nitems : c.cov ? cv.nitems : c.mix ? c.mix->nitems : channels;
+    const size_t launch_channels = c.cross ? cs.nitems : c.xsmooth ? c.xsmooth->nitems : c.cov ? cv.nitems : c.mix ? c.mix->nitems : channels;
     // pooled power and peak-hold analysis: the workspace of the windows a chunk boundary cuts (grown on demand, kept by the plan)
     PowerSumArgs<FD> ps{};
     if (c.psum)
@@ -952,6 +959,28 @@ class Plan
           smooth_pw_a = sm.a; smooth_pw_len = (size_t)r.len;
         }
         sm.ends = d_smooth_ws.p; sm.pw = d_smooth_pw.p;
+      }
+    }
+    // smoothed cross-spectrum analysis: the same workspace and table with the pairs for channels and rows of 2 * band numbers; xc is
+    // what the scan and the fix-up see of the call
+    CrossSmoothArgs<FD> xs{};
+    PowerSmoothArgs<FD> xc{};
+    if (c.xsmooth)
+    {
+      xs = *c.xsmooth;
+      if (chunks > 1)
+      {
+        const size_t unit_row = logic::cross_smooth_unit_row(xs.nbins_out);
+        if (!d_smooth_ws.reserve(logic::power_smooth_workspace(xs.npairs, (size_t)chunks, unit_row))) return false;
+        if (smooth_pw_a != xs.a || smooth_pw_len != (size_t)r.len)
+        {
+          const std::vector<FD> table = logic::power_smooth_table<FD>(xs.a, (size_t)r.len);
+          smooth_pw_a = (FD)-1;                              // (as above)
+          if (!d_smooth_pw.reserve(table.size()) || !to_device(d_smooth_pw.p, table.data(), table.size() * sizeof(FD))) return false;
+          smooth_pw_a = xs.a; smooth_pw_len = (size_t)r.len;
+        }
+        xs.ends = d_smooth_ws.p;
+        xc = PowerSmoothArgs<FD>{xs.out, xs.out_stride, xs.state_in, xs.state_out, xs.ends, d_smooth_pw.p, xs.a, xs.b, xs.every, xs.first, 2u * xs.bin0, (unsigned)unit_row};
       }
     }
     // filterbank and band-peak analysis: the workspace of the bands a tile boundary cuts, [channels][rows of a launch][slots]
@@ -1047,6 +1076,7 @@ class Plan
       case K::POWER_PEAK: if (!grid_fits(blocks)) return false; launch_forward_power_peak(fa, ps, (unsigned)blocks, c.hold); break;
       case K::POWER_SUM: if (!grid_fits(blocks)) return false; launch_forward_power_sum(fa, ps, (unsigned)blocks); break;
       case K::POWER_SMOOTH: if (!grid_fits(blocks)) return false; launch_forward_power_smooth(fa, sm, (unsigned)blocks); break;
+      case K::CROSS_SMOOTH: if (!grid_fits(blocks)) return false; launch_forward_cross_smooth(fa, xs, (unsigned)blocks); break;
       case K::POWER: if (!grid_fits(blocks)) return false; launch_forward_power(fa, *c.power, (unsigned)blocks); break;
       case K::EVERY: if (!grid_fits(blocks)) return false; launch_forward_every(fa, *c.every, (unsigned)blocks); break;
       }
@@ -1068,9 +1098,17 @@ class Plan
     // the smoothed power call's carry across chunks: the scan of the end values, then what the chunks c >= 1 left out of their rows
     if (chunks > 1 && c.smooth)
     {
-      if (!launch_smooth_scan(sm, n, chunks, r.len, r.shift)) return false;
+      if (!launch_smooth_scan(sm, n, chunks, r.len, r.shift, channels)) return false;
       const size_t kept = logic::every_rows(n, (size_t)sm.every, (size_t)sm.first);
-      if (kept && !launch_smooth_fix(sm, kept, chunks, r.len, r.shift)) return false;
+      if (kept && !launch_smooth_fix(sm, kept, chunks, r.len, r.shift, channels)) return false;
+      SDFT_TRY(hipGetLastError());
+    }
+    // the smoothed cross-spectrum call's: the same two kernels over its pairs
+    if (chunks > 1 && c.xsmooth)
+    {
+      if (!launch_smooth_scan(xc, n, chunks, r.len, r.shift, xs.npairs)) return false;
+      const size_t kept = logic::every_rows(n, (size_t)xs.every, (size_t)xs.first);
+      if (kept && !launch_smooth_fix(xc, kept, chunks, r.len, r.shift, xs.npairs)) return false;
       SDFT_TRY(hipGetLastError());
     }
     if (r.flow) SDFT_TRY(hipStreamWaitEvent(stream, seg_events[0], 0));          // the call ends when both launches have

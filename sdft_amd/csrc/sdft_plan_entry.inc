@@ -106,13 +106,13 @@
     return true;
   }
 
-  // ---- grid analysis calls: sdft_every_n and its eleven siblings ---------------------------------------------------------------
-  // What the twelve share.  The stream state after a call is the one sdft_n leaves on the same samples.  A call is never resident,
+  // ---- grid analysis calls: sdft_every_n and its twelve siblings ---------------------------------------------------------------
+  // What the thirteen share.  The stream state after a call is the one sdft_n leaves on the same samples.  A call is never resident,
   // pipelined or fused: whatever is in flight is retired / joined first, then one forward call on the plan's stream with the
   // call's own kernel (ForwardCall).  `rows` receives the row count.  Device samples and a device output take that one call; host
   // memory goes through device scratch in time segments of at most logic::grid_segment samples, each segment a call of its own
   // under the streaming contract, with its own first.
-  // The every-grid calls (every, power, power_smooth, filterbank, band_peak, mix) keep the rows of the samples first, first + every, ... < n; a segment
+  // The every-grid calls (every, power, power_smooth, cross_smooth, filterbank, band_peak, mix) keep the rows of the samples first, first + every, ... < n; a segment
   // keeps the rows of the grid that fall into it.  The pooled calls (power_sum, power_peak, power_moments, cross_sum, lag_sum, covariance) write
   // one row per window the grid cuts the call into (logic::power_sum_window), row 0 the head window [0, first) when first > 0; a
   // segment that starts inside a window has a head row of its own, which is kept apart (the call's head buffer) and joined into
@@ -483,6 +483,51 @@
                                p.grid.every, p.grid.first, (unsigned)bin0, (unsigned)nbins_out};
       return forward_device(p.m, p.td, p.td_stride, nullptr, 0, nullptr, ForwardCall::cross_sum(g));
     });
+  }
+
+  // smoothed cross-spectrum analysis (sdft_hip_sdft_cross_smooth_n): per pair (a, b) of the installed list and per component of
+  // A conj(B), s[t] = fl(fl(a * s[t - 1]) + fl(b * term[t])), advanced at every sample and kept on the grid, dense
+  // [npairs][rows][nbins_out] complex numbers -- forward_cross_smooth_kernel, then, in a call of more than one chunk,
+  // smooth_scan_kernel and smooth_fix_kernel over 2 * nbins_out real numbers per pair.  sdft_power_smooth_n's path with the pairs
+  // for units: s travels through the two halves of d_cross_smooth_state, the rows of a host buffer through d_cross_smooth_stage
+  // (the fix-up re-reads the rows it completes).
+  bool sdft_cross_smooth_n(size_t n, const TD* x, size_t every, size_t first, size_t bin0, size_t nbins_out, double decay, FD* state, FD* smooth,
+                           size_t& rows)
+  {
+    static const char* fn = "sdft_hip_sdft_cross_smooth_n";
+    rows = 0;
+    const size_t npairs = pairs_count();
+    if (npairs == 0) { set_error(fn, "no pairs are installed (sdft_hip_set_pairs)"); return false; }
+    const char* const refused = logic::power_smooth_decay_ok<FD>(decay) ? nullptr : "decay must be at least 0 and less than 1 after rounding to sdft_fd_t";
+    if (!grid_args(fn, n, every, first, true, bin0, nbins_out, refused, false, smooth, "smooth", rows)) return false;
+    if (n == 0 || nbins == 0) return true;
+    const FD a = (FD)decay, b = (FD)1 - a;
+    const size_t unit_row = logic::cross_smooth_unit_row(nbins_out);
+    const size_t count = npairs * unit_row;
+    bool state_device = false;
+    int cur = 0;                                             // the half of d_cross_smooth_state that holds s
+    long pieces = 0;                                         // forward calls: more than one when host memory goes in segments
+    auto ready = [&] {
+      if (!d_cross_smooth_state.reserve(2 * count)) return false;
+      state_device = state && on_device(state);
+      if (!state) SDFT_TRY(hipMemsetAsync(d_cross_smooth_state.p, 0, count * sizeof(FD), stream));
+      else if (state_device) SDFT_TRY(hipMemcpyAsync(d_cross_smooth_state.p, state, count * sizeof(FD), hipMemcpyDeviceToDevice, stream));
+      else if (!to_device(d_cross_smooth_state.p, state, count * sizeof(FD))) return false;
+      return true;
+    };
+    if (!every_grid_call(n, x, every, first, smooth, rows, npairs, unit_row, ready, [&](const GridPiece& p, FD* at, size_t at_rows) {
+          const CrossSmoothArgs<FD> g{at, logic::power_channel_stride(at_rows, unit_row), d_cross_smooth_state.p + cur * count,
+                                      d_cross_smooth_state.p + (cur ^ 1) * count, nullptr, d_cross_items.p, (unsigned)pairs.items.size(), (unsigned)npairs,
+                                      a, b, p.grid.every, p.grid.first, (unsigned)bin0, (unsigned)nbins_out};
+          if (!forward_device(p.m, p.td, p.td_stride, nullptr, 0, nullptr, ForwardCall::cross_smooth(g))) return false;
+          cur ^= 1; ++pieces;
+          return true;
+        }, &d_cross_smooth_stage)) return false;
+    if (pieces > 1) last_segments = pieces;                  // (as sdft_power_smooth_n reports them)
+    if (!state) return true;
+    if (!state_device) return to_host(state, d_cross_smooth_state.p + cur * count, count * sizeof(FD));
+    SDFT_TRY(hipMemcpyAsync(state, d_cross_smooth_state.p + cur * count, count * sizeof(FD), hipMemcpyDeviceToDevice, stream));
+    return async || synchronize();
   }
 
   // lag-product analysis (sdft_hip_sdft_lag_sum_n): per channel the sums of X[t] conj(X[t - 1]) over the windows of the grid, dense

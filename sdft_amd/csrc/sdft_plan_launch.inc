@@ -361,22 +361,35 @@
       default:           hipLaunchKernelGGL((forward_power_smooth_kernel<FD, BPL, WIN_BOXCAR>), gr, b, 0, stream, fa, g); break;
     }
   }
-  // its carry across chunks (chunks > 1): one thread per (channel, bin of the band) scans the chunks' end values in ascending order ...
-  bool launch_smooth_scan(const PowerSmoothArgs<FD>& g, size_t n, long chunks, long len, long shift)
+  void launch_forward_cross_smooth(const ForwardArgs<FD>& fa, const CrossSmoothArgs<FD>& g, unsigned blocks)
   {
-    const unsigned long long threads = (unsigned long long)channels * g.nbins_out;
+    constexpr int BPL = sizeof(fdx) == 16 ? 1 : 2;
+    const dim3 gr(blocks), b(kBlock);
+    switch (window)
+    {
+      case WIN_HANN:     hipLaunchKernelGGL((forward_cross_smooth_kernel<FD, BPL, WIN_HANN>), gr, b, 0, stream, fa, g); break;
+      case WIN_HAMMING:  hipLaunchKernelGGL((forward_cross_smooth_kernel<FD, BPL, WIN_HAMMING>), gr, b, 0, stream, fa, g); break;
+      case WIN_BLACKMAN: hipLaunchKernelGGL((forward_cross_smooth_kernel<FD, BPL, WIN_BLACKMAN>), gr, b, 0, stream, fa, g); break;
+      default:           hipLaunchKernelGGL((forward_cross_smooth_kernel<FD, BPL, WIN_BOXCAR>), gr, b, 0, stream, fa, g); break;
+    }
+  }
+  // their carry across chunks (chunks > 1) over `units` channels or pairs: one thread per (unit, number of the unit's row) scans the
+  // chunks' end values in ascending order ...
+  bool launch_smooth_scan(const PowerSmoothArgs<FD>& g, size_t n, long chunks, long len, long shift, size_t units)
+  {
+    const unsigned long long threads = (unsigned long long)units * g.nbins_out;
     const unsigned long long blocks = (threads + kBlock - 1) / kBlock;
     if (!grid_fits(blocks)) return false;
-    hipLaunchKernelGGL((smooth_scan_kernel<FD>), dim3((unsigned)blocks), dim3(kBlock), 0, stream, g, n, (unsigned)chunks, (unsigned)len, (unsigned)shift, (unsigned)channels);
+    hipLaunchKernelGGL((smooth_scan_kernel<FD>), dim3((unsigned)blocks), dim3(kBlock), 0, stream, g, n, (unsigned)chunks, (unsigned)len, (unsigned)shift, (unsigned)units);
     return true;
   }
-  // ... and one thread per (channel, kept row, bin of the band) adds what a chunk c >= 1 left out of the row
-  bool launch_smooth_fix(const PowerSmoothArgs<FD>& g, size_t rows, long chunks, long len, long shift)
+  // ... and one thread per (unit, kept row, number of the row) adds what a chunk c >= 1 left out of the row
+  bool launch_smooth_fix(const PowerSmoothArgs<FD>& g, size_t rows, long chunks, long len, long shift, size_t units)
   {
-    const unsigned long long threads = (unsigned long long)channels * (unsigned long long)rows * g.nbins_out;
+    const unsigned long long threads = (unsigned long long)units * (unsigned long long)rows * g.nbins_out;
     const unsigned long long blocks = (threads + kBlock - 1) / kBlock;
     if (!grid_fits(blocks)) return false;
-    hipLaunchKernelGGL((smooth_fix_kernel<FD>), dim3((unsigned)blocks), dim3(kBlock), 0, stream, g, rows, (unsigned)chunks, (unsigned)len, (unsigned)shift, (unsigned)channels);
+    hipLaunchKernelGGL((smooth_fix_kernel<FD>), dim3((unsigned)blocks), dim3(kBlock), 0, stream, g, rows, (unsigned)chunks, (unsigned)len, (unsigned)shift, (unsigned)units);
     return true;
   }
   void launch_forward_filterbank(const ForwardArgs<FD>& fa, const FilterbankArgs<FD>& g, unsigned blocks)

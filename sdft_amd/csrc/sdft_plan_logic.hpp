@@ -346,6 +346,14 @@ inline PowerSmoothFix power_smooth_fix(size_t t, long len, long shift)
   return {c, t - chunk_begin(c, len, shift) + 1};
 }
 
+// ---- smoothed cross-spectrum analysis (sdft_hip_sdft_cross_smooth_n) -------------------------------------------------------------
+// The same recursion on each component of the cross-spectrum call's every == 1 term (re, im) of a pair, with the pair list's work
+// items (cross_items) in the channels' place.  A unit of the carry is a pair and its row is the 2 * nbins_out real numbers
+// (re, im) of the band: the scan and the fix-up above are real-valued and elementwise, so they serve unchanged with
+// power_smooth_slot / power_smooth_workspace / power_smooth_fix taking (npairs, cross_smooth_unit_row(nbins_out)) for (channels,
+// nbins_out).  The items of the pairs come first and in the pairs' order: item i < npairs is unit i.
+inline size_t cross_smooth_unit_row(size_t nbins_out) { return 2 * nbins_out; }
+
 // ---- pooled cross-spectrum analysis (sdft_hip_sdft_cross_sum_n) ------------------------------------------------------------------
 // Row r of pair p = (a, b) is the sum over the r-th window of the pooled power call's grid of A conj(B), A and B the windowed bins
 // of the channels a and b.  A wave of forward_cross_sum_kernel steps the recurrences of the two channels of ONE work item, so the
@@ -1017,6 +1025,7 @@ struct ForwardQuery
   bool band_peak = false;                 // band-peak analysis (forward_band_peak_kernel) on the grid of power_every: the filterbank call's route and chunk choice (never with filterbank)
   bool cross_sum = false;                 // pooled cross-spectrum analysis (forward_cross_sum_kernel) of ...
   size_t cross_items = 0;                 // ... this many work items (logic::cross_items), which take the channels' place in the launch
+  bool cross_smooth = false;              // smoothed cross-spectrum analysis (forward_cross_smooth_kernel): cross_sum's items, route and chunk choice (never with cross_sum)
   bool covariance = false;                // array covariance analysis (forward_covariance_kernel): cross_items counts its block items (logic::covariance_items)
   bool mix = false;                       // channel-mix analysis (forward_mix_kernel) on the grid of power_every: cross_items counts its items (logic::mix_items)
   bool row_pointers = false;              // rows go to a table of row pointers
@@ -1029,7 +1038,7 @@ struct ForwardQuery
        chain_L = 0, relay_flow = 1, segments = 0, xcd_map = 1, rows_f32 = 1, pipeline = 1;
   long prefix_cells = 1;                  // test hook: 0 = never the prefix-cell route, 1 = calls beyond kSelfMax, 2 = whatever the length
 };
-enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6, FK_FILTERBANK = 7, FK_CROSS_SUM = 8, FK_COVARIANCE = 9, FK_MIX = 10, FK_POWER_PEAK = 11, FK_LAG_SUM = 12, FK_POWER_MOMENTS = 13, FK_BAND_PEAK = 14, FK_POWER_SMOOTH = 15 };     // = get_option "last_kernel"
+enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6, FK_FILTERBANK = 7, FK_CROSS_SUM = 8, FK_COVARIANCE = 9, FK_MIX = 10, FK_POWER_PEAK = 11, FK_LAG_SUM = 12, FK_POWER_MOMENTS = 13, FK_BAND_PEAK = 14, FK_POWER_SMOOTH = 15, FK_CROSS_SMOOTH = 16 };     // = get_option "last_kernel"
 // carries: the single chunk's are the stream state (delta_kernel copies it); pre-pass partial sums + scan (carries from the
 // closed-form table); the serial exact pass (carry_exact_kernel); the relay form of the exact pass (carry_relay_kernel)
 enum CarryForm : int { CARRY_STATE = 0, CARRY_SUMS = 1, CARRY_SERIAL = 2, CARRY_RELAY = 3 };
@@ -1077,10 +1086,10 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   ForwardRoute r;
   const size_t nb = q.nbins, span = 2 * nb, n = q.n, ch = std::max<size_t>(q.channels, 1);
   const bool pow2 = (span & (span - 1)) == 0;
-  // the decimated, the power-spectrogram, the pooled power, the peak-hold, the lag-product, the power-moments, the smoothed power, the filterbank, the band-peak, the cross-spectrum, the covariance and the mix analysis have the tile form only
-  const bool grid = q.every || q.power || q.power_sum || q.power_peak || q.lag_sum || q.power_moments || q.power_smooth || q.filterbank || q.band_peak || q.cross_sum || q.covariance || q.mix;
-  // (channel, chunk) groups of a tile launch per chunk: the cross-spectrum, the covariance and the mix call's are their work items
-  const size_t lanes = (q.cross_sum || q.covariance || q.mix) ? std::max<size_t>(q.cross_items, 1) : ch;
+  // the decimated, the power-spectrogram, the pooled power, the peak-hold, the lag-product, the power-moments, the smoothed power, the filterbank, the band-peak, the cross-spectrum, the smoothed cross-spectrum, the covariance and the mix analysis have the tile form only
+  const bool grid = q.every || q.power || q.power_sum || q.power_peak || q.lag_sum || q.power_moments || q.power_smooth || q.filterbank || q.band_peak || q.cross_sum || q.cross_smooth || q.covariance || q.mix;
+  // (channel, chunk) groups of a tile launch per chunk: the two cross-spectrum, the covariance and the mix call's are their work items
+  const size_t lanes = (q.cross_sum || q.cross_smooth || q.covariance || q.mix) ? std::max<size_t>(q.cross_items, 1) : ch;
   const bool rows = !grid && rows_kernel_ok(nb, q.fdx_bytes, q.row_pointers, q.rows_kernel != 0, q.row_slots_max);
   const bool folded = q.fuse && !q.reference_order && !q.fuse_store && q.fold && q.coeff_ready;
   // pipelined calls (forward_self): decided first because they take the self-carried form at any length and cut time differently
@@ -1106,12 +1115,12 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   {
     EveryQuery e;
     e.n = n; e.channels = lanes; e.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); e.exact = q.exact; e.forced_chunk = q.chunk; e.compute_units = q.compute_units;
-    c = (q.power_sum || q.power_peak || q.lag_sum || q.power_moments || q.power_smooth || q.cross_sum || q.covariance) ? choose_power_sum_chunks(e) : (q.power || q.filterbank || q.band_peak || q.mix) ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
+    c = (q.power_sum || q.power_peak || q.lag_sum || q.power_moments || q.power_smooth || q.cross_sum || q.cross_smooth || q.covariance) ? choose_power_sum_chunks(e) : (q.power || q.filterbank || q.band_peak || q.mix) ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
   }
   else c = choose_chunks(chunk_query(q, rows, r.pipelined));
   r.chunks = c.chunks; r.len = c.len;
   r.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); r.interior = interior_lanes(q.window, q.fdx_bytes, q.interior);
-  r.kernel = q.mix ? FK_MIX : q.covariance ? FK_COVARIANCE : q.cross_sum ? FK_CROSS_SUM : q.filterbank ? FK_FILTERBANK : q.band_peak ? FK_BAND_PEAK : q.power_smooth ? FK_POWER_SMOOTH : q.power_moments ? FK_POWER_MOMENTS : q.lag_sum ? FK_LAG_SUM : q.power_peak ? FK_POWER_PEAK : q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
+  r.kernel = q.mix ? FK_MIX : q.covariance ? FK_COVARIANCE : q.cross_smooth ? FK_CROSS_SMOOTH : q.cross_sum ? FK_CROSS_SUM : q.filterbank ? FK_FILTERBANK : q.band_peak ? FK_BAND_PEAK : q.power_smooth ? FK_POWER_SMOOTH : q.power_moments ? FK_POWER_MOMENTS : q.lag_sum ? FK_LAG_SUM : q.power_peak ? FK_POWER_PEAK : q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
   if (r.chunks == 1 && q.hop_kernel && nb >= 2 && !q.fuse && !grid) { r.kernel = FK_HOP; return r; }
 
   // self-carried chunks: every workgroup derives its carry-in from the raw samples (fold + one FFT in LDS) and forms

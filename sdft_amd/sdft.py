@@ -384,6 +384,37 @@ class SDFT:
             raise ValueError("no pairs are installed: call set_pairs first")
         return self._grid_call("sdft_cross_sum_n", x, power_sum_rows, every, first, (bin0, nb), npairs, nb, self.fdx, out)
 
+    def cross_smooth(self, x, decay: float, every: int = 1, first: int = 0, bins=None, state=None, out=None):
+        """Smoothed cross-spectrum analysis (``sdft_hip_sdft_cross_smooth_n``): per pair ``(a, b)`` of the installed list
+        (:meth:`set_pairs`) the one-pole average ``s = a * s + b * X_a * conj(X_b)`` of :meth:`cross_sum`'s ``every = 1`` term, each
+        component on its own, ``(a, b) = smooth_coefficients(decay, dtype)``, advanced at every sample and kept on :meth:`power`'s
+        grid -> complex array of shape (npairs, rows, nbins), numpy for numpy input, a device tensor for a device tensor: row r is
+        the average after the sample ``first + r * every``.  ``x`` is (channels, n) [(n,) for a single-channel plan].  ``state`` is a
+        numpy array or a device tensor (whatever ``x`` is) of shape (npairs, nbins) in the complex FD dtype, updated in place: the
+        average before the first sample on entry, after the last on return; ``None`` starts from zero and drops the end value.  A
+        stream passes ``state`` and :func:`every_next_first` from call to call; :func:`coherence` relates the pairs ``(a, b)``,
+        ``(a, a)`` and ``(b, b)`` of one call.  The state of every channel of the plan advances over all n samples and all bins, as
+        with :meth:`sdft`."""
+        self.api.clear()
+        every, first, bin0, nb = _grid_args(self.dftsize, every, first, bins)
+        smooth_coefficients(decay, self.fd)                  # (raises for a decay the library would refuse)
+        npairs = self.pairs
+        if npairs == 0:
+            raise ValueError("no pairs are installed: call set_pairs first")
+        sp = None
+        if state is not None:
+            shape = (npairs, nb)
+            if _is_tensor(state):
+                self._check_tensor(state, "state", self.fdx, shape)
+                sp = state.data_ptr()
+            else:
+                if not isinstance(state, np.ndarray) or state.dtype != self.fdx or not state.flags.c_contiguous or not state.flags.writeable:
+                    raise ValueError(f"state must be a writable C-contiguous numpy array of dtype {np.dtype(self.fdx).name} (it is updated in place) or a device tensor")
+                if state.shape != shape:
+                    raise ValueError(f"state must have shape {shape}, got {state.shape}")
+                sp = state.ctypes.data
+        return self._grid_call("sdft_cross_smooth_n", x, every_rows, every, first, (bin0, nb, float(decay), C.c_void_p(sp)), npairs, nb, self.fdx, out)
+
     def set_array(self, chan):
         """Installs an array in the plan (``sdft_hip_set_array``; the list is copied): an ordered list of distinct channels, the
         elements of the array whose covariance :meth:`covariance` forms.  An int n means the channels ``0 ... n - 1``; an empty list
@@ -746,6 +777,21 @@ def smooth_decay(time_constant_samples: float) -> float:
     if not tau > 0:
         raise ValueError(f"the time constant must be positive, got {time_constant_samples!r}")
     return float(np.exp(-1.0 / tau))
+
+
+def coherence(s_ab, s_aa, s_bb):
+    """The magnitude-squared coherence of :meth:`SDFT.cross_smooth`'s averages: ``|s_ab|**2 / (s_aa * s_bb)`` with the real parts
+    of the auto-spectra ``s_aa`` and ``s_bb`` (the rows of the pairs ``(a, a)`` and ``(b, b)``; real arrays are taken as they
+    are), in float64; NaN where ``s_aa * s_bb`` is 0.  Takes numpy arrays or tensors (which are copied to the host).  Between 0
+    and 1 up to rounding for averages of one call with one decay."""
+    def host(v):
+        return np.asarray(v.detach().cpu().numpy() if _is_tensor(v) else v)
+    ab = host(s_ab).astype(np.complex128)
+    aa, bb = (host(v).real.astype(np.float64) for v in (s_aa, s_bb))
+    den = aa * bb
+    with np.errstate(divide="ignore", invalid="ignore"):
+        c = (ab.real * ab.real + ab.imag * ab.imag) / den
+    return np.where(den == 0, np.nan, c)
 
 
 HOLDS = {"max": 0, "min": 1, 0: 0, 1: 1}                     # SDFT.power_peak's hold -> enum sdft_hip_hold
