@@ -41,6 +41,8 @@ const char* sdft_hip_last_error(void);
                                         std::size_t bin0, std::size_t nbins, int hold, void* peaks);                   \
   long sdft_hip_sdft_power_smooth_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, \
                                           std::size_t bin0, std::size_t nbins, double decay, void* state, void* smooth); \
+  long sdft_hip_sdft_smooth_peak_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, \
+                                         std::size_t bin0, std::size_t nbins, double decay, int hold, void* state, void* peaks); \
   long sdft_hip_sdft_power_moments_n_##SUF(void* plan, std::size_t n, const TD* samples, std::size_t every, std::size_t first, \
                                            std::size_t bin0, std::size_t nbins, void* moments);                        \
   int sdft_hip_set_filterbank_##SUF(void* plan, std::size_t nbands, const std::size_t* band_bin0, const std::size_t* band_nbins, \
@@ -109,6 +111,7 @@ namespace sdft
       static long sdft_power_sum_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_power_sum_n_##SUF(p, n, x, e, f, b, k, d); } \
       static long sdft_power_peak_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, int h, void* d) { return sdft_hip_sdft_power_peak_n_##SUF(p, n, x, e, f, b, k, h, d); } \
       static long sdft_power_smooth_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, double a, void* s, void* d) { return sdft_hip_sdft_power_smooth_n_##SUF(p, n, x, e, f, b, k, a, s, d); } \
+      static long sdft_smooth_peak_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, double a, int h, void* s, void* d) { return sdft_hip_sdft_smooth_peak_n_##SUF(p, n, x, e, f, b, k, a, h, s, d); } \
       static long sdft_power_moments_n(void* p, std::size_t n, const TD* x, std::size_t e, std::size_t f, std::size_t b, std::size_t k, void* d) { return sdft_hip_sdft_power_moments_n_##SUF(p, n, x, e, f, b, k, d); } \
       static int set_filterbank(void* p, std::size_t nb, const std::size_t* b0, const std::size_t* bn, const void* w) { return sdft_hip_set_filterbank_##SUF(p, nb, b0, bn, w); } \
       static std::size_t filterbank_bands(const void* p) { return sdft_hip_filterbank_bands_##SUF(p); } \
@@ -283,6 +286,27 @@ namespace sdft
       {
         const char* e = sdft_hip_last_error();
         throw std::runtime_error(std::string("sdft_hip_sdft_power_smooth_n: ") + (e ? e : "failed"));
+      }
+      return static_cast<std::size_t>(rows);
+    }
+
+    /**
+     * Smoothed peak-hold analysis (sdft_hip_sdft_smooth_peak_n): power_peak()'s grid, windows, head row and layout with
+     * power_smooth()'s sequence for the term: row r of out, dense (rows, nbins) [(channels, rows, nbins)], is the largest
+     * (Hold::Max) or the smallest (Hold::Min) over the r-th window of s = a * s + (1 - a) * p, a = F(decay), advanced at every
+     * sample and taken after the sample's update; s does not restart at a window.  state is (nbins) [(channels, nbins)] numbers
+     * of the band, host or device memory, read (s before the first sample) and written (s after the last); nullptr starts from
+     * zero and drops the end value.  A stream passes state and sdft_every()'s next first from call to call and, when first > 0,
+     * takes the larger / smaller of row 0 and the previous call's last row.  Returns the number of rows written.
+     **/
+    std::size_t smooth_peak(const std::size_t nsamples, const T* samples, const std::size_t every, const std::size_t first,
+                            const std::size_t bin0, const std::size_t nbins, const double decay, const Hold hold, F* const state, F* const out)
+    {
+      const long rows = api::sdft_smooth_peak_n(plan_, nsamples, samples, every, first, bin0, nbins, decay, static_cast<int>(hold), state, out);
+      if (rows < 0)
+      {
+        const char* e = sdft_hip_last_error();
+        throw std::runtime_error(std::string("sdft_hip_sdft_smooth_peak_n: ") + (e ? e : "failed"));
       }
       return static_cast<std::size_t>(rows);
     }

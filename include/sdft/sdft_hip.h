@@ -307,6 +307,62 @@ long sdft_hip_sdft_power_smooth_n(sdft_t* sdft, const sdft_size_t nsamples, cons
                                   const sdft_size_t bin0, const sdft_size_t nbins,
                                   const double decay, sdft_fd_t* state, sdft_fd_t* smooth) SDFT_HIP_SYMBOL(sdft_power_smooth_n);
 
+/* ---- smoothed peak-hold analysis -------------------------------------------------------------------
+   What hosts compose from the three detectors above: the smallest (hold = sdft_hip_hold_min: the noise floor of minimum
+   statistics, which takes its minimum over the smoothed estimate, not over raw powers) or the largest (hold = sdft_hip_hold_max:
+   smoothed max-hold, envelope peak) of the SMOOTHED power over windows of samples, without storing a smoothed row per sample.
+   The sequence is sdft_hip_sdft_power_smooth_n's, exactly: with p[t][k] what sdft_hip_sdft_power_n stores at every == 1,
+   first == 0, in sdft_fd_t and with no fused multiply-add,
+     a = (sdft_fd_t)decay     b = (sdft_fd_t)1 - a     s[-1] = state (zero if state == NULL)
+     s[t] = fl( fl(a * s[t-1]) + fl(b * p[t]) )          at EVERY sample
+   The grid, the windows, the head row, rows = (first > 0 && nsamples > 0 ? 1 : 0) + (rows of sdft_hip_sdft_every_n), the next
+   call's first, every > nsamples, the band, host or device pointers (option "async" applies to device pointers) and the layout
+   -- peaks is [rows][nbins], dense, aligned to sizeof(sdft_fd_t) only; batched plans: samples [channels][nsamples], peaks
+   [channels][rows][nbins] -- are sdft_hip_sdft_power_peak_n's, unchanged.  Row r holds, for bin0 <= k < bin0 + nbins, the extreme
+   by that call's rule (a NaN sticks, anything else is one of the terms) over the r-th window of s[t][k], s[t] taken after sample
+   t's update.  state is [channels][nbins] (the bins of the band only), read and written as by sdft_hip_sdft_power_smooth_n: on
+   entry s before the call's first sample, on return s after its last; host or device memory whatever the other pointers are;
+   NULL: the call starts from zero and drops the end value.  A stream cut into calls passes state and the next first along and
+   combines a call's head row (first > 0) with the previous call's last row by fmax / fmin.  s does not restart at a window: only
+   the held extreme does.  A call on host memory beyond option "stage_bytes" goes in time segments, with state passed along on
+   the device and head rows joined by the rule; "last_segments" then answers their number.
+   A long call cuts time into chunks ("last_chunks").  The extreme of s over a window cannot be formed from a recursion started
+   at +0 and corrected afterwards, so here the carries come before the rows: a first pass steps the recursion of every chunk for
+   its end value only and writes no row, an ordered scan turns the end values into S_c, the value of s before chunk c (the scan
+   of sdft_hip_sdft_power_smooth_n), and a second pass steps every chunk again from S_c and holds.  No row is corrected
+   afterwards, and a long call steps the recurrence twice.
+   Promised.
+   (1) The same plan, options and input give the same bits on every run: no atomics.
+   (2) A call of one time chunk ("last_chunks" = 1; every call shorter than 512 samples is one) is bit for bit the extreme over
+       each window of the sequential expression above, evaluated on the reference's powers, wherever sdft_sdft_n is bit-identical
+       to the reference (FD float, FD double with option "carry" = 1, calls shorter than 512 samples) -- for any every, first,
+       band, hold, pointer placement and staging -- and the returned state is the loop's end value.  every == 1, first == 0 then
+       gives sdft_hip_sdft_power_smooth_n's rows bit for bit.
+   (3) A stream cut into one-chunk calls that pass state and the next first along, head rows joined by fmax / fmin, has the bits
+       of (2) over the whole signal, wherever it is cut.
+   (4) decay == 0 gives sdft_hip_sdft_power_peak_n's values bit for bit for finite powers, on every route and any chunking.
+   (5) Calls of several chunks hold exactly: the rows at (every, first) are bit for bit the extreme over each window of the rows
+       the same call gives at (1, 0) when both cut time alike ("last_chunk_len"), and the returned state is the last of those
+       rows.  Against the exact recursion: with u = 2^-24 (float) or 2^-53 (double), s the exact recursion on the sdft_fd_t terms
+       and the rounded coefficients, peak its extreme over the window and M the largest of the incoming state and s[tau],
+       tau <= t, barring underflow
+         |peaks - peak| <= 8 u M / (1 - a)
+       and likewise the returned state (|ext(x') - ext(x)| <= max |x' - x|; inside a chunk the values are the sequential
+       recursion from S_c, so an element's error is a convex mix of the scan's, 5, and the recursion's own, 2 -- DESIGN.md has
+       the derivation; 8 is kept so that one bound serves both smoothed calls).  On the routes that are not bit-identical the
+       power call's term deviation comes on top: 2.1e-11 of the largest power, with no factor 1 / (1 - a).
+   (6) The stream state of every channel is afterwards the one sdft_sdft_n of the same samples leaves -- bins outside the band
+       step every sample too -- so any other entry point may follow.
+   The call is never resident, pipelined or fused and always runs its own kernel ("last_kernel" = 17).  Returns the number of rows
+   written (0 only for nsamples == 0), or -1 with sdft_hip_last_error() set, the stream state and *state untouched: a NULL plan,
+   every == 0, nbins == 0, bin0 + nbins > dftsize, hold neither 0 nor 1, a decay that is NaN, negative or not below 1 after
+   rounding to sdft_fd_t, peaks == NULL with rows > 0, or a workspace that cannot be reserved. */
+long sdft_hip_sdft_smooth_peak_n(sdft_t* sdft, const sdft_size_t nsamples, const sdft_td_t* samples,
+                                 const sdft_size_t every, const sdft_size_t first,
+                                 const sdft_size_t bin0, const sdft_size_t nbins,
+                                 const double decay, const int hold,
+                                 sdft_fd_t* state, sdft_fd_t* peaks) SDFT_HIP_SYMBOL(sdft_smooth_peak_n);
+
 /* ---- power-moments analysis ------------------------------------------------------------------------
    The one statistic of the power that no pooled output yields because it is not linear in it: the second moment.  With the sum
    of the power it gives the variance of the power per bin, the spectral kurtosis (the RFI flagger of radio astronomy, the
@@ -779,7 +835,7 @@ double sdft_hip_time_hops(sdft_t* sdft, size_t hops, size_t hop, const sdft_td_t
    "relay_flow", "relay_groups", "chain_debug", "inverse_nt", "inverse_nt_skip_mb", "inverse_step", "inverse_ordered", "host_direct", "copy_streams", "prefix_cells", "array_group", "mix_group", "mix_block" (sdft_capi.inc names what each selects);
    get_option "test_hooks" = 1 in that build.
    get_option additionally answers "tiles", "bins_per_lane", "row_slots", "last_chunks",
-   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis, 6 pooled power analysis, 7 filterbank analysis, 8 pooled cross-spectrum analysis, 9 array covariance analysis, 10 channel-mix analysis, 11 peak-hold analysis), 12 (lag-product analysis), 13 (power-moments analysis), 14 (band-peak analysis), 15 (smoothed power analysis) or 16 (smoothed cross-spectrum analysis), "last_segments", "last_fused",
+   "last_chunk_len", "last_kernel" (1 tiles, 2 row groups, 3 hop, 4 decimated analysis, 5 power-spectrogram analysis, 6 pooled power analysis, 7 filterbank analysis, 8 pooled cross-spectrum analysis, 9 array covariance analysis, 10 channel-mix analysis, 11 peak-hold analysis), 12 (lag-product analysis), 13 (power-moments analysis), 14 (band-peak analysis), 15 (smoothed power analysis), 16 (smoothed cross-spectrum analysis) or 17 (smoothed peak-hold analysis), "last_segments", "last_fused",
    "last_filterbank_launches" (forward_filterbank_kernel launches of the last filterbank call, over all of its host segments: more than its carry segments once its pieces exceed the workspace bound),
    "last_band_peak_launches" (its twin: forward_band_peak_kernel launches of the last band-peak call),
    "last_chain", "last_fused_exact", "last_fused_fold", "last_process_path" (1 fused kernel, 2 hop pair, 3 two-pass),

@@ -26,7 +26,7 @@ LIB_HOOKS = os.path.join(OUT_DIR, "libsdft_hip_hooks.so")
 ARCH = "gfx950"
 COMBOS = ("f32f64", "f32f32", "f64f64", "f64f32")
 SOURCES = ["sdft_common.hip"] + [f"sdft_capi_{c}.hip" for c in COMBOS]
-KERNEL_FILES = ["sdft_base.hpp", "sdft_carry_fast.hpp", "sdft_carry_exact.hpp", "sdft_forward.hpp", "sdft_forward_every.hpp", "sdft_forward_power.hpp", "sdft_forward_power_sum.hpp", "sdft_forward_power_peak.hpp", "sdft_forward_power_smooth.hpp", "sdft_forward_cross_sum.hpp", "sdft_forward_cross_smooth.hpp", "sdft_forward_lag_sum.hpp", "sdft_forward_power_moments.hpp", "sdft_forward_covariance.hpp", "sdft_forward_mix.hpp", "sdft_forward_filterbank.hpp", "sdft_forward_band_peak.hpp",
+KERNEL_FILES = ["sdft_base.hpp", "sdft_carry_fast.hpp", "sdft_carry_exact.hpp", "sdft_forward.hpp", "sdft_forward_every.hpp", "sdft_forward_power.hpp", "sdft_forward_power_sum.hpp", "sdft_forward_power_peak.hpp", "sdft_forward_power_smooth.hpp", "sdft_forward_cross_sum.hpp", "sdft_forward_cross_smooth.hpp", "sdft_forward_smooth_peak.hpp", "sdft_forward_lag_sum.hpp", "sdft_forward_power_moments.hpp", "sdft_forward_covariance.hpp", "sdft_forward_mix.hpp", "sdft_forward_filterbank.hpp", "sdft_forward_band_peak.hpp",
                 "sdft_forward_hop.hpp",
                 "sdft_ops.hpp", "sdft_forward_rows.hpp", "sdft_fused.hpp", "sdft_inverse.hpp"]      # in include order (sdft_kernels.hpp)
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hpp", ".inc")))            # everything a translation unit may include

@@ -58,6 +58,7 @@ def typed_signatures(combo: str):
         "sdft_power_sum_n": (C.c_long, [vp, sz, vp, sz, sz, sz, sz, vp]),
         "sdft_power_peak_n": (C.c_long, [vp, sz, vp, sz, sz, sz, sz, C.c_int, vp]),
         "sdft_power_smooth_n": (C.c_long, [vp, sz, vp, sz, sz, sz, sz, C.c_double, vp, vp]),
+        "sdft_smooth_peak_n": (C.c_long, [vp, sz, vp, sz, sz, sz, sz, C.c_double, C.c_int, vp, vp]),
         "sdft_cross_smooth_n": (C.c_long, [vp, sz, vp, sz, sz, sz, sz, C.c_double, vp, vp]),
         "sdft_lag_sum_n": (C.c_long, [vp, sz, vp, sz, sz, sz, sz, vp]),
         "sdft_power_moments_n": (C.c_long, [vp, sz, vp, sz, sz, sz, sz, vp]),

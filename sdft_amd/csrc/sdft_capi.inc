@@ -111,6 +111,10 @@ long SDFT_FN(sdft_power_moments_n)(void* p, size_t n, const SDFT_TD* x, size_t e
 long SDFT_FN(sdft_power_smooth_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, size_t bin0, size_t nbins, double decay,
                                   SDFT_FD* state, SDFT_FD* smooth)
 { return SDFT_GRID_CALL(sdft_power_smooth_n, n, x, every, first, bin0, nbins, decay, state, smooth); }
+// smoothed peak-hold analysis: the largest or smallest of that average over the windows of the grid; see sdft_hip.h
+long SDFT_FN(sdft_smooth_peak_n)(void* p, size_t n, const SDFT_TD* x, size_t every, size_t first, size_t bin0, size_t nbins, double decay, int hold,
+                                 SDFT_FD* state, SDFT_FD* peaks)
+{ return SDFT_GRID_CALL(sdft_smooth_peak_n, n, x, every, first, bin0, nbins, decay, hold, state, peaks); }
 // filterbank analysis: weighted band sums of those powers on the grid; see sdft_hip.h
 int SDFT_FN(set_filterbank)(void* p, size_t nbands, const size_t* band_bin0, const size_t* band_nbins, const SDFT_FD* weights)
 {

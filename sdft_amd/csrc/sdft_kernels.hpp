@@ -29,6 +29,10 @@
 //                          for the sums -- the one-pole average of A conj(B) per component, advanced at every sample and stored on the
 //                          grid; smooth_scan_kernel and smooth_fix_kernel carry it across the time chunks as 2 * nbins real numbers
 //                          per pair (sdft_hip_sdft_cross_smooth_n)
+//   sdft_forward_smooth_peak.hpp K1os forward_smooth_peak_kernel: the peak-hold kernel with the smoothed power kernel's recursion in the
+//                          loop -- the largest or the smallest of the one-pole average over each window; every chunk starts from the
+//                          value smooth_scan_kernel left for it after a carry pass of forward_power_smooth_kernel, peak_rows_kernel
+//                          combines the pieces of the windows a chunk boundary cuts (sdft_hip_sdft_smooth_peak_n)
 //   sdft_forward_lag_sum.hpp K1l forward_lag_sum_kernel: the pooled power kernel with the cross-spectrum kernel's term between a row and
 //                          the row before it -- X[t] conj(X[t - 1]) of one channel, the previous row of a chunk's first sample
 //                          demodulated from the chunk's carry-in (sdft_hip_sdft_lag_sum_n)
@@ -81,6 +85,7 @@
 #include "sdft_forward_power_smooth.hpp"
 #include "sdft_forward_cross_sum.hpp"
 #include "sdft_forward_cross_smooth.hpp"
+#include "sdft_forward_smooth_peak.hpp"
 #include "sdft_forward_lag_sum.hpp"
 #include "sdft_forward_power_moments.hpp"
 #include "sdft_forward_covariance.hpp"

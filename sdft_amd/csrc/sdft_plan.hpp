@@ -205,7 +205,7 @@ class Plan
   long opt_prefix_cells = 1;     // test hook: the prefix-cell route of long calls (logic::ForwardQuery::prefix_cells)
   long last_prefix = 0;          // the last analysis call took it (one pre-pass launch: prefix_cells_kernel)
 
-  long last_kernel = 0;          // 1 = forward_kernel (independent tiles), 2 = forward_rows_kernel, 3 = hop, 4 = forward_every_kernel, 5 = forward_power_kernel, 6 = forward_pooled_power_kernel, 7 = forward_filterbank_kernel, 8 = forward_cross_sum_kernel, 9 = forward_covariance_kernel, 10 = forward_mix_kernel, 11 = forward_power_peak_kernel, 12 = forward_lag_sum_kernel, 13 = forward_power_moments_kernel, 14 = forward_band_peak_kernel, 15 = forward_power_smooth_kernel, 16 = forward_cross_smooth_kernel
+  long last_kernel = 0;          // 1 = forward_kernel (independent tiles), 2 = forward_rows_kernel, 3 = hop, 4 = forward_every_kernel, 5 = forward_power_kernel, 6 = forward_pooled_power_kernel, 7 = forward_filterbank_kernel, 8 = forward_cross_sum_kernel, 9 = forward_covariance_kernel, 10 = forward_mix_kernel, 11 = forward_power_peak_kernel, 12 = forward_lag_sum_kernel, 13 = forward_power_moments_kernel, 14 = forward_band_peak_kernel, 15 = forward_power_smooth_kernel, 16 = forward_cross_smooth_kernel, 17 = forward_smooth_peak_kernel
 
   // device-resident stream state
   DevBuf<fdx> d_tw, d_syn, d_wtab;
@@ -613,6 +613,7 @@ class Plan
   // FILTERBANK: filterbank analysis (sdft_filterbank_n) -- forward_filterbank_kernel stores the band sums of the plan's filterbank
   // BAND_PEAK: band-peak analysis (sdft_band_peak_n) -- forward_band_peak_kernel stores per band of that filterbank the largest weighted power and its bin, as a pair; fbk as FILTERBANK's, a pair for a number
   // CROSS_SUM: cross-spectrum analysis (sdft_cross_sum_n) -- forward_cross_sum_kernel sums A conj(B) of the plan's pairs over the grid's windows
+  // SMOOTH_PEAK: smoothed peak-hold analysis (sdft_smooth_peak_n) -- forward_smooth_peak_kernel holds the largest or smallest of POWER_SMOOTH's average over POWER_PEAK's windows; in a call of several chunks after a carry pass of forward_power_smooth_kernel and smooth_scan_kernel
   // CROSS_SMOOTH: smoothed cross-spectrum analysis (sdft_cross_smooth_n) -- forward_cross_smooth_kernel runs the one-pole average of that term at every sample and stores it on the grid; the carry across chunks is POWER_SMOOTH's over 2 * band numbers per pair
   // LAG_SUM: lag-product analysis (sdft_lag_sum_n) -- forward_lag_sum_kernel sums X[t] conj(X[t - 1]) of every channel over those windows; cross has the plan's channels in the pairs' place and no items
   // POWER_MOMENTS: power-moments analysis (sdft_power_moments_n) -- forward_power_moments_kernel sums the power and its square of every channel over those windows, as (s1, s2) pairs; cross as LAG_SUM's
@@ -622,9 +623,10 @@ class Plan
   {
     enum Kind : int { PLAIN = 0, FUSE = -1, EVERY = logic::FK_EVERY, POWER = logic::FK_POWER, POWER_SUM = logic::FK_POWER_SUM, FILTERBANK = logic::FK_FILTERBANK,
                       CROSS_SUM = logic::FK_CROSS_SUM, COVARIANCE = logic::FK_COVARIANCE, MIX = logic::FK_MIX, POWER_PEAK = logic::FK_POWER_PEAK, LAG_SUM = logic::FK_LAG_SUM,
-                      POWER_MOMENTS = logic::FK_POWER_MOMENTS, BAND_PEAK = logic::FK_BAND_PEAK, POWER_SMOOTH = logic::FK_POWER_SMOOTH, CROSS_SMOOTH = logic::FK_CROSS_SMOOTH };
+                      POWER_MOMENTS = logic::FK_POWER_MOMENTS, BAND_PEAK = logic::FK_BAND_PEAK, POWER_SMOOTH = logic::FK_POWER_SMOOTH, CROSS_SMOOTH = logic::FK_CROSS_SMOOTH, SMOOTH_PEAK = logic::FK_SMOOTH_PEAK };
     Kind kind = PLAIN;
-    int hold = 0;                                            // POWER_PEAK
+    int hold = 0;                                            // POWER_PEAK, SMOOTH_PEAK
+    const SmoothPeakArgs<FD>* speak = nullptr;               // SMOOTH_PEAK
     const PowerSmoothArgs<FD>* smooth = nullptr;             // POWER_SMOOTH
     const FuseArgs<TD, FD>* fuse = nullptr;                  // FUSE
     const EveryGrid* every = nullptr;                        // EVERY
@@ -642,6 +644,7 @@ class Plan
     static ForwardCall power_sum(const PowerSumArgs<FD>& a) { ForwardCall c = of(POWER_SUM); c.psum = &a; return c; }
     static ForwardCall power_peak(const PowerSumArgs<FD>& a, int hold) { ForwardCall c = of(POWER_PEAK); c.psum = &a; c.hold = hold; return c; }
     static ForwardCall power_smooth(const PowerSmoothArgs<FD>& a) { ForwardCall c = of(POWER_SMOOTH); c.smooth = &a; return c; }
+    static ForwardCall smooth_peak(const SmoothPeakArgs<FD>& a, int hold) { ForwardCall c = of(SMOOTH_PEAK); c.speak = &a; c.hold = hold; return c; }
     static ForwardCall filterbank(const FilterbankArgs<FD>& a) { ForwardCall c = of(FILTERBANK); c.fbk = &a; return c; }
     static ForwardCall band_peak(const FilterbankArgs<FD>& a) { ForwardCall c = of(BAND_PEAK); c.fbk = &a; return c; }
     static ForwardCall cross_sum(const CrossSumArgs<FD>& a) { ForwardCall c = of(CROSS_SUM); c.cross = &a; return c; }
@@ -697,6 +700,7 @@ class Plan
     q.power_sum = c.kind == ForwardCall::POWER_SUM;
     q.power_peak = c.kind == ForwardCall::POWER_PEAK;
     q.power_smooth = c.kind == ForwardCall::POWER_SMOOTH;
+    q.smooth_peak = c.kind == ForwardCall::SMOOTH_PEAK;
     q.filterbank = c.kind == ForwardCall::FILTERBANK;
     q.band_peak = c.kind == ForwardCall::BAND_PEAK;
     q.cross_sum = c.kind == ForwardCall::CROSS_SUM;
@@ -961,6 +965,32 @@ class Plan
         sm.ends = d_smooth_ws.p; sm.pw = d_smooth_pw.p;
       }
     }
+    // smoothed peak-hold analysis: the peak-hold call's workspace of cut windows, and for a call of several chunks the smoothed
+    // power call's workspace and table; sc is what the carry pass and the scan see of the call -- no output, a grid that keeps no
+    // row, the call's state buffers (the row pass writes state_out again, after the scan, with the bits of its last sample)
+    SmoothPeakArgs<FD> sp{};
+    PowerSmoothArgs<FD> sc{};
+    if (c.speak)
+    {
+      sp = *c.speak;
+      const unsigned band = sp.rows.nbins_out;
+      if (!d_psum_ws.reserve(logic::power_sum_workspace(channels, (size_t)chunks, band))) return false;
+      sp.rows.ws = chunks > 1 ? d_psum_ws.p : nullptr;
+      if (chunks > 1)
+      {
+        if (!d_smooth_ws.reserve(logic::power_smooth_workspace(channels, (size_t)chunks, band))) return false;
+        if (smooth_pw_a != sp.a || smooth_pw_len != (size_t)r.len)
+        {
+          const std::vector<FD> table = logic::power_smooth_table<FD>(sp.a, (size_t)r.len);
+          smooth_pw_a = (FD)-1;                              // (as above)
+          if (!d_smooth_pw.reserve(table.size()) || !to_device(d_smooth_pw.p, table.data(), table.size() * sizeof(FD))) return false;
+          smooth_pw_a = sp.a; smooth_pw_len = (size_t)r.len;
+        }
+        sp.ends = d_smooth_ws.p;
+        const logic::SmoothPeakCarryGrid none = logic::smooth_peak_carry_grid(n);
+        sc = PowerSmoothArgs<FD>{nullptr, 0, sp.state_in, sp.state_out, d_smooth_ws.p, d_smooth_pw.p, sp.a, sp.b, none.every, none.first, sp.rows.bin0, band};
+      }
+    }
     // smoothed cross-spectrum analysis: the same workspace and table with the pairs for channels and rows of 2 * band numbers; xc is
     // what the scan and the fix-up see of the call
     CrossSmoothArgs<FD> xs{};
@@ -1077,6 +1107,10 @@ class Plan
       case K::POWER_SUM: if (!grid_fits(blocks)) return false; launch_forward_power_sum(fa, ps, (unsigned)blocks); break;
       case K::POWER_SMOOTH: if (!grid_fits(blocks)) return false; launch_forward_power_smooth(fa, sm, (unsigned)blocks); break;
       case K::CROSS_SMOOTH: if (!grid_fits(blocks)) return false; launch_forward_cross_smooth(fa, xs, (unsigned)blocks); break;
+      case K::SMOOTH_PEAK:                                   // one chunk: the rows at once; several: the carry pass first
+        if (!grid_fits(blocks)) return false;
+        if (chunks > 1) launch_forward_power_smooth(fa, sc, (unsigned)blocks); else launch_forward_smooth_peak(fa, sp, (unsigned)blocks, c.hold);
+        break;
       case K::POWER: if (!grid_fits(blocks)) return false; launch_forward_power(fa, *c.power, (unsigned)blocks); break;
       case K::EVERY: if (!grid_fits(blocks)) return false; launch_forward_every(fa, *c.every, (unsigned)blocks); break;
       }
@@ -1101,6 +1135,27 @@ class Plan
       if (!launch_smooth_scan(sm, n, chunks, r.len, r.shift, channels)) return false;
       const size_t kept = logic::every_rows(n, (size_t)sm.every, (size_t)sm.first);
       if (kept && !launch_smooth_fix(sm, kept, chunks, r.len, r.shift, channels)) return false;
+      SDFT_TRY(hipGetLastError());
+    }
+    // the smoothed peak-hold call of several chunks: the scan turns the carry pass's end values into the chunks' starts, the row
+    // pass runs over the same chunks (the segments' carries have all been waited for; it reads d_carry and writes the same half of
+    // the stream state with the same values as the carry pass did), then the windows a chunk boundary cut
+    if (chunks > 1 && c.speak)
+    {
+      if (!launch_smooth_scan(sc, n, chunks, r.len, r.shift, channels)) return false;
+      for (long sg = 0; sg < segments; ++sg)
+      {
+        const long j0 = chunks * sg / segments, j1 = chunks * (sg + 1) / segments;
+        const size_t groups = channels * (size_t)(j1 - j0);
+        fa.chunk0 = (unsigned)j0; fa.launch_chunks = (unsigned)(j1 - j0); fa.inv_chunks = inv32(fa.launch_chunks);
+        fa.xcd_map = logic::xcd_groups(r.xcd_map, groups);
+        fa.total_waves = (unsigned long long)groups * (unsigned long long)r.tiles;
+        const unsigned long long blocks = (fa.total_waves + kWavesPerBlock - 1) / kWavesPerBlock;
+        if (!grid_fits(blocks)) return false;
+        launch_forward_smooth_peak(fa, sp, (unsigned)blocks, c.hold);
+        SDFT_TRY(hipGetLastError());
+      }
+      if (!launch_peak_rows(sp.rows, n, chunks, r.len, r.shift, channels, c.hold)) return false;
       SDFT_TRY(hipGetLastError());
     }
     // the smoothed cross-spectrum call's: the same two kernels over its pairs

@@ -106,14 +106,14 @@
     return true;
   }
 
-  // ---- grid analysis calls: sdft_every_n and its twelve siblings ---------------------------------------------------------------
-  // What the thirteen share.  The stream state after a call is the one sdft_n leaves on the same samples.  A call is never resident,
+  // ---- grid analysis calls: sdft_every_n and its thirteen siblings ---------------------------------------------------------------
+  // What the fourteen share.  The stream state after a call is the one sdft_n leaves on the same samples.  A call is never resident,
   // pipelined or fused: whatever is in flight is retired / joined first, then one forward call on the plan's stream with the
   // call's own kernel (ForwardCall).  `rows` receives the row count.  Device samples and a device output take that one call; host
   // memory goes through device scratch in time segments of at most logic::grid_segment samples, each segment a call of its own
   // under the streaming contract, with its own first.
   // The every-grid calls (every, power, power_smooth, cross_smooth, filterbank, band_peak, mix) keep the rows of the samples first, first + every, ... < n; a segment
-  // keeps the rows of the grid that fall into it.  The pooled calls (power_sum, power_peak, power_moments, cross_sum, lag_sum, covariance) write
+  // keeps the rows of the grid that fall into it.  The pooled calls (power_sum, power_peak, smooth_peak, power_moments, cross_sum, lag_sum, covariance) write
   // one row per window the grid cuts the call into (logic::power_sum_window), row 0 the head window [0, first) when first > 0; a
   // segment that starts inside a window has a head row of its own, which is kept apart (the call's head buffer) and joined into
   // the row the segment before it ended with -- on the host for a host buffer, by a small kernel for a device buffer.
@@ -429,6 +429,44 @@
       const PowerSumArgs<FD> g{row0, row0_stride, rest, rest_stride, nullptr, p.grid.every, p.grid.first, (unsigned)bin0, (unsigned)nbins_out};
       return forward_device(p.m, p.td, p.td_stride, nullptr, 0, nullptr, ForwardCall::power_peak(g, hold));
     });
+  }
+  // smoothed peak-hold analysis (sdft_hip_sdft_smooth_peak_n): the largest (hold 0) or the smallest (hold 1) over the windows of the
+  // grid of sdft_power_smooth_n's sequence s, taken after every sample's step -- the peak-hold call's path (its head buffer, its
+  // join of the segments' head rows) with forward_smooth_peak_kernel, and sdft_power_smooth_n's travel of s: from the caller's state
+  // through the two halves of d_smooth_state, a forward call reading one and writing the other, the next segment of a call on host
+  // memory going on from there, and back to the caller once the whole call has succeeded.  A call in several segments reports
+  // their number as "last_segments".
+  bool sdft_smooth_peak_n(size_t n, const TD* x, size_t every, size_t first, size_t bin0, size_t nbins_out, double decay, int hold, FD* state,
+                          FD* peaks, size_t& rows)
+  {
+    if (!grid_args("sdft_hip_sdft_smooth_peak_n", n, every, first, true, bin0, nbins_out, logic::smooth_peak_refusal<FD>(hold, decay), true, peaks, "peaks", rows)) return false;
+    if (n == 0 || nbins == 0) return true;
+    const FD a = (FD)decay, b = (FD)1 - a;
+    const size_t count = channels * nbins_out;
+    bool state_device = false;
+    int cur = 0;                                             // the half of d_smooth_state that holds s
+    long pieces = 0;                                         // forward calls: more than one when host memory goes in segments
+    auto ready = [&] {
+      if (!d_smooth_state.reserve(2 * count)) return false;
+      state_device = state && on_device(state);
+      if (!state) SDFT_TRY(hipMemsetAsync(d_smooth_state.p, 0, count * sizeof(FD), stream));
+      else if (state_device) SDFT_TRY(hipMemcpyAsync(d_smooth_state.p, state, count * sizeof(FD), hipMemcpyDeviceToDevice, stream));
+      else if (!to_device(d_smooth_state.p, state, count * sizeof(FD))) return false;
+      return true;
+    };
+    if (!pooled_grid_call(n, x, every, first, peaks, rows, channels, nbins_out, d_psum_head, nullptr, hold, ready,
+                          [&](const GridPiece& p, FD* row0, size_t row0_stride, FD* rest, size_t rest_stride) {
+          const SmoothPeakArgs<FD> g{{row0, row0_stride, rest, rest_stride, nullptr, p.grid.every, p.grid.first, (unsigned)bin0, (unsigned)nbins_out},
+                                     d_smooth_state.p + cur * count, d_smooth_state.p + (cur ^ 1) * count, nullptr, a, b};
+          if (!forward_device(p.m, p.td, p.td_stride, nullptr, 0, nullptr, ForwardCall::smooth_peak(g, hold))) return false;
+          cur ^= 1; ++pieces;
+          return true;
+        })) return false;
+    if (pieces > 1) last_segments = pieces;                  // ("last_segments": the call went in that many time segments, each a call with its own carries)
+    if (!state) return true;
+    if (!state_device) return to_host(state, d_smooth_state.p + cur * count, count * sizeof(FD));
+    SDFT_TRY(hipMemcpyAsync(state, d_smooth_state.p + cur * count, count * sizeof(FD), hipMemcpyDeviceToDevice, stream));
+    return async || synchronize();
   }
   // ---- pooled cross-spectrum analysis ------------------------------------------------------------------------------------------
   // sdft_hip_set_pairs: the arrays are host memory and are copied; a refused list leaves the installed one as it is.  The work

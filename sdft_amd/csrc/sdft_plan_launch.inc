@@ -349,6 +349,22 @@
   {
     if (hold == logic::kHoldMin) launch_forward_power_peak_h<logic::kHoldMin>(fa, g, blocks); else launch_forward_power_peak_h<logic::kHoldMax>(fa, g, blocks);
   }
+  template <int HOLD> void launch_forward_smooth_peak_h(const ForwardArgs<FD>& fa, const SmoothPeakArgs<FD>& g, unsigned blocks)
+  {
+    constexpr int BPL = sizeof(fdx) == 16 ? 1 : 2;
+    const dim3 gr(blocks), b(kBlock);
+    switch (window)
+    {
+      case WIN_HANN:     hipLaunchKernelGGL((forward_smooth_peak_kernel<FD, BPL, WIN_HANN, HOLD>), gr, b, 0, stream, fa, g); break;
+      case WIN_HAMMING:  hipLaunchKernelGGL((forward_smooth_peak_kernel<FD, BPL, WIN_HAMMING, HOLD>), gr, b, 0, stream, fa, g); break;
+      case WIN_BLACKMAN: hipLaunchKernelGGL((forward_smooth_peak_kernel<FD, BPL, WIN_BLACKMAN, HOLD>), gr, b, 0, stream, fa, g); break;
+      default:           hipLaunchKernelGGL((forward_smooth_peak_kernel<FD, BPL, WIN_BOXCAR, HOLD>), gr, b, 0, stream, fa, g); break;
+    }
+  }
+  void launch_forward_smooth_peak(const ForwardArgs<FD>& fa, const SmoothPeakArgs<FD>& g, unsigned blocks, int hold)
+  {
+    if (hold == logic::kHoldMin) launch_forward_smooth_peak_h<logic::kHoldMin>(fa, g, blocks); else launch_forward_smooth_peak_h<logic::kHoldMax>(fa, g, blocks);
+  }
   void launch_forward_power_smooth(const ForwardArgs<FD>& fa, const PowerSmoothArgs<FD>& g, unsigned blocks)
   {
     constexpr int BPL = sizeof(fdx) == 16 ? 1 : 2;

@@ -354,6 +354,54 @@ inline PowerSmoothFix power_smooth_fix(size_t t, long len, long shift)
 // nbins_out).  The items of the pairs come first and in the pairs' order: item i < npairs is unit i.
 inline size_t cross_smooth_unit_row(size_t nbins_out) { return 2 * nbins_out; }
 
+// ---- smoothed peak-hold analysis (sdft_hip_sdft_smooth_peak_n) -------------------------------------------------------------------
+// Row r holds, per bin, peak_hold over the r-th window of the peak-hold call's grid (power_sum_rows, power_sum_window) of the
+// smoothed power call's sequence s[t], taken after sample t's step.  The extreme of s0[t] + a^j * S_c over a window is not a
+// function of the extreme of s0[t], so the rows cannot be formed from +0 and fixed up: the carries come before the rows.  A call
+// of several chunks runs forward_power_smooth_kernel on a grid that keeps no row (smooth_peak_carry_grid) for the chunks' end
+// values E_c, smooth_scan_kernel for S_c, then forward_smooth_peak_kernel, whose chunk c >= 1 starts from S_c
+// (power_smooth_slot), then peak_rows_kernel for the windows a chunk boundary cuts.  A call of one chunk is one launch and the
+// sequential loop bit for bit.
+// why a call is refused beyond the grid and the band: the hold first, then the decay (nullptr: neither)
+template <typename T> inline const char* smooth_peak_refusal(int hold, double decay)
+{
+  if (!peak_hold_ok(hold)) return "hold must be sdft_hip_hold_max (0) or sdft_hip_hold_min (1)";
+  if (!power_smooth_decay_ok<T>(decay)) return "decay must be at least 0 and less than 1 after rounding to sdft_fd_t";
+  return nullptr;
+}
+// the grid the carry pass gives forward_power_smooth_kernel: its first point lies beyond the call's n samples, so no row is stored
+struct SmoothPeakCarryGrid { size_t every, first; };
+inline SmoothPeakCarryGrid smooth_peak_carry_grid(size_t n) { return {1, n}; }
+// the scheme on a host, for one bin: p[0 .. n) are the terms, s_in the incoming state, the chunks are [c * len - shift, ...) as
+// chunk_begin cuts them.  Writes s[t] after every sample to s_out[0 .. n) as the kernels form it -- the carry pass from +0, the
+// scan with P[j] = power_smooth_table, the row pass from S_c -- and returns the state the call leaves (the last s).
+template <typename T> inline T smooth_peak_scheme(const T* p, size_t n, T a, T s_in, long len, long shift, T* s_out)
+{
+  const T b = (T)1 - a;
+  const long chunks = n ? chunk_of(n - 1, len, shift) + 1 : 0;
+  const std::vector<T> pw = power_smooth_table<T>(a, (size_t)len);
+  std::vector<T> start((size_t)std::max(chunks, 1L), s_in);
+  T S = s_in;
+  for (long c = 0; c < chunks; ++c)
+  {
+    const size_t t0 = chunk_begin(c, len, shift), t1 = std::min(n, chunk_begin(c + 1, len, shift));
+    volatile T e = c ? (T)0 : s_in;                        // (volatile: each product and sum is rounded to T, no contraction)
+    for (size_t t = t0; t < t1; ++t) { volatile T as = a * e, bp = b * p[t]; e = as + bp; }
+    start[(size_t)c] = S;
+    if (c == 0) S = e;
+    else { volatile T ps = pw[t1 - t0] * S; S = ps + e; }
+  }
+  T s = s_in;
+  for (long c = 0; c < chunks; ++c)
+  {
+    const size_t t0 = chunk_begin(c, len, shift), t1 = std::min(n, chunk_begin(c + 1, len, shift));
+    volatile T v = start[(size_t)c];
+    for (size_t t = t0; t < t1; ++t) { volatile T as = a * v, bp = b * p[t]; v = as + bp; s_out[t] = v; }
+    s = v;
+  }
+  return s;
+}
+
 // ---- pooled cross-spectrum analysis (sdft_hip_sdft_cross_sum_n) ------------------------------------------------------------------
 // Row r of pair p = (a, b) is the sum over the r-th window of the pooled power call's grid of A conj(B), A and B the windowed bins
 // of the channels a and b.  A wave of forward_cross_sum_kernel steps the recurrences of the two channels of ONE work item, so the
@@ -1025,6 +1073,7 @@ struct ForwardQuery
   bool band_peak = false;                 // band-peak analysis (forward_band_peak_kernel) on the grid of power_every: the filterbank call's route and chunk choice (never with filterbank)
   bool cross_sum = false;                 // pooled cross-spectrum analysis (forward_cross_sum_kernel) of ...
   size_t cross_items = 0;                 // ... this many work items (logic::cross_items), which take the channels' place in the launch
+  bool smooth_peak = false;               // smoothed peak-hold analysis (forward_smooth_peak_kernel): the pooled power call's route and chunk choice (never with another of these)
   bool cross_smooth = false;              // smoothed cross-spectrum analysis (forward_cross_smooth_kernel): cross_sum's items, route and chunk choice (never with cross_sum)
   bool covariance = false;                // array covariance analysis (forward_covariance_kernel): cross_items counts its block items (logic::covariance_items)
   bool mix = false;                       // channel-mix analysis (forward_mix_kernel) on the grid of power_every: cross_items counts its items (logic::mix_items)
@@ -1038,7 +1087,7 @@ struct ForwardQuery
        chain_L = 0, relay_flow = 1, segments = 0, xcd_map = 1, rows_f32 = 1, pipeline = 1;
   long prefix_cells = 1;                  // test hook: 0 = never the prefix-cell route, 1 = calls beyond kSelfMax, 2 = whatever the length
 };
-enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6, FK_FILTERBANK = 7, FK_CROSS_SUM = 8, FK_COVARIANCE = 9, FK_MIX = 10, FK_POWER_PEAK = 11, FK_LAG_SUM = 12, FK_POWER_MOMENTS = 13, FK_BAND_PEAK = 14, FK_POWER_SMOOTH = 15, FK_CROSS_SMOOTH = 16 };     // = get_option "last_kernel"
+enum ForwardKernel : int { FK_TILES = 1, FK_ROWS = 2, FK_HOP = 3, FK_EVERY = 4, FK_POWER = 5, FK_POWER_SUM = 6, FK_FILTERBANK = 7, FK_CROSS_SUM = 8, FK_COVARIANCE = 9, FK_MIX = 10, FK_POWER_PEAK = 11, FK_LAG_SUM = 12, FK_POWER_MOMENTS = 13, FK_BAND_PEAK = 14, FK_POWER_SMOOTH = 15, FK_CROSS_SMOOTH = 16, FK_SMOOTH_PEAK = 17 };     // = get_option "last_kernel"
 // carries: the single chunk's are the stream state (delta_kernel copies it); pre-pass partial sums + scan (carries from the
 // closed-form table); the serial exact pass (carry_exact_kernel); the relay form of the exact pass (carry_relay_kernel)
 enum CarryForm : int { CARRY_STATE = 0, CARRY_SUMS = 1, CARRY_SERIAL = 2, CARRY_RELAY = 3 };
@@ -1086,8 +1135,8 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   ForwardRoute r;
   const size_t nb = q.nbins, span = 2 * nb, n = q.n, ch = std::max<size_t>(q.channels, 1);
   const bool pow2 = (span & (span - 1)) == 0;
-  // the decimated, the power-spectrogram, the pooled power, the peak-hold, the lag-product, the power-moments, the smoothed power, the filterbank, the band-peak, the cross-spectrum, the smoothed cross-spectrum, the covariance and the mix analysis have the tile form only
-  const bool grid = q.every || q.power || q.power_sum || q.power_peak || q.lag_sum || q.power_moments || q.power_smooth || q.filterbank || q.band_peak || q.cross_sum || q.cross_smooth || q.covariance || q.mix;
+  // the decimated, the power-spectrogram, the pooled power, the peak-hold, the lag-product, the power-moments, the smoothed power, the filterbank, the band-peak, the cross-spectrum, the smoothed cross-spectrum, the smoothed peak-hold, the covariance and the mix analysis have the tile form only
+  const bool grid = q.every || q.power || q.power_sum || q.power_peak || q.lag_sum || q.power_moments || q.power_smooth || q.smooth_peak || q.filterbank || q.band_peak || q.cross_sum || q.cross_smooth || q.covariance || q.mix;
   // (channel, chunk) groups of a tile launch per chunk: the two cross-spectrum, the covariance and the mix call's are their work items
   const size_t lanes = (q.cross_sum || q.cross_smooth || q.covariance || q.mix) ? std::max<size_t>(q.cross_items, 1) : ch;
   const bool rows = !grid && rows_kernel_ok(nb, q.fdx_bytes, q.row_pointers, q.rows_kernel != 0, q.row_slots_max);
@@ -1115,12 +1164,12 @@ inline ForwardRoute forward_route(const ForwardQuery& q, GateOk&& gate_ok)
   {
     EveryQuery e;
     e.n = n; e.channels = lanes; e.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); e.exact = q.exact; e.forced_chunk = q.chunk; e.compute_units = q.compute_units;
-    c = (q.power_sum || q.power_peak || q.lag_sum || q.power_moments || q.power_smooth || q.cross_sum || q.cross_smooth || q.covariance) ? choose_power_sum_chunks(e) : (q.power || q.filterbank || q.band_peak || q.mix) ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
+    c = (q.power_sum || q.power_peak || q.lag_sum || q.power_moments || q.power_smooth || q.smooth_peak || q.cross_sum || q.cross_smooth || q.covariance) ? choose_power_sum_chunks(e) : (q.power || q.filterbank || q.band_peak || q.mix) ? choose_power_chunks(e, q.power_every) : choose_every_chunks(e);
   }
   else c = choose_chunks(chunk_query(q, rows, r.pipelined));
   r.chunks = c.chunks; r.len = c.len;
   r.tiles = tiles(nb, q.window, q.fdx_bytes, q.interior); r.interior = interior_lanes(q.window, q.fdx_bytes, q.interior);
-  r.kernel = q.mix ? FK_MIX : q.covariance ? FK_COVARIANCE : q.cross_smooth ? FK_CROSS_SMOOTH : q.cross_sum ? FK_CROSS_SUM : q.filterbank ? FK_FILTERBANK : q.band_peak ? FK_BAND_PEAK : q.power_smooth ? FK_POWER_SMOOTH : q.power_moments ? FK_POWER_MOMENTS : q.lag_sum ? FK_LAG_SUM : q.power_peak ? FK_POWER_PEAK : q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
+  r.kernel = q.mix ? FK_MIX : q.covariance ? FK_COVARIANCE : q.cross_smooth ? FK_CROSS_SMOOTH : q.cross_sum ? FK_CROSS_SUM : q.filterbank ? FK_FILTERBANK : q.band_peak ? FK_BAND_PEAK : q.smooth_peak ? FK_SMOOTH_PEAK : q.power_smooth ? FK_POWER_SMOOTH : q.power_moments ? FK_POWER_MOMENTS : q.lag_sum ? FK_LAG_SUM : q.power_peak ? FK_POWER_PEAK : q.power_sum ? FK_POWER_SUM : q.power ? FK_POWER : q.every ? FK_EVERY : rows ? FK_ROWS : FK_TILES;
   if (r.chunks == 1 && q.hop_kernel && nb >= 2 && !q.fuse && !grid) { r.kernel = FK_HOP; return r; }
 
   // self-carried chunks: every workgroup derives its carry-in from the raw samples (fold + one FFT in LDS) and forms

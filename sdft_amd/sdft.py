@@ -557,6 +557,35 @@ class SDFT:
                 sp = state.ctypes.data
         return self._grid_call("sdft_power_smooth_n", x, every_rows, every, first, (bin0, nb, float(decay), C.c_void_p(sp)), None, nb, self.fd, out)
 
+    def smooth_peak(self, x, decay: float, every: int = 1, first: int = 0, bins=None, hold="max", state=None, out=None):
+        """Smoothed peak-hold analysis (``sdft_hip_sdft_smooth_peak_n``): :meth:`power_peak`'s grid, windows, head row, shapes and
+        pointers with :meth:`power_smooth`'s sequence for the term: row r is the largest (``hold="max"`` or 0) or the smallest
+        (``hold="min"`` or 1: the noise floor of minimum statistics) over the r-th window of ``s = a * s + b * p``,
+        ``(a, b) = smooth_coefficients(decay, dtype)``, advanced at every sample and taken after the sample's update; ``s`` does not
+        restart at a window.  ``state`` is :meth:`power_smooth`'s: a numpy array or a device tensor (whatever ``x`` is) of shape
+        (nbins,) [(channels, nbins)] in the FD dtype, updated in place; ``None`` starts from zero and drops the end value.  A
+        stream passes ``state`` and :func:`every_next_first` from call to call and, with ``first > 0``, joins row 0 with the
+        previous call's last row by ``np.fmax`` / ``np.fmin``.  The plan's state advances over all n samples and all bins."""
+        self.api.clear()
+        every, first, bin0, nb = _grid_args(self.dftsize, every, first, bins)
+        if hold not in HOLDS:
+            raise ValueError(f"hold must be 'max' (0) or 'min' (1), got {hold!r}")
+        smooth_coefficients(decay, self.fd)                  # (raises for a decay the library would refuse)
+        sp = None
+        if state is not None:
+            batched = (x.dim() if _is_tensor(x) else np.ndim(x)) == 2
+            shape = (self.channels, nb) if batched else (nb,)
+            if _is_tensor(state):
+                self._check_tensor(state, "state", self.fd, shape)
+                sp = state.data_ptr()
+            else:
+                if not isinstance(state, np.ndarray) or state.dtype != self.fd or not state.flags.c_contiguous or not state.flags.writeable:
+                    raise ValueError(f"state must be a writable C-contiguous numpy array of dtype {np.dtype(self.fd).name} (it is updated in place) or a device tensor")
+                if state.shape != shape:
+                    raise ValueError(f"state must have shape {shape}, got {state.shape}")
+                sp = state.ctypes.data
+        return self._grid_call("sdft_smooth_peak_n", x, power_sum_rows, every, first, (bin0, nb, float(decay), HOLDS[hold], C.c_void_p(sp)), None, nb, self.fd, out)
+
     def power_moments(self, x, every: int = 1, first: int = 0, bins=None, out=None):
         """Power-moments analysis (``sdft_hip_sdft_power_moments_n``): :meth:`power_sum`'s grid, windows, head row and pointers,
         with two sums per window and bin -> real array of shape (rows, nbins, 2) [(channels, rows, nbins, 2) if batched] in the FD
